@@ -28,6 +28,9 @@ under `other_configs` (bf16 GloVe-300d batch 64 with its own roofline, UMPR-R ba
 4 views x 32 samples in fp32 and bf16, inference fp32 / bf16): 8 timed steps each; `--no-other-configs` skips them.
 `python bench.py --gpus N` without a launcher starts N workers, ends all of them when one dies and retries once with the async
 form of the gradient exchange if the in-stream form failed (spawn_workers).
+`--dump-outputs DIR` writes what the last timed step of the headline workload computed (prediction, loss, and a seeded
+sample of the parameters and gradients after it) as DIR/<name>.npy; inputs and weights are seeded, so two builds run with
+the same arguments can be compared output for output.
 """
 import argparse
 import ctypes
@@ -76,6 +79,8 @@ def parse():
     ap.add_argument("--other-steps", type=int, default=12, help="timed steps of each `other_configs` sub-line")
     ap.add_argument("--cpu-batch", type=int, default=0, help="batch of the CPU baseline sample (0: the GPU batch)")
     ap.add_argument("--cpu-steps", type=int, default=2)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
     return ap.parse_args()
 
 
@@ -352,6 +357,36 @@ def _roofline(w, fam, value, traffic_ok=True):
                                "training step) x samples/s against 8 TB/s"}
 
 
+DUMP_SAMPLE = 1 << 16          # elements kept of each parameter / gradient (the whole tensor if it is smaller)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, pred, loss, with_grads):
+    """What one step of the timed path gives its caller: `pred` and `loss`, and - a training step updates the model in
+    place - every parameter after the step and the gradient it computed (`param.<name>`, `grad.<name>`), float32.
+    Tensors larger than DUMP_SAMPLE elements are stored as the elements at a fixed seeded set of flat indices, so that
+    two builds run with the same arguments can be compared file for file."""
+    import numpy as np
+    import torch
+    arrays = {"pred": pred, "loss": loss}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p
+        if with_grads and p.grad is not None:
+            arrays["grad." + name] = p.grad
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.unique(np.random.default_rng(0).integers(0, t.numel(), DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.float().cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs would write more than {DUMP_LIMIT_BYTES} bytes"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    note(f"wrote {len(arrays)} arrays ({total / 2**20:.1f} MB) to {out_dir}")
+
+
 def workload_name(w):
     return (("UMPR-R (review_net_only)" if w.review_net_only else f"full UMPR, {w.views} view(s), 1 photo/view")
             + f", GloVe-{w.emb}d-shaped table {w.vocab}x{w.emb}, batch {w.batch}/GPU, "
@@ -424,13 +459,15 @@ def run_workload(w, env):
     L.fn["umpr_profile_enable"](1)
     t0 = time.perf_counter()
     for _ in range(w.steps):
-        _, loss = step()
+        pred, loss = step()
         losses.append(loss.detach().clone() if graphed is not None else loss.detach())   # a replayed graph rewrites its outputs
     t_issue = time.perf_counter() - t0        # host time to ENQUEUE the steps (no wait): close to dt => host-bound
     barrier()
     dt_local = dt = time.perf_counter() - t0
     L.fn["umpr_profile_enable"](0)
     note(f"{w.steps} steps in {dt:.3f} s")
+    if getattr(w, "dump_outputs", None) and rank == 0:    # before the h2d loop below runs more steps on the same model
+        dump_outputs(w.dump_outputs, model, pred, loss, with_grads=opt is not None and not getattr(w, "fwd_train", False))
     per_rank_ms = [1e3 * dt / w.steps]
     rccl_ranks = 1
     if parallel.active():
@@ -562,7 +599,8 @@ def main():
         if default_line:
             others = {}
             for name, over in OTHER_CONFIGS:
-                w = argparse.Namespace(**{**vars(args), **over, "steps": args.other_steps, "warmup": 5, "h2d": False})
+                w = argparse.Namespace(**{**vars(args), **over, "steps": args.other_steps, "warmup": 5, "h2d": False,
+                                          "dump_outputs": None})
                 try:
                     o, _ = run_workload(w, env)
                 except Exception as e:    # a sub-line must never cost the headline; say what happened

@@ -363,8 +363,9 @@ def gen_dataset():
             b = batch_loader([ds[i] for i in range(min(4, len(ds)))], ignore_photos=True)
             out["batch/" + name] = [t.tolist() for t in b]
     out["pad_reviews"] = pad_reviews([[[1, 2, 3], []], [[4]]])
+    # photo paths are stored relative to the corpus (tests/test_data_pipeline.py::CORPUS), so the fixture fits any checkout
     with open(os.path.join(HERE, "dataset_golden.json"), "w") as f:
-        json.dump(out, f)
+        f.write(json.dumps(out).replace(json.dumps(root)[1:-1], "<tiny_corpus>"))
     print("wrote dataset_golden.json", os.path.getsize(os.path.join(HERE, "dataset_golden.json")) // 1024, "KB")
 
 

@@ -12,6 +12,7 @@ from umpr_amd.data import Dataset, Word2vec, batch_loader, pad_reviews
 
 ROOT = os.path.join(GOLDEN, "tiny_corpus")
 G = json.load(open(os.path.join(GOLDEN, "dataset_golden.json")))
+CORPUS = "<tiny_corpus>"   # the fixture's photo paths start with this in place of the corpus directory
 
 
 class Cfg:
@@ -40,7 +41,7 @@ def test_word2vec():
 
 
 def _norm(x):
-    return json.loads(json.dumps(x))
+    return json.loads(json.dumps(x).replace(json.dumps(ROOT)[1:-1], CORPUS))
 
 
 def test_dataset_and_collate():

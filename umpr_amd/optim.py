@@ -204,7 +204,7 @@ class FusedAdam:
         """train_step: the coming backward belongs to exactly one optimiser step with this gradient scale.
         UMPR_EARLY_ADAM=0 turns it off.  Worth 0.3-0.5 ms per step behind the all-reduce in the RCCL rehearsal (43.16 vs
         43.49 ms fp32, 16.06 vs 16.51 ms bf16); on a single GPU 0.1-0.3 ms in bf16 (9.56 vs 9.71 ms) and nothing in fp32.  Its stream is one more next to main / text / weight-gradient / RCCL:
-        umpr_amd/__init__.py raises GPU_MAX_HW_QUEUES so that they do not share hardware queues."""
+        umpr_amd/__init__.py sets GPU_MAX_HW_QUEUES, the number of hardware queues they share."""
         if _EARLY_ADAM == "0":
             return
         self._early = (float(grad_scale),)
