@@ -386,6 +386,42 @@ def test_cfg4_full_size_forward_vs_oracle_and_backward_properties(dev):
     assert abs(float(l1) - float(rl)) < 1e-4
 
 
+def test_cfg1_full_size_forward_vs_oracle(dev):
+    """BASELINE.json configs[1] at its own size: full UMPR, batch 64, one view (64 images), GloVe-50d, fully padded reviews.
+    Forward: predictions and loss within 1e-4 of the oracle's (eval mode).  Backward: two runs are bitwise identical and
+    scaling the loss by 2 scales every gradient by exactly 2.  (The VGG16 gradients of a batch of 64 are held to a float64
+    reference by tests/test_gpu_vgg_grad.py.)"""
+    from oracle import umpr_ref as R
+    from umpr_amd.model import UMPR
+    from umpr_amd.synthetic import make_batch, make_param_state
+    P = make_param_state(231, 50, 3000, 1, False, m_scale=0.05)
+    batch = make_batch(232, 64, 3000, 1, full_pad=True)
+    assert tuple(batch[6].shape) == (64, 1, 1, 3, 224, 224)
+    model = UMPR(_cfg(views=["unknown"]), P["embedding.weight"].numpy())
+    model.load_state_dict(P)
+    model = model.to(dev).eval()
+
+    def grads(scale):
+        model.zero_grad(set_to_none=True)
+        pred, loss = model(*batch)
+        (loss * scale).backward()
+        return pred.detach().clone(), loss.detach().clone(), {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None}
+
+    p1, l1, g1 = grads(1.0)
+    p2, l2, g2 = grads(1.0)
+    p3, l3, g3 = grads(2.0)
+    assert torch.equal(p1, p2) and torch.equal(l1, l2)
+    assert any("vgg16" in k for k in g1)
+    for k in g1:
+        assert torch.isfinite(g1[k]).all(), k
+        assert torch.equal(g1[k], g2[k]), f"{k}: two runs differ"
+        assert torch.equal(g3[k], 2 * g1[k]), f"{k}: gradient is not linear in the upstream gradient"
+    with torch.no_grad():
+        rp, rl = R.umpr_forward(P, batch, review_net_only=False, aten=True)
+    assert float((p1.cpu() - rp).abs().max()) < 1e-4, float((p1.cpu() - rp).abs().max())
+    assert abs(float(l1) - float(rl)) < 1e-4
+
+
 def test_graphed_umpr_r_step_equals_eager(dev):
     """umpr_amd/graphs.py: the UMPR-R training step captured once as a hipGraph and replayed on four different batches of one
     geometry leaves parameters and Adam moments BIT-identical to four eager train_step calls from the same start (the Adam
