@@ -309,6 +309,24 @@ int umpr_head_bwd(const float* rr, const float* c_u, const float* c_i, const flo
                   float* d_rr, float* d_cu, float* d_ci, float* d_pp, float* d_pn, float* d_vgg, float* d_pos_v,
                   float* d_neg_v, float* d_lin_w, float* d_lin_b, float* d_fus_w, float* d_fus_b, void* stream);
 
+/* ---- photo resize (umpr_amd/photos.py; finishes src/dataset.py:134-143's get_image on the device) ----------------------------
+ * The loader decodes each photo on the host and ships, in ONE uint8 buffer `packed` of `packed_bytes` (device memory), only the
+ * source rows and columns its resize taps read, plus per-photo tap tables it computed with the numpy expressions of
+ * umpr_amd/data.py::resize_bilinear_u8.  out [n_photos][3][dst_h][dst_w] fp32 = that resize (OpenCV's 8-bit INTER_LINEAR,
+ * 11-bit fixed point) / 255, bit-identical to the host path.  `desc` is HOST memory (n_photos entries, read and validated during
+ * the call: every region must lie inside the buffer, else the call fails without launching); offsets are bytes into `packed`.
+ * Tap tables, int32 at desc.taps (4-byte aligned): cx0[dst_w] cx1[dst_w] ax0[dst_w] ax1[dst_w] ry0[dst_h] ry1[dst_h] by0[dst_h]
+ * by1[dst_h] - column / row indices into the compacted source and their weights.  rows = cols = 0 marks a missing photo
+ * (all-zero image).  No allocation or copy: capture-safe. */
+typedef struct umpr_photo_desc {
+  int64_t pixels; /* byte offset of the compacted source, uint8 [rows][cols][3] (RGB) */
+  int64_t taps;   /* byte offset of the tap tables */
+  int32_t rows;
+  int32_t cols;
+} umpr_photo_desc;
+int umpr_photo_resize_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc, int n_photos, int dst_h,
+                         int dst_w, float* out, void* stream);
+
 /* ---- R-Net pre-training head (pretrain/pretrain_rnet.py:147-169): result = sigmoid(Linear(K -> 1)(att)),
  * loss = BCELoss(mean)(result, target) with torch's log clamp at -100.  att rows at att + b*ld (K = 256: [atte_u;atte_i]
  * as umpr_coattention_fwd leaves them).  ws: B floats.  Backward follows ATen's binary_cross_entropy_backward

@@ -71,7 +71,8 @@ class _Collate:
 
     def __call__(self, samples):
         from umpr_amd.data import batch_loader
-        return batch_loader(samples, self.ignore_photos, shard=self.shard)
+        # photos leave as decoded uint8 and are resized on the device (umpr_amd/photos.py): bit-identical, a fraction of the host work
+        return batch_loader(samples, self.ignore_photos, shard=self.shard, resize_on_gpu=not self.ignore_photos)
 
 
 def _agree(value, rank):

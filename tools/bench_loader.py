@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Real-data path throughput: a synthetic corpus in the reference's on-disk layout
 (train.csv, photos.json, photos/*.jpg, GloVe text) -> umpr_amd.data.Dataset -> DataLoader(batch_loader) -> UMPR.
-Prints loader-only batches/s for several worker counts, then end-to-end training samples/s with the best one.
+Prints, for both forms of the photo element (host: decode + resize + /255 on the host, float32 upload; gpu: decode on the
+host, uint8 upload, resize in csrc/photos.hip - what main.py uses), loader-only samples/s for several worker counts and
+where the host time of one photo goes; then end-to-end training samples/s with each form at its best worker count.
 
-    python tools/bench_loader.py [--items 64] [--users 400] [--batch 64] [--workers 0,4,8,16] [--steps 20]
+    python tools/bench_loader.py [--items 64] [--users 200] [--batch 64] [--workers 0,4,8,12] [--steps 20]
 """
 import argparse
+import functools
 import json
 import os
 import random
@@ -52,13 +55,13 @@ def main():
     ap.add_argument("--items", type=int, default=64)
     ap.add_argument("--users", type=int, default=200)
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--workers", default="0,4,8,16")
+    ap.add_argument("--workers", default="0,4,8,12")
     ap.add_argument("--steps", type=int, default=20)
     a = ap.parse_args()
     from torch.utils.data import DataLoader
     from main import _Collate
     from umpr_amd.config import Config
-    from umpr_amd.data import Dataset, Word2vec
+    from umpr_amd.data import Dataset, Word2vec, batch_loader
     with tempfile.TemporaryDirectory() as d:
         n = write_corpus(d, a.users, a.items)
         cfg = Config(argv=[])
@@ -67,54 +70,92 @@ def main():
         t0 = time.perf_counter()
         ds = Dataset(os.path.join(d, "train.csv"), os.path.join(d, "photos.json"), os.path.join(d, "photos"), w2v, cfg)
         print(f"corpus: {n} reviews -> {len(ds)} samples, Dataset built in {time.perf_counter() - t0:.2f} s", flush=True)
-        best = (0.0, 0)
+        photo = ds[0][3][0][0]
+        per_photo(photo)
+        forms = {"host": functools.partial(batch_loader, ignore_photos=False, resize_on_gpu=False), "gpu": _Collate(False)}
+        best = {}
         for w in [int(x) for x in a.workers.split(",")]:
-            kw = dict(collate_fn=_Collate(False), num_workers=w, pin_memory=torch.cuda.is_available())
-            if w:
-                kw.update(prefetch_factor=2, persistent_workers=True)
-            dl = DataLoader(ds, batch_size=a.batch, shuffle=True, **kw)
-            it = iter(dl)
-            next(it)  # workers started, first batch decoded
-            t0 = time.perf_counter()
-            k = 0
-            for b in it:
-                k += 1
-                if k >= a.steps:
-                    break
-            dt = time.perf_counter() - t0
-            rate = k * a.batch / dt
-            print(f"loader only, {w:2d} workers: {rate:8.1f} samples/s ({1e3 * dt / k:.1f} ms per batch of {a.batch})", flush=True)
-            if rate > best[0]:
-                best = (rate, w)
-            del it, dl
+            for form, collate in forms.items():
+                kw = dict(collate_fn=collate, num_workers=w, pin_memory=torch.cuda.is_available())
+                if w:
+                    kw.update(prefetch_factor=2, persistent_workers=True)
+                dl = DataLoader(ds, batch_size=a.batch, shuffle=True, **kw)
+                it = iter(dl)
+                next(it)  # workers started, first batch decoded
+                t0 = time.perf_counter()
+                k = 0
+                for b in it:
+                    k += 1
+                    if k >= a.steps:
+                        break
+                dt = time.perf_counter() - t0
+                rate = k * a.batch / dt
+                print(f"loader only, {form:4s} form, {w:2d} workers: {rate:8.1f} samples/s ({1e3 * dt / k:.1f} ms per batch of "
+                      f"{a.batch})", flush=True)
+                if rate > best.get(form, (0.0, 0))[0]:
+                    best[form] = (rate, w)
+                del it, dl
         if not torch.cuda.is_available():
             return
         from umpr_amd.model import UMPR
         from umpr_amd.optim import FusedAdam
         from umpr_amd.train import train_step
         dev = torch.device("cuda:0")
-        model = UMPR(cfg, w2v.embedding).to(dev)
-        opt = FusedAdam(model, cfg.learning_rate, cfg.l2_regularization, cfg.lr_decay)
-        w = best[1]
-        kw = dict(collate_fn=_Collate(False), num_workers=w, pin_memory=True)
-        if w:
-            kw.update(prefetch_factor=2, persistent_workers=True)
-        dl = DataLoader(ds, batch_size=a.batch, shuffle=True, drop_last=True, **kw)
-        it = iter(dl)
-        for _ in range(3):
-            train_step(model, opt, next(it))
-        torch.cuda.synchronize()
+        for form in ("gpu", "host"):
+            torch.manual_seed(0)
+            model = UMPR(cfg, w2v.embedding).to(dev)
+            opt = FusedAdam(model, cfg.learning_rate, cfg.l2_regularization, cfg.lr_decay)
+            w = best[form][1]
+            kw = dict(collate_fn=forms[form], num_workers=w, pin_memory=True)
+            if w:
+                kw.update(prefetch_factor=2, persistent_workers=True)
+            dl = DataLoader(ds, batch_size=a.batch, shuffle=True, drop_last=True, **kw)
+            it = iter(dl)
+            for _ in range(3):
+                train_step(model, opt, next(it))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            k = 0
+            for b in it:
+                train_step(model, opt, b)
+                k += 1
+                if k >= a.steps:
+                    break
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            print(f"end to end (CSV + JPEG decode + collate + H2D + train step), {form} form, {w} workers: "
+                  f"{k * a.batch / dt:.1f} samples/s ({1e3 * dt / k:.1f} ms per step)", flush=True)
+            del it, dl, model, opt
+
+
+def per_photo(path, reps=20):
+    """Host time of one photo on this thread, by stage: the host form's get_image and float32 cast, and the gpu form's
+    decode, tap tables + compaction, and share of RawPhotos.pack."""
+    from PIL import Image
+    from umpr_amd.data import _column_taps, _row_taps, get_image
+    from umpr_amd.photos import RawPhotos, decode_for_gpu
+
+    def ms(f):
+        f()
         t0 = time.perf_counter()
-        k = 0
-        for b in it:
-            train_step(model, opt, b)
-            k += 1
-            if k >= a.steps:
-                break
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        print(f"end to end (CSV + JPEG decode + collate + H2D + train step), {w} workers: {k * a.batch / dt:.1f} samples/s "
-              f"({1e3 * dt / k:.1f} ms per step)", flush=True)
+        for _ in range(reps):
+            f()
+        return 1e3 * (time.perf_counter() - t0) / reps
+
+    def decode():
+        with Image.open(path) as im:
+            return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+    one = decode_for_gpu(path)
+    t_dec = ms(decode)
+    t_host = ms(lambda: get_image(path).astype(np.float32))
+    t_gpu = ms(lambda: decode_for_gpu(path))
+    t_pack = ms(lambda: RawPhotos.pack([one] * 64, (64, 1, 1), (224, 224))) / 64
+    t_pin = ms(lambda: RawPhotos.pack([one] * 64, (64, 1, 1), (224, 224)).pin_memory()) / 64 - t_pack \
+        if torch.cuda.is_available() else float("nan")
+    print(f"per photo ({path.rsplit('/', 1)[-1]}): decode {t_dec:.2f} ms; host form get_image + float32 {t_host:.2f} ms; "
+          f"gpu form decode_for_gpu {t_gpu:.2f} ms (taps + compaction {t_gpu - t_dec:.2f}), pack {t_pack:.3f} ms, "
+          f"pin {t_pin:.3f} ms; upload {one[0].nbytes + 16 * 448} B vs {3 * 224 * 224 * 4} B", flush=True)
 
 
 if __name__ == "__main__":

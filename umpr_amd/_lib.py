@@ -96,6 +96,7 @@ SIGNATURES = {
     "umpr_control_net_bwd": ("pppipppppiiiiiiiiipppppppzp", "i"),
     "umpr_head_fwd": ("pppppppppppppfiiipppppppp", "i"),
     "umpr_head_bwd": ("pppppppppppfiiippppppppppppppppppppp", "i"),
+    "umpr_photo_resize_u8": ("pzpiiipp", "i"),
     "umpr_bce_head_fwd": ("plpppiipppzp", "i"),
     "umpr_bce_head_bwd": ("plpppppiiplpppzp", "i"),
     "umpr_adam_step": ("ppppldddddldp", "i"),

@@ -182,6 +182,26 @@ def _linear_coeffs(dst, src):
     return s, w
 
 
+def _column_taps(dst, src):
+    """Horizontal taps of resize_bilinear_u8: source columns (x0, x1) and their 11-bit weights (a0, a1) per output column.
+    Taps left of column 0 or right of the last column collapse onto the edge pixel with weight 1."""
+    sx, fx = _linear_coeffs(dst, src)
+    fx = np.where((sx < 0) | (sx >= src - 1), np.float32(0), fx)
+    sx = np.clip(sx, 0, src - 1)
+    sx1 = np.minimum(sx + 1, src - 1)
+    a1 = np.rint(fx * np.float32(2048)).astype(np.int32)
+    a0 = np.rint((np.float32(1) - fx) * np.float32(2048)).astype(np.int32)
+    return sx, sx1, a0, a1
+
+
+def _row_taps(dst, src):
+    """Vertical taps of resize_bilinear_u8: source rows (y0, y1), clipped to the image, and their 11-bit weights (b0, b1)."""
+    sy, fy = _linear_coeffs(dst, src)
+    b1 = np.rint(fy * np.float32(2048)).astype(np.int32)
+    b0 = np.rint((np.float32(1) - fy) * np.float32(2048)).astype(np.int32)
+    return np.clip(sy, 0, src - 1), np.clip(sy + 1, 0, src - 1), b0, b1
+
+
 def resize_bilinear_u8(img, size):
     """cv2.resize(img, size) for uint8 HxWxC with the default INTER_LINEAR, restated from OpenCV's fixed-point path
     (resize.cpp: HResizeLinear / VResizeLinear for uchar - 2 taps, no antialiasing, coefficients scaled by 2^11):
@@ -190,17 +210,8 @@ def resize_bilinear_u8(img, size):
     what the reference's get_image computes by construction, where PIL's own BILINEAR filter would antialias."""
     dw, dh = size
     h, w, _ = img.shape
-    sx, fx = _linear_coeffs(dw, w)
-    fx = np.where((sx < 0) | (sx >= w - 1), np.float32(0), fx)
-    sx = np.clip(sx, 0, w - 1)
-    sx1 = np.minimum(sx + 1, w - 1)
-    a1 = np.rint(fx * np.float32(2048)).astype(np.int32)
-    a0 = np.rint((np.float32(1) - fx) * np.float32(2048)).astype(np.int32)
-    sy, fy = _linear_coeffs(dh, h)
-    b1 = np.rint(fy * np.float32(2048)).astype(np.int32)
-    b0 = np.rint((np.float32(1) - fy) * np.float32(2048)).astype(np.int32)
-    y0 = np.clip(sy, 0, h - 1)
-    y1 = np.clip(sy + 1, 0, h - 1)
+    sx, sx1, a0, a1 = _column_taps(dw, w)
+    y0, y1, b0, b1 = _row_taps(dh, h)
     used = np.unique(np.concatenate([y0, y1]))                     # only the source rows some output row taps
     src = np.ascontiguousarray(np.take(img, used, axis=0).transpose(2, 0, 1)).astype(np.int32)   # [c][rows][w]
     rows = np.take(src, sx, axis=2) * a0 + np.take(src, sx1, axis=2) * a1                         # scaled by 2^11
@@ -222,12 +233,15 @@ def get_image(path, resize=(224, 224)):
         return np.zeros([3] + list(resize))
 
 
-def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, shard=None):
+def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, shard=None, resize_on_gpu=False):
     """src/dataset.py:146-182.  `shard=(rank, world)` (data parallel, not in the reference): the review tensors are padded
     to the GLOBAL batch's common (max_count, max_len) exactly as the reference's single collate does before
     DataParallel scatters them (main.py:82), but only this rank's contiguous chunk is kept - and only its photos are
     decoded, so R ranks do 1/R of the JPEG work each instead of all of it.  A ninth element then carries the number
-    of ranks with a non-empty chunk (parallel.active_shards)."""
+    of ranks with a non-empty chunk (parallel.active_shards).
+
+    `resize_on_gpu=True` (not in the reference): the photos element is a photos.RawPhotos of this rank's chunk - decoded
+    pixels as uint8, resized on the device by its .to(device) - instead of the float32 tensor; the same values once uploaded."""
     lo, hi = 0, len(batch_list)
     if shard is not None:
         from .parallel import active_shards, shard_bounds
@@ -237,8 +251,14 @@ def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, 
     items = [s[1] for s in batch_list]
     uis = [s[2] for s in batch_list]
     ratings = [s[4] for s in mine]
-    photos = []
-    if not ignore_photos and mine:
+    photos, raw = [], None
+    if resize_on_gpu and not ignore_photos and batch_list:
+        from .photos import RawPhotos, decode_for_gpu
+        paths = [p for s in mine for view in s[3] for p in view]
+        with ThreadPoolExecutor() as pool:
+            decoded = list(pool.map(lambda x: decode_for_gpu(x, photo_size), paths))
+        raw = RawPhotos.pack(decoded, (len(mine), len(batch_list[0][3]), len(batch_list[0][3][0])), photo_size)
+    elif not ignore_photos and mine:
         paths = [p for s in mine for view in s[3] for p in view]
         with ThreadPoolExecutor() as pool:
             imgs = iter(list(pool.map(lambda x: get_image(x, photo_size), paths)))
@@ -250,6 +270,7 @@ def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, 
     pui, lui = pad_reviews(uis, pad=pad)
     long = lambda rows: torch.LongTensor(rows[lo:hi]) if hi > lo else torch.zeros((0,) + tuple(torch.LongTensor(rows[:1]).shape[1:]), dtype=torch.long)
     out = (long(pu), long(pi), long(pui), long(lu), long(li), long(lui),
+           raw if raw is not None else
            torch.from_numpy(np.asarray(photos, dtype=np.float32)) if photos else
            (torch.Tensor([]) if ignore_photos or not batch_list else
             torch.zeros((0, len(batch_list[0][3]), len(batch_list[0][3][0]), 3) + tuple(photo_size))),
