@@ -21,11 +21,13 @@ launch stream inside the timed region (libumpr_hip's umpr_profile_*):
                     (F(4x4,3x3) / F(3x3,4x4)).  Only `frac` is an MFMA utilisation.
   bf16 full model : the bf16 implicit-GEMM convolution (forward launches), executed = algorithmic FLOPs.
   UMPR-R          : the recurrent GRU kernels (HBM / latency bound), algorithmic bytes / time against 8 TB/s.
-`cpu_baseline` times the oracle (oracle/umpr_ref.py, the CPU restatement pinned to the reference) on this box's host
-cores for a bounded sample.
-A default invocation (no workload flag, one GPU) also runs the other single-GPU workloads BASELINE.json names and reports them
-under `other_configs` (bf16 GloVe-300d batch 64 with its own roofline, UMPR-R batch 32 eager and as one hipGraph launch per step,
-4 views x 32 samples in fp32 and bf16, inference fp32 / bf16): 8 timed steps each; `--no-other-configs` skips them.
+A plain run does only what that line needs: set up, warm up, time the steps, write `--dump-outputs`, print.
+`--full` adds the measurements that take runs of their own, after the headline's timed steps:
+  `cpu_baseline` times the oracle (oracle/umpr_ref.py, the CPU restatement pinned to the reference) on the host cores
+  for a bounded sample (one GPU, training workloads; `--no-cpu-baseline` skips it);
+  with no workload flag on one GPU, `other_configs` holds the other single-GPU workloads BASELINE.json names (bf16
+  GloVe-300d batch 64 with its own roofline, UMPR-R batch 32 eager and as one hipGraph launch per step, 4 views x 32
+  samples in fp32 and bf16, inference fp32 / bf16): `--other-steps` timed steps each; `--no-other-configs` skips them.
 `python bench.py --gpus N` without a launcher starts N workers, ends all of them when one dies and retries once with the async
 form of the gradient exchange if the in-stream form failed (spawn_workers).
 `--dump-outputs DIR` writes what the last timed step of the headline workload computed (prediction, loss, and a seeded
@@ -52,7 +54,7 @@ VGG_MMAC_FWD = 15470.1                    # per image; train = 3 x forward; cfg2
 KB_PER_SAMPLE_UMPR_R = 187.0   # compulsory forward traffic of UMPR-R per sample (E = 50)
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
@@ -73,15 +75,27 @@ def parse():
                          "under the previous step), reported as h2d_inclusive; `value` stays the resident figure")
     ap.add_argument("--graph", action="store_true",
                     help="UMPR-R only: the training step as one captured hipGraph launch (umpr_amd/graphs.py)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baseline and (default workload, one GPU) the `other_configs` "
+                         "sub-lines; a plain run times the headline workload alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default invocation only: skip the `other_configs` sub-lines (bf16 GloVe-300d, UMPR-R, 4 views, inference)")
+                    help="with --full: skip the `other_configs` sub-lines (bf16 GloVe-300d, UMPR-R, 4 views, inference)")
     ap.add_argument("--other-steps", type=int, default=12, help="timed steps of each `other_configs` sub-line")
     ap.add_argument("--cpu-batch", type=int, default=0, help="batch of the CPU baseline sample (0: the GPU batch)")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
-    return ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def extras(args, world):
+    """Which `--full` measurements follow the headline: (other_configs, cpu_baseline).  A plain run has neither."""
+    default_workload = (not args.eval and not args.fwd_train and not args.review_net_only and not args.realistic
+                        and not args.h2d and (args.batch, args.views, args.emb, args.dtype) == (64, 1, 50, "fp32"))
+    others = args.full and world == 1 and not args.no_other_configs and default_workload
+    cpu = args.full and world == 1 and not args.no_cpu_baseline and not args.eval and not args.fwd_train
+    return others, cpu
 
 
 def host_cores():
@@ -556,8 +570,8 @@ def run_workload(w, env):
     return out, P
 
 
-# The other single-GPU workloads BASELINE.json names, run after the headline by a default invocation so that the
-# driver-timed record holds them.  Keys: overrides of the headline's argparse namespace.
+# The other single-GPU workloads BASELINE.json names, run after the headline by `--full` on the default workload so that
+# one record holds them.  Keys: overrides of the headline's argparse namespace.
 OTHER_CONFIGS = (
     ("configs[4]_per_gpu_bf16_glove300_b64", dict(dtype="bf16", emb=300, batch=64)),
     ("configs[0]_umpr_r_b32", dict(review_net_only=True, batch=32)),
@@ -593,10 +607,8 @@ def main():
         torch.cuda.set_device(dev)
         env = {"L": lib(), "dev": dev, "rank": rank, "world": world}
         out, P = run_workload(args, env)
-        default_line = (world == 1 and not args.no_other_configs and not args.eval and not args.fwd_train and not args.review_net_only
-                        and not args.realistic and not args.h2d
-                        and (args.batch, args.views, args.emb, args.dtype) == (64, 1, 50, "fp32"))
-        if default_line:
+        with_others, with_cpu = extras(args, world)
+        if with_others:
             others = {}
             for name, over in OTHER_CONFIGS:
                 w = argparse.Namespace(**{**vars(args), **over, "steps": args.other_steps, "warmup": 5, "h2d": False,
@@ -616,7 +628,7 @@ def main():
                                                               "launches", "avg_launch_ms") if k in r}
             out["other_configs"] = others
         if rank == 0:
-            if world == 1 and not args.no_cpu_baseline and not args.eval and not args.fwd_train:
+            if with_cpu:
                 out["cpu_baseline"] = cpu_baseline(args, P, rank)
             result_out.write(json.dumps(out) + "\n")
             result_out.flush()
