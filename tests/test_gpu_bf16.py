@@ -583,7 +583,11 @@ def test_review_head_bf16_mode_vs_oracle(L, dev, B, S, Lm, m_scale):
          like the fp32 test; the argmax routing then agrees, and the gradients are within 5e-3 relative L2 (the kernels also
          round the GRADIENT operands of their products to bf16, 2^-9 relative each);
       f: the unrounded fp32 oracle: outputs within 3e-2 absolute (the stated bf16 bound); gradients are logged only - a bf16
-         score can pick another near-tied maximum, which re-routes the gradient."""
+         score can pick another near-tied maximum, which re-routes the gradient.
+    The cases (4, 20, 20, m_scale 1.0) and (2, 7, 9, 0.3) are SATURATED - 77 % / 33 % of A and every row and column maximum
+    are exactly 1.0f, the routed term carries 1 - max^2 = 0 - and pin only the forward and the tanh' = 0 path.  Only
+    (3, 20, 20, 0.05) exercises the routing (its maxima reach 0.9999998), which tests/test_gpu_coattn.py pins decision by
+    decision for umpr_coattention_fwd_bf16.  The saturated share is logged."""
     from umpr_amd.model import _ReviewHead
     from umpr_amd.synthetic import make_param_state
     P0 = make_param_state(11, 50, 500, 1, False, with_vgg=False, m_scale=m_scale)
@@ -603,6 +607,10 @@ def test_review_head_bf16_mode_vs_oracle(L, dev, B, S, Lm, m_scale):
         A = torch.tanh(r(T) @ r(gru_u).transpose(-1, -2))
         soft_u = torch.softmax(A.max(dim=-2).values, -1)
         soft_i = torch.softmax(A.max(dim=-1).values, -1)
+        if tag == "q":
+            maxima = torch.cat([A.detach().max(dim=-2).values, A.detach().max(dim=-1).values], -1)
+            log(f"review head bf16 mode B{B} S{S} m{m_scale}: {float((A.detach().abs() == 1).float().mean()):.1%} of A "
+                f"saturated, {float((maxima.abs() == 1).float().mean()):.1%} of the row / column maxima exactly 1")
         atte_u = (gru_u.transpose(-1, -2) @ soft_u.unsqueeze(-1)).squeeze(-1)
         atte_i = (gru_i.transpose(-1, -2) @ soft_i.unsqueeze(-1)).squeeze(-1)
         _, su = _s_net_q(gru_u, soft_u, Lm, W[1], W[2], tag == "q")

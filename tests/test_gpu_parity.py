@@ -360,8 +360,16 @@ def _text_params(seed, V, m_scale):
 
 @pytest.mark.parametrize("B,S,Lm,m_scale", [(3, 20, 20, 1.0), (2, 7, 9, 0.05), (5, 20, 20, 0.05),
                                             # sentences longer than one wave (review_level='review', src/dataset.py:24)
-                                            (2, 3, 100, 0.05), (1, 2, 200, 0.3)])
+                                            (2, 3, 100, 0.05), (1, 2, 200, 0.3),
+                                            # the non-saturated twin of the case before it (same inputs, smaller M)
+                                            (1, 2, 200, 0.05)])
 def test_review_head(L, dev, B, S, Lm, m_scale):
+    """_ReviewHead against the oracle in fp32.  The cases (3, 20, 20, m_scale 1.0) and (1, 2, 200, 0.3) are SATURATED: 77 % /
+    34 % of A = tanh(G_i M G_u^T) and every row and column maximum are exactly 1.0f, so the routed term of the co-attention
+    backward is multiplied by 1 - max^2 = 0 and the reference dM is identically zero.  They pin the forward and the tanh' = 0
+    path only - no argmax route can change any of their outputs.  The m_scale 0.05 cases exercise the routing (their top-2
+    margins go down to 1e-8, so which float32 order wins a near tie is not pinned here); the routing itself is pinned by
+    tests/test_gpu_coattn.py against a float64 backward that replays the HIP decisions.  The saturated share is logged."""
     from oracle import umpr_ref as R
     from umpr_amd.model import _ReviewHead
     P = _text_params(11, 1, m_scale)
@@ -377,6 +385,9 @@ def test_review_head(L, dev, B, S, Lm, m_scale):
     A = torch.tanh(gru_i @ P[keys[0]] @ gru_u.transpose(-1, -2))
     soft_u = torch.softmax(A.max(dim=-2).values, -1)
     soft_i = torch.softmax(A.max(dim=-1).values, -1)
+    maxima = torch.cat([A.detach().max(dim=-2).values, A.detach().max(dim=-1).values], -1)
+    log(f"review_head B{B} S{S} L{Lm} m{m_scale}: {float((A.detach().abs() == 1).float().mean()):.1%} of A saturated, "
+        f"{float((maxima.abs() == 1).float().mean()):.1%} of the row / column maxima exactly 1")
     atte_u = (gru_u.transpose(-1, -2) @ soft_u.unsqueeze(-1)).squeeze(-1)
     atte_i = (gru_i.transpose(-1, -2) @ soft_i.unsqueeze(-1)).squeeze(-1)
     _, su = R.s_net(gru_u, soft_u, Lm, P, pre + "s_net_u.")
