@@ -327,6 +327,20 @@ typedef struct umpr_photo_desc {
 int umpr_photo_resize_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc, int n_photos, int dst_h,
                          int dst_w, float* out, void* stream);
 
+/* ---- device-resident photo store (umpr_amd/photos.py::PhotoStore) ---------------------------------------------------------------
+ * `store` (device memory, 16-byte aligned) holds n_slots slots of umpr_photo_store_slot_bytes(dst_h, dst_w) bytes: the uint8 value
+ * behind every output pixel of one resized photo, planar [3][dst_h][dst_w] (slot byte j <-> output float j), so that
+ * out = lut[slot] reproduces umpr_photo_resize_u8's floats bit for bit.  src_slot, dst_slot and desc are HOST memory (n_photos
+ * entries each), read and validated during the call.  Photo i with src_slot[i] >= 0 is read from that slot (its descriptor must
+ * be 0 x 0); otherwise it is resized exactly as by umpr_photo_resize_u8 (zeros for a 0 x 0 descriptor) and, if dst_slot[i] >= 0,
+ * its uint8 image is also written to that slot.  Refused without launching: a slot outside [0, n_slots), a null store with a slot
+ * in use, a hit with a non-empty descriptor, a dst_slot on a 0 x 0 descriptor, one dst_slot given twice, a dst_slot that a photo
+ * of the same call reads.  No allocation or copy: capture-safe. */
+size_t umpr_photo_store_slot_bytes(int dst_h, int dst_w); /* 3*dst_h*dst_w rounded up to 16; 0 for a size the resize refuses */
+int umpr_photo_fetch_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc, const int32_t* src_slot,
+                        const int32_t* dst_slot, int n_photos, int dst_h, int dst_w, uint8_t* store, long n_slots, float* out,
+                        void* stream);
+
 /* ---- R-Net pre-training head (pretrain/pretrain_rnet.py:147-169): result = sigmoid(Linear(K -> 1)(att)),
  * loss = BCELoss(mean)(result, target) with torch's log clamp at -100.  att rows at att + b*ld (K = 256: [atte_u;atte_i]
  * as umpr_coattention_fwd leaves them).  ws: B floats.  Backward follows ATen's binary_cross_entropy_backward

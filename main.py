@@ -65,14 +65,16 @@ class ShardedLoader:
 class _Collate:
     """Picklable collate (worker processes): src/dataset.py:173-182 via umpr_amd.data.batch_loader."""
 
-    def __init__(self, ignore_photos, rank=0, world=1):
+    def __init__(self, ignore_photos, rank=0, world=1, store=None):
         self.ignore_photos = ignore_photos
         self.shard = (rank, world) if world > 1 else None
+        self.store = store          # a PhotoStore's index (--photo_store_gb): photos the store holds are not decoded
 
     def __call__(self, samples):
         from umpr_amd.data import batch_loader
         # photos leave as decoded uint8 and are resized on the device (umpr_amd/photos.py): bit-identical, a fraction of the host work
-        return batch_loader(samples, self.ignore_photos, shard=self.shard, resize_on_gpu=not self.ignore_photos)
+        return batch_loader(samples, self.ignore_photos, shard=self.shard, resize_on_gpu=not self.ignore_photos,
+                            store=None if self.ignore_photos else self.store)
 
 
 def _agree(value, rank):
@@ -99,7 +101,16 @@ def run_real(config, rank, world, log):
         log(f'{model_path} is not exist! (--test_only needs --model_path <trained checkpoint>)')
         sys.exit(-1)                                   # the reference exits here too (main.py:89-91)
     w2v = Word2vec(config.word2vec_file)
-    collate = _Collate(config.review_net_only, rank, world)
+    # --photo_store_gb X: this rank keeps every resized photo it has decoded in X GB of device memory (150 528 B per photo, no
+    # eviction) and decodes it once per run instead of once per epoch and validation pass (umpr_amd/photos.py::PhotoStore)
+    store = None
+    if config.photo_store_gb > 0 and not config.review_net_only:
+        from umpr_amd.photos import PhotoStore
+        store = PhotoStore(config.device, capacity_bytes=int(config.photo_store_gb * 1e9))
+        log(f'Photo store: {store.slots} slots of {store.slot_bytes} B ({store.slots * store.slot_bytes / 1e9:.2f} GB) on '
+            f'{config.device}')
+    known = lambda data: store and store.register(data.photo_paths())
+    collate = _Collate(config.review_net_only, rank, world, store.index if store else None)
     workers = max(0, int(getattr(config, "loader_workers", 0)))
     # decode + resize + collate in worker processes, pinned staging buffers, batches prefetched ahead of the GPU; with
     # loader_workers = 0 everything runs on the training thread, as in the reference (main.py:70-73)
@@ -114,11 +125,14 @@ def run_real(config, rank, world, log):
         train_data = Dataset(os.path.join(d, 'train.csv'), photo_json, photo_path, w2v, config)
         valid_data = Dataset(os.path.join(d, 'valid.csv'), photo_json, photo_path, w2v, config)
         log(f'Training dataset contains {len(train_data)} samples.')
+        known(train_data), known(valid_data)           # before the loaders exist: their workers copy the path table
         g = torch.Generator().manual_seed(0)  # same shuffle on every rank
         train_dlr = ShardedLoader(DataLoader(train_data, batch_size=config.batch_size, shuffle=True, generator=g, **dl),
                                   rank, world)
         valid_dlr = ShardedLoader(DataLoader(valid_data, batch_size=config.batch_size, **dl), rank, world)
         _, saved = training(train_dlr, valid_dlr, model, config, model_path, logger=logger, world=world, rank=rank)
+        if store:
+            log(f'Photo store after training: {store.stats()}')
     if config.test_only or saved:
         load_checkpoint(model_path, model, map_location=config.device)
         log(f'Testing the checkpoint {model_path}')
@@ -126,8 +140,11 @@ def run_real(config, rank, world, log):
         log('No checkpoint was written in this run (validation never improved at a multiple of the validation '
             'interval): testing the model as it stands at the end of training')
     test_data = Dataset(os.path.join(d, 'test.csv'), photo_json, photo_path, w2v, config)
+    known(test_data)
     test_dlr = ShardedLoader(DataLoader(test_data, batch_size=config.batch_size, **dl), rank, world)
     log(f"Test end, test mse is {evaluate_mse(model, test_dlr):.6f}")
+    if store:
+        log(f'Photo store after the test: {store.stats()}')
 
 
 def main():
@@ -149,7 +166,7 @@ def main():
 
 def _main():
     extra = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
-             "loader_workers": 0, "valid_every": 500, "dtype": "fp32"}
+             "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0}
     Config.extend(extra)
     config = Config()
     rank, local, world = parallel.init_distributed()

@@ -6,6 +6,12 @@ host, uint8 upload, resize in csrc/photos.hip - what main.py uses), loader-only 
 where the host time of one photo goes; then end-to-end training samples/s with each form at its best worker count.
 
     python tools/bench_loader.py [--items 64] [--users 200] [--batch 64] [--workers 0,4,8,12] [--steps 20]
+
+With `--photo_store_gb X` it measures the device-resident photo store (umpr_amd/photos.py::PhotoStore) instead: per worker
+count (default 0,4,8) whole epochs of the gpu form with the store off (twice: the spread), on and cold, on and warm, the
+forms alternating; then end-to-end training, fp32 and bf16, store off and warm, beside bench.py's resident-batch rate.
+
+    python tools/bench_loader.py --items 2000 --photo_store_gb 1
 """
 import argparse
 import functools
@@ -53,11 +59,16 @@ def write_corpus(root, n_users, n_items, seed=3):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--items", type=int, default=64)
-    ap.add_argument("--users", type=int, default=200)
+    ap.add_argument("--users", type=int, default=None, help="default 200; items / 2 with --photo_store_gb (8 reviews per "
+                    "user: 4 per item on average, so that most items pass the dataset's minimum sentence count)")
     ap.add_argument("--batch", type=int, default=64)
-    ap.add_argument("--workers", default="0,4,8,12")
+    ap.add_argument("--workers", default=None, help="default 0,4,8,12; 0,4,8 with --photo_store_gb")
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--photo_store_gb", type=float, default=0.0, help="measure the photo store with this capacity")
     a = ap.parse_args()
+    a.workers = a.workers or ("0,4,8" if a.photo_store_gb > 0 else "0,4,8,12")
+    a.users = a.users or (max(200, a.items // 2) if a.photo_store_gb > 0 else 200)
+    resident = resident_rates(a.batch) if a.photo_store_gb > 0 else None
     from torch.utils.data import DataLoader
     from main import _Collate
     from umpr_amd.config import Config
@@ -72,6 +83,8 @@ def main():
         print(f"corpus: {n} reviews -> {len(ds)} samples, Dataset built in {time.perf_counter() - t0:.2f} s", flush=True)
         photo = ds[0][3][0][0]
         per_photo(photo)
+        if a.photo_store_gb > 0:
+            return photo_store(a, ds, cfg, w2v, resident)
         forms = {"host": functools.partial(batch_loader, ignore_photos=False, resize_on_gpu=False), "gpu": _Collate(False)}
         best = {}
         for w in [int(x) for x in a.workers.split(",")]:
@@ -126,6 +139,87 @@ def main():
             print(f"end to end (CSV + JPEG decode + collate + H2D + train step), {form} form, {w} workers: "
                   f"{k * a.batch / dt:.1f} samples/s ({1e3 * dt / k:.1f} ms per step)", flush=True)
             del it, dl, model, opt
+
+
+def photo_store(a, ds, cfg, w2v, resident):
+    """The store against the plain gpu form, in whole epochs of `ds` (timed from the first batch's arrival, which leaves the
+    workers' start out).  A store epoch includes RawPhotos.to(device) for every batch - that is what makes photos resident -
+    and a final synchronize; the store-off epochs are the loader alone, as in the plain run."""
+    from torch.utils.data import DataLoader
+    from main import _Collate
+    from umpr_amd.model import UMPR
+    from umpr_amd.optim import FusedAdam
+    from umpr_amd.photos import PhotoStore
+    from umpr_amd.train import train_step
+    if not torch.cuda.is_available():
+        sys.exit("--photo_store_gb needs an MI355X: the store lives in device memory")
+    dev = torch.device("cuda:0")
+    print(f"an epoch: {len(ds) // a.batch} batches of {a.batch}, {len(set(ds.photo_paths()) - {'unknown'})} distinct photos",
+          flush=True)
+
+    def loader(w, store):
+        kw = dict(collate_fn=_Collate(False, store=store.index if store else None), num_workers=w, pin_memory=True)
+        if w:
+            kw.update(prefetch_factor=2, persistent_workers=True)
+        return DataLoader(ds, batch_size=a.batch, shuffle=True, drop_last=True, **kw)
+
+    def epoch(dl, step=None):
+        it = iter(dl)
+        first = next(it)
+        if step:
+            step(first)
+        t0 = time.perf_counter()
+        k = 0
+        for b in it:
+            if step:
+                step(b)
+            k += 1
+        torch.cuda.synchronize()
+        return k * a.batch / (time.perf_counter() - t0)
+
+    # one worker pool at a time: off, on (cold, then warm on the same persistent workers), off again
+    for w in [int(x) for x in a.workers.split(",")]:
+        dl = loader(w, None)
+        print(f"loader only, store off,       {w:2d} workers: {epoch(dl):8.1f} samples/s", flush=True)
+        del dl
+        store = PhotoStore(dev, capacity_bytes=int(a.photo_store_gb * 1e9)).register(ds.photo_paths())
+        fetch = lambda b: b[6].to(dev, non_blocking=True)
+        dl = loader(w, store)
+        print(f"loader only, store on (cold), {w:2d} workers: {epoch(dl, fetch):8.1f} samples/s", flush=True)
+        print(f"loader only, store on (warm), {w:2d} workers: {epoch(dl, fetch):8.1f} samples/s   {store.stats()}", flush=True)
+        del dl
+        dl = loader(w, None)
+        print(f"loader only, store off again, {w:2d} workers: {epoch(dl):8.1f} samples/s", flush=True)
+        del dl
+        for dtype in ("fp32", "bf16"):
+            cfg.dtype = dtype
+            rates = {}
+            for name, st in (("store off", None), ("store on, warm", store)):
+                torch.manual_seed(0)
+                model = UMPR(cfg, w2v.embedding).to(dev)
+                opt = FusedAdam(model, cfg.learning_rate, cfg.l2_regularization, cfg.lr_decay)
+                step = lambda b: train_step(model, opt, b)
+                dl = loader(w, st)
+                epoch(dl, step)                      # warm-up: allocator, workspaces, first-use setup
+                rates[name] = epoch(dl, step)
+                del model, opt, dl
+            print(f"end to end, {dtype}, {w:2d} workers: " + ", ".join(f"{k} {v:.1f} samples/s" for k, v in rates.items()),
+                  flush=True)
+        del store
+    for dtype, rate in resident.items():
+        print(f"resident batch (bench.py --dtype {dtype}): {rate:.1f} samples/s", flush=True)
+
+
+def resident_rates(batch):
+    """bench.py's training samples/s on a batch resident in HBM, fp32 and bf16: child processes, run before this process
+    touches the GPU (a process that has initialised the GPU starts no other GPU program)."""
+    import subprocess
+    rates = {}
+    for dtype in ("fp32", "bf16"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5",
+                              "--batch", str(batch), "--dtype", dtype], capture_output=True, text=True, check=True).stdout
+        rates[dtype] = [json.loads(l) for l in out.splitlines() if l.startswith("{")][-1]["value"]
+    return rates
 
 
 def per_photo(path, reps=20):

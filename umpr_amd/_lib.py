@@ -97,6 +97,8 @@ SIGNATURES = {
     "umpr_head_fwd": ("pppppppppppppfiiipppppppp", "i"),
     "umpr_head_bwd": ("pppppppppppfiiippppppppppppppppppppp", "i"),
     "umpr_photo_resize_u8": ("pzpiiipp", "i"),
+    "umpr_photo_store_slot_bytes": ("ii", "z"),
+    "umpr_photo_fetch_u8": ("pzpppiiiplpp", "i"),
     "umpr_bce_head_fwd": ("plpppiipppzp", "i"),
     "umpr_bce_head_bwd": ("plpppppiiplpppzp", "i"),
     "umpr_adam_step": ("ppppldddddldp", "i"),

@@ -8,6 +8,9 @@
 // then travel in the kernel arguments, in chunks of kPhotoChunk photos per launch: no descriptor can make the kernel read outside
 // the buffer, and the launch needs no hipMemcpy (capture-safe).  The tap indices themselves live in device memory; the kernel
 // clamps them to the photo's compacted source, so a corrupt table gives a wrong picture, never an out-of-bounds read.
+#include <algorithm>
+#include <vector>
+
 #include "umpr_common.h"
 #include "../../include/umpr_hip.h"
 
@@ -72,6 +75,107 @@ __global__ __launch_bounds__(kThreads) void photo_resize_u8_kernel(PhotoChunk ch
   }
 }
 
+
+// ---- device-resident photo store (umpr_amd/photos.py::PhotoStore) --------------------------------------------------------------
+// A slot holds the uint8 value behind every output pixel of one resized photo, planar [3][dh][dw] like the float output, padded to
+// 16 bytes.  Since the float photo is lut[that byte], a resident photo is reproduced bit for bit without its source pixels.
+
+struct PhotoMiss {
+  const uint8_t* pix;
+  const int32_t* taps;
+  int rows, cols;
+  int photo;             // index into this launch's `out`
+  int dst_slot;          // slot that receives the uint8 image, or -1
+};
+struct MissChunk {
+  PhotoMiss p[kPhotoChunk];
+};
+struct PhotoHit {
+  int photo, slot;
+};
+struct HitChunk {
+  PhotoHit p[kPhotoChunk];
+};
+
+// photo_resize_u8_kernel with one more store per channel: the byte the table lookup reads also goes to the photo's slot.
+__global__ __launch_bounds__(kThreads) void photo_resize_store_u8_kernel(MissChunk chunk, int dh, int dw, uint8_t* __restrict__ store,
+                                                                         size_t slot_bytes, float* __restrict__ out) {
+  __shared__ float lut[256];
+  lut[threadIdx.x] = kLut.v[threadIdx.x];
+  __syncthreads();
+  const int npix = dh * dw;
+  const int idx = blockIdx.x * kThreads + threadIdx.x;
+  if (idx >= npix) return;
+  const PhotoMiss src = chunk.p[blockIdx.y];
+  float* o = out + (size_t)src.photo * 3 * npix + idx;
+  if (src.rows <= 0) {            // missing / unreadable: never cached (the host refuses a dst_slot here)
+    o[0] = 0.f;
+    o[npix] = 0.f;
+    o[2 * npix] = 0.f;
+    return;
+  }
+  const int oy = idx / dw, ox = idx - oy * dw;
+  const int32_t* t = src.taps;
+  const int cx0 = min(max(t[ox], 0), src.cols - 1), cx1 = min(max(t[dw + ox], 0), src.cols - 1);
+  const int ax0 = t[2 * dw + ox], ax1 = t[3 * dw + ox];
+  const int32_t* ty = t + 4 * dw;
+  const int ry0 = min(max(ty[oy], 0), src.rows - 1), ry1 = min(max(ty[dh + oy], 0), src.rows - 1);
+  const int by0 = ty[2 * dh + oy], by1 = ty[3 * dh + oy];
+  const size_t stride = (size_t)src.cols * 3;
+  const uint8_t* r0 = src.pix + ry0 * stride;
+  const uint8_t* r1 = src.pix + ry1 * stride;
+  uint8_t* keep = src.dst_slot >= 0 ? store + (size_t)src.dst_slot * slot_bytes + idx : nullptr;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const int h0 = (r0[cx0 * 3 + c] * ax0 + r0[cx1 * 3 + c] * ax1) >> 4;
+    const int h1 = (r1[cx0 * 3 + c] * ax0 + r1[cx1 * 3 + c] * ax1) >> 4;
+    const int v = min(max((((by0 * h0) >> 16) + ((by1 * h1) >> 16) + 2) >> 2, 0), 255);
+    o[c * npix] = lut[v];
+    if (keep) keep[c * npix] = (uint8_t)v;
+  }
+}
+
+typedef float float4_dw __attribute__((ext_vector_type(4), aligned(4)));   // a photo of an odd pixel count starts 4-byte aligned only
+
+constexpr int kHitBytes = kThreads * 16;   // slot bytes per block
+
+// Resident photos: out[photo][j] = lut[slot[j]], j < n = 3*dh*dw, a contiguous uint8 -> float32 conversion.  A block converts
+// kHitBytes bytes of one slot: each thread loads 16 of them (one dwordx4 per lane, 1 KiB per wave), the block turns them over
+// through LDS so that thread t holds dword j*256 + t, and stores its four floats as one float4: both the load and the stores of a
+// wave are contiguous.  The last n % 16 bytes go one per thread.  kAligned: n % 4 == 0, so every photo of `out` is 16-byte aligned.
+template <bool kAligned>
+__global__ __launch_bounds__(kThreads) void photo_fetch_u8_kernel(HitChunk chunk, int n, const uint8_t* __restrict__ store,
+                                                                  size_t slot_bytes, float* __restrict__ out) {
+  __shared__ float lut[256];
+  __shared__ uint4 stage[kThreads];
+  const int tid = threadIdx.x;
+  lut[tid] = kLut.v[tid];
+  const PhotoHit hit = chunk.p[blockIdx.y];
+  const uint8_t* s = store + (size_t)hit.slot * slot_bytes;
+  float* o = out + (size_t)hit.photo * n;
+  const int nvec = n & ~15;
+  const int base = blockIdx.x * kHitBytes;
+  if (base + tid * 16 < nvec) stage[tid] = *reinterpret_cast<const uint4*>(s + base + tid * 16);
+  __syncthreads();
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(stage);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int d = j * kThreads + tid;
+    const int e = base + d * 4;
+    if (e < nvec) {                 // nvec is a multiple of 16: the 16-byte group of dword d was loaded
+      const uint32_t w = words[d];
+      const float f0 = lut[w & 255], f1 = lut[(w >> 8) & 255], f2 = lut[(w >> 16) & 255], f3 = lut[w >> 24];
+      if (kAligned) {
+        *reinterpret_cast<float4*>(o + e) = make_float4(f0, f1, f2, f3);
+      } else {
+        float4_dw f = {f0, f1, f2, f3};
+        *reinterpret_cast<float4_dw*>(o + e) = f;
+      }
+    }
+  }
+  if (blockIdx.x == gridDim.x - 1 && tid < n - nvec) o[nvec + tid] = lut[s[nvec + tid]];
+}
+
 }  // namespace
 
 extern "C" int umpr_photo_resize_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc, int n_photos,
@@ -110,6 +214,94 @@ extern "C" int umpr_photo_resize_u8(const uint8_t* packed, size_t packed_bytes, 
     photo_resize_u8_kernel<<<dim3(cdiv(npix, kThreads), n), kThreads, 0, s>>>(chunk, dst_h, dst_w,
                                                                                 out + (size_t)first * 3 * npix);
     UMPR_LAUNCH_CHECK("photo_resize_u8");
+  }
+  return 0;
+}
+
+extern "C" size_t umpr_photo_store_slot_bytes(int dst_h, int dst_w) {
+  if (dst_h <= 0 || dst_w <= 0 || (long)dst_h * dst_w > (1L << 24)) return 0;
+  return ((size_t)3 * dst_h * dst_w + 15) & ~(size_t)15;
+}
+
+extern "C" int umpr_photo_fetch_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc,
+                                   const int32_t* src_slot, const int32_t* dst_slot, int n_photos, int dst_h, int dst_w,
+                                   uint8_t* store, long n_slots, float* out, void* stream) {
+  UMPR_REQUIRE(n_photos >= 0, "photo_fetch_u8: n_photos = %d", n_photos);
+  if (n_photos == 0) return 0;
+  UMPR_REQUIRE(desc != nullptr && src_slot != nullptr && dst_slot != nullptr && out != nullptr, "photo_fetch_u8: null argument");
+  UMPR_REQUIRE(dst_h > 0 && dst_w > 0 && (long)dst_h * dst_w <= (1L << 24), "photo_fetch_u8: bad output size %d x %d", dst_h,
+               dst_w);
+  UMPR_REQUIRE(n_slots >= 0 && n_slots <= 0x7fffffffL, "photo_fetch_u8: n_slots = %ld", n_slots);
+  const long tap_bytes = 16L * (dst_w + dst_h);
+  std::vector<int32_t> written;
+  for (int i = 0; i < n_photos; ++i) {
+    const umpr_photo_desc& d = desc[i];
+    const bool empty = d.rows == 0 && d.cols == 0;
+    if (src_slot[i] >= 0 || dst_slot[i] >= 0) {
+      UMPR_REQUIRE(store != nullptr, "photo_fetch_u8: photo %d uses a slot but the store is null", i);
+      const int32_t slot = src_slot[i] >= 0 ? src_slot[i] : dst_slot[i];
+      UMPR_REQUIRE(slot < n_slots, "photo_fetch_u8: photo %d: slot %d outside the %ld-slot store", i, slot, n_slots);
+    }
+    if (src_slot[i] >= 0) {
+      UMPR_REQUIRE(dst_slot[i] < 0, "photo_fetch_u8: photo %d has both a src_slot and a dst_slot", i);
+      UMPR_REQUIRE(empty, "photo_fetch_u8: photo %d is read from slot %d but carries a %d x %d source", i, src_slot[i], d.rows,
+                   d.cols);
+      continue;
+    }
+    if (dst_slot[i] >= 0) {
+      UMPR_REQUIRE(!empty, "photo_fetch_u8: photo %d has no source to fill slot %d with", i, dst_slot[i]);
+      written.push_back(dst_slot[i]);
+    }
+    if (empty) continue;
+    UMPR_REQUIRE(packed != nullptr, "photo_fetch_u8: null packed buffer");
+    UMPR_REQUIRE(d.rows > 0 && d.cols > 0 && d.rows <= (1 << 20) && d.cols <= (1 << 20),
+                 "photo_fetch_u8: photo %d has a %d x %d source", i, d.rows, d.cols);
+    UMPR_REQUIRE(d.taps >= 0 && d.taps % 4 == 0 && (uint64_t)d.taps + tap_bytes <= packed_bytes,
+                 "photo_fetch_u8: photo %d: tap tables at byte %lld (+%ld) outside the %zu-byte buffer or misaligned", i,
+                 (long long)d.taps, tap_bytes, packed_bytes);
+    UMPR_REQUIRE(d.pixels >= 0 && (uint64_t)d.pixels + 3ull * (uint64_t)d.rows * (uint64_t)d.cols <= packed_bytes,
+                 "photo_fetch_u8: photo %d: %d x %d pixels at byte %lld outside the %zu-byte buffer", i, d.rows, d.cols,
+                 (long long)d.pixels, packed_bytes);
+  }
+  std::sort(written.begin(), written.end());
+  for (size_t k = 1; k < written.size(); ++k)
+    UMPR_REQUIRE(written[k] != written[k - 1], "photo_fetch_u8: slot %d is the dst_slot of two photos", written[k]);
+  for (int i = 0; i < n_photos; ++i)
+    UMPR_REQUIRE(src_slot[i] < 0 || !std::binary_search(written.begin(), written.end(), src_slot[i]),
+                 "photo_fetch_u8: photo %d reads slot %d, which this call writes", i, src_slot[i]);
+  UMPR_REQUIRE(((uintptr_t)packed & 3) == 0, "photo_fetch_u8: packed buffer not 4-byte aligned");
+  UMPR_REQUIRE(((uintptr_t)store & 15) == 0 && ((uintptr_t)out & 15) == 0, "photo_fetch_u8: store or out not 16-byte aligned");
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int npix = dst_h * dst_w, n = 3 * npix;
+  const size_t slot_bytes = umpr_photo_store_slot_bytes(dst_h, dst_w);
+  for (int first = 0; first < n_photos; first += kPhotoChunk) {
+    const int cnt = min(kPhotoChunk, n_photos - first);
+    MissChunk miss = {};
+    HitChunk hit = {};
+    int n_miss = 0, n_hit = 0;
+    for (int i = 0; i < cnt; ++i) {
+      const umpr_photo_desc& d = desc[first + i];
+      if (src_slot[first + i] >= 0) {
+        hit.p[n_hit++] = {i, src_slot[first + i]};
+        continue;
+      }
+      const bool have = d.rows > 0;
+      miss.p[n_miss++] = {have ? packed + d.pixels : nullptr, have ? reinterpret_cast<const int32_t*>(packed + d.taps) : nullptr,
+                          have ? d.rows : 0, have ? d.cols : 0, i, have ? dst_slot[first + i] : -1};
+    }
+    float* o = out + (size_t)first * n;
+    if (n_miss) {
+      photo_resize_store_u8_kernel<<<dim3(cdiv(npix, kThreads), n_miss), kThreads, 0, s>>>(miss, dst_h, dst_w, store, slot_bytes, o);
+      UMPR_LAUNCH_CHECK("photo_fetch_u8 (resize)");
+    }
+    if (n_hit) {
+      const dim3 grid(cdiv(n, kHitBytes), n_hit);
+      if (n % 4 == 0)
+        photo_fetch_u8_kernel<true><<<grid, kThreads, 0, s>>>(hit, n, store, slot_bytes, o);
+      else
+        photo_fetch_u8_kernel<false><<<grid, kThreads, 0, s>>>(hit, n, store, slot_bytes, o);
+      UMPR_LAUNCH_CHECK("photo_fetch_u8 (fetch)");
+    }
   }
   return 0;
 }

@@ -110,6 +110,10 @@ class Dataset(torch.utils.data.Dataset):
     def __getitem__(self, idx):
         return tuple(x[idx] for x in self.data)
 
+    def photo_paths(self):
+        """The photo path of every sample, view and photo slot of this set, repeats and 'unknown' included."""
+        return (p for views in self.data[3] for view in views for p in view)
+
     def __len__(self):
         return len(self.data[0])
 
@@ -233,7 +237,7 @@ def get_image(path, resize=(224, 224)):
         return np.zeros([3] + list(resize))
 
 
-def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, shard=None, resize_on_gpu=False):
+def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, shard=None, resize_on_gpu=False, store=None):
     """src/dataset.py:146-182.  `shard=(rank, world)` (data parallel, not in the reference): the review tensors are padded
     to the GLOBAL batch's common (max_count, max_len) exactly as the reference's single collate does before
     DataParallel scatters them (main.py:82), but only this rank's contiguous chunk is kept - and only its photos are
@@ -241,7 +245,8 @@ def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, 
     of ranks with a non-empty chunk (parallel.active_shards).
 
     `resize_on_gpu=True` (not in the reference): the photos element is a photos.RawPhotos of this rank's chunk - decoded
-    pixels as uint8, resized on the device by its .to(device) - instead of the float32 tensor; the same values once uploaded."""
+    pixels as uint8, resized on the device by its .to(device) - instead of the float32 tensor; the same values once uploaded.
+    With `store=` a photos.PhotoStore's index, photos the store already holds are not opened at all: they travel as an id."""
     lo, hi = 0, len(batch_list)
     if shard is not None:
         from .parallel import active_shards, shard_bounds
@@ -255,9 +260,18 @@ def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, 
     if resize_on_gpu and not ignore_photos and batch_list:
         from .photos import RawPhotos, decode_for_gpu
         paths = [p for s in mine for view in s[3] for p in view]
+        if store is not None:
+            if tuple(store.size) != tuple(photo_size):
+                raise ValueError(f"photo store of {store.size} photos, batch of {tuple(photo_size)}")
+            ids, hits = store.lookup(paths)
+            todo = [None if h else p for p, h in zip(paths, hits)]
+        else:
+            todo = paths
         with ThreadPoolExecutor() as pool:
-            decoded = list(pool.map(lambda x: decode_for_gpu(x, photo_size), paths))
+            decoded = list(pool.map(lambda x: None if x is None else decode_for_gpu(x, photo_size), todo))
         raw = RawPhotos.pack(decoded, (len(mine), len(batch_list[0][3]), len(batch_list[0][3][0])), photo_size)
+        if store is not None:
+            raw.ids, raw.hits, raw.store_key = torch.from_numpy(ids), torch.from_numpy(hits), store.key
     elif not ignore_photos and mine:
         paths = [p for s in mine for view in s[3] for p in view]
         with ThreadPoolExecutor() as pool:

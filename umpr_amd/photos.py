@@ -6,8 +6,16 @@ taps read (at most 2*dh x 2*dw x 3 bytes, never more than the 3*dh*dw*4 bytes of
 data.resize_bilinear_u8 would use; ``RawPhotos`` packs a batch of them into one uint8 buffer (descriptors, tables, pixels), so
 a batch is one H2D copy, and ``RawPhotos.to(device)`` runs the integer resize on the device.  The result is bit-identical to
 the host form.
+
+``PhotoStore`` (off unless asked for) keeps the resized uint8 image of every photo it has seen in device memory: a photo is
+decoded once per run, every later use ships no pixels and is a table lookup on the device (umpr_photo_fetch_u8), still
+bit-identical.  No eviction: once the slots are used up, further photos are decoded every time.
 """
 from __future__ import annotations
+
+import logging
+import uuid
+import weakref
 
 import numpy as np
 import torch
@@ -50,14 +58,20 @@ class RawPhotos:
     ``.pin_memory()`` (DataLoader(pin_memory=True)) and pickling (DataLoader workers) keep the buffer, and
     ``.to(device)`` uploads it on the current stream and returns the float32 photos resized there."""
 
-    def __init__(self, data, geometry, size):
+    def __init__(self, data, geometry, size, ids=None, hits=None, store_key=None):
         self.data = data                          # torch.uint8, 1-D, host
         self.geometry = tuple(int(g) for g in geometry)
         self.size = (int(size[0]), int(size[1]))  # (dw, dh)
+        # collated against a PhotoStore's index (batch_loader(store=...)): per photo its id in the store (-1: none) and whether
+        # the worker left it undecoded because the store held it; the key finds the store in this process
+        self.ids = ids                            # torch.int32 [n] or None
+        self.hits = hits                          # torch.uint8 [n] or None
+        self.store_key = store_key
 
     @classmethod
     def pack(cls, decoded, geometry, size):
-        """Packs decode_for_gpu results (photo order: sample, view, photo) for a batch of `geometry` = (B, V, P)."""
+        """Packs decode_for_gpu results (photo order: sample, view, photo) for a batch of `geometry` = (B, V, P).  None stands
+        for a missing photo, and for one a PhotoStore holds: both get a 0 x 0 descriptor."""
         n = int(np.prod(geometry))
         assert len(decoded) == n, (len(decoded), geometry)
         dw, dh = size
@@ -95,7 +109,7 @@ class RawPhotos:
         return self.data.numpy()[:n * DESC.itemsize].view(DESC)
 
     def pin_memory(self, device=None):
-        return RawPhotos(self.data.pin_memory(), self.geometry, self.size)
+        return RawPhotos(self.data.pin_memory(), self.geometry, self.size, self.ids, self.hits, self.store_key)
 
     def is_pinned(self):
         return self.data.is_pinned()
@@ -108,6 +122,13 @@ class RawPhotos:
             raise RuntimeError("RawPhotos resize on an MI355X only (no CPU path): use batch_loader(resize_on_gpu=False)")
         dw, dh = self.size
         n = int(np.prod(self.geometry))
+        if self.store_key is not None and n:
+            store = PhotoStore.find(self.store_key)
+            if store is not None:
+                return store.fetch(self, device, non_blocking)
+            if bool(self.hits.any()):
+                raise UmprHipError(f"RawPhotos: {int(self.hits.sum())} photos were left to photo store {self.store_key}, which "
+                                   f"is not registered in this process")
         out = torch.empty(self.shape, dtype=torch.float32, device=device)
         if n == 0:
             return out
@@ -121,4 +142,176 @@ class RawPhotos:
         return out
 
     def __repr__(self):
-        return f"RawPhotos(shape={tuple(self.shape)}, bytes={self.data.numel()})"
+        kept = "" if self.hits is None else f", {int(self.hits.sum())} left to the store"
+        return f"RawPhotos(shape={tuple(self.shape)}, bytes={self.data.numel()}{kept})"
+
+
+class PhotoIndex:
+    """What the loader workers know of a PhotoStore: path -> dense id, and one byte per id in shared memory that the store
+    sets once the photo is resident.  Picklable; the bytes stay shared across fork and torch.multiprocessing pickling."""
+
+    def __init__(self, key, size, max_photos):
+        self.key = key
+        self.size = (int(size[0]), int(size[1]))
+        self.ids = {}
+        self.resident = torch.zeros(int(max_photos), dtype=torch.uint8).share_memory_()
+
+    def lookup(self, paths):
+        """(ids int32 [n], hits uint8 [n]) of `paths`; a hit is a photo the worker need not open."""
+        ids = np.fromiter((self.ids.get(p, -1) for p in paths), dtype=np.int32, count=len(paths))
+        hits = np.zeros(len(paths), dtype=np.uint8)
+        known = ids >= 0
+        hits[known] = self.resident.numpy()[ids[known]]
+        return ids, hits
+
+
+class PhotoTable:
+    """The host half of a PhotoStore: ids, the id -> slot table, which photo of a batch reads or fills which slot, and the
+    counters.  Touches no device, so the planning is testable without one."""
+
+    def __init__(self, size=(224, 224), slots=0, max_photos=1 << 22):
+        self.key = uuid.uuid4().hex
+        self.index = PhotoIndex(self.key, size, max_photos)
+        self.slots = int(slots)
+        self.max_photos = int(max_photos)
+        self._slot = np.full(self.max_photos, -1, dtype=np.int32)      # id -> slot; with index.ids the path -> slot table
+        self.used = self.hits = self.inserts = self.decoded_while_full = self.unregistered = 0
+        self._logged_overflow = False
+
+    @property
+    def size(self):
+        return self.index.size
+
+    def register(self, paths):
+        """Ids for the new paths among `paths` (any iterable; 'unknown' and paths past max_photos get none).  Call it before
+        the DataLoader that serves these paths is built: its workers copy the table when they start."""
+        ids = self.index.ids
+        for p in paths:
+            if p == 'unknown' or p in ids:
+                continue
+            if len(ids) >= self.max_photos:
+                self.unregistered += 1
+                continue
+            ids[p] = len(ids)
+        if self.unregistered and not self._logged_overflow:
+            self._logged_overflow = True
+            logging.getLogger(__name__).warning("photo store: more than max_photos = %d distinct photos; the rest are decoded "
+                                                "every time", self.max_photos)
+        return self
+
+    def id_of(self, path):
+        return self.index.ids.get(path, -1)
+
+    def slot_of(self, path):
+        """Slot that holds `path`'s resized image, or -1."""
+        i = self.id_of(path)
+        return int(self._slot[i]) if i >= 0 else -1
+
+    def plan(self, raw):
+        """(src_slot, dst_slot) int32 [n] for a RawPhotos collated against this table's index: hits read their slot; the first
+        decoded occurrence of an id that is not resident yet gets a free slot while there is one; everything else - later
+        occurrences, photos decoded by a worker whose view lagged, photos beyond the capacity - is only resized."""
+        from ._lib import UmprHipError
+        if raw.size != self.size:
+            raise UmprHipError(f"photo store holds {self.size} photos, the batch is {raw.size}")
+        n = int(np.prod(raw.geometry))
+        ids, hits = raw.ids.numpy(), raw.hits.numpy()
+        if len(ids) != n or len(hits) != n:
+            raise UmprHipError(f"RawPhotos: {len(ids)} ids and {len(hits)} hit flags for {n} photos")
+        src = np.full(n, -1, dtype=np.int32)
+        dst = np.full(n, -1, dtype=np.int32)
+        hit = np.flatnonzero(hits)
+        if len(hit):
+            if ids[hit].min() < 0 or ids[hit].max() >= self.max_photos or self._slot[ids[hit]].min() < 0:
+                raise UmprHipError("photo store: a photo was left to the store, which does not hold it")
+            src[hit] = self._slot[ids[hit]]
+        free, full = self.used, 0
+        taken = set()
+        for i in np.flatnonzero((hits == 0) & (ids >= 0) & (ids < self.max_photos) & (raw.descriptors()["rows"] > 0)):
+            k = int(ids[i])
+            if self._slot[k] >= 0 or k in taken:
+                continue
+            if free >= self.slots:
+                full += 1
+                continue
+            dst[i] = free
+            free += 1
+            taken.add(k)
+        return src, dst, full
+
+    def commit(self, raw, src, dst, full=0):
+        """Books a fetch that has been enqueued: the filled slots become resident, for the workers too.  Returns the number of
+        slots filled."""
+        ids = raw.ids.numpy()
+        new = np.flatnonzero(dst >= 0)
+        self.decoded_while_full += full
+        self._slot[ids[new]] = dst[new]
+        self.used += len(new)
+        self.inserts += len(new)
+        self.hits += int((src >= 0).sum())
+        self.index.resident.numpy()[ids[new]] = 1
+        return len(new)
+
+    def stats(self):
+        return dict(slots=self.slots, used=self.used, hits=self.hits, inserts=self.inserts,
+                    decoded_while_full=self.decoded_while_full, unregistered=self.unregistered)
+
+
+class PhotoStore(PhotoTable):
+    """Resized photos kept in device memory: `capacity_bytes // slot_bytes` slots of 3*dh*dw uint8 (rounded up to 16), allocated
+    once.  `register(paths)` gives paths ids, `index` goes to batch_loader(store=...), and RawPhotos.to(device) finds the store
+    again by its key: the first decoded use of a photo also fills a slot, later uses read it.  No eviction: when the slots run
+    out, further photos are decoded every time."""
+
+    _registry = weakref.WeakValueDictionary()
+
+    def __init__(self, device, size=(224, 224), capacity_bytes=1 << 30, max_photos=1 << 22):
+        from ._lib import UmprHipError, lib
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("PhotoStore lives on an MI355X (no CPU path)")
+        self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        dw, dh = size
+        self.slot_bytes = lib().size("umpr_photo_store_slot_bytes", int(dh), int(dw))
+        if self.slot_bytes == 0:
+            raise UmprHipError(f"PhotoStore: bad photo size {size}")
+        super().__init__(size, int(capacity_bytes) // self.slot_bytes, max_photos)
+        self.buffer = torch.empty(max(self.slots, 1) * self.slot_bytes, dtype=torch.uint8, device=self.device)
+        self._insert_stream = self._insert_event = None
+        PhotoStore._registry[self.key] = self
+
+    @classmethod
+    def find(cls, key):
+        return cls._registry.get(key)
+
+    def fetch(self, raw, device, non_blocking=False):
+        """RawPhotos.to(device) with this store, on the current stream: float32 [B, V, P, 3, dh, dw]."""
+        from ._lib import UmprHipError, lib
+        device = torch.device(device)
+        if device.index is not None and device != self.device:
+            raise UmprHipError(f"PhotoStore on {self.device} asked for photos on {device}")
+        dw, dh = raw.size
+        n = int(np.prod(raw.geometry))
+        if raw.data.dtype != torch.uint8 or raw.data.dim() != 1 or raw.data.numel() < n * DESC.itemsize:
+            raise UmprHipError(f"RawPhotos: buffer of {raw.data.numel()} bytes cannot hold the {n} photo descriptors")
+        src, dst, full = self.plan(raw)
+        with torch.cuda.device(self.device):
+            out = torch.empty(raw.shape, dtype=torch.float32, device=self.device)
+            stream = torch.cuda.current_stream(self.device)
+            if self._insert_event is not None and stream != self._insert_stream:
+                stream.wait_event(self._insert_event)     # slots filled on another stream
+            packed = raw.data.to(self.device, non_blocking=non_blocking)
+            lib().call("umpr_photo_fetch_u8", packed, packed.numel(), raw.data, src.ctypes.data, dst.ctypes.data, len(src), dh,
+                       dw, self.buffer, self.slots, out, stream.cuda_stream)
+            if self.commit(raw, src, dst, full):               # the workers stop decoding these only now that the fill is enqueued
+                self._insert_event = torch.cuda.Event()
+                self._insert_event.record(stream)
+                self._insert_stream = stream
+        return out
+
+    def stats(self):
+        return dict(super().stats(), bytes=self.slots * self.slot_bytes)
+
+    def __repr__(self):
+        return (f"PhotoStore({self.size[0]}x{self.size[1]}, {self.used}/{self.slots} slots of {self.slot_bytes} B on "
+                f"{self.device}, {len(self.index.ids)} photos registered)")
