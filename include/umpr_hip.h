@@ -135,7 +135,15 @@ int umpr_review_merge_bwd(const float* repr_u, const float* repr_i, const float*
 
 /* ---- K8: C-Net head: Conv1d(128->KC,k=KS,pad)+ReLU+max_L, Linear(KC->V)+Sigmoid, threshold, sum p^2
  * (model.py:118-125).  X [B][S][L][128]; Wc [KC][128][KS]; Wl [V][KC].  Outputs view_p [B][S][V], final [B][V].
- * Saved: Y [B][S][L][KC], cmax [B][S][KC], argl int32 [B][S][KC], sp [B][S][V]. */
+ * Saved: Y [B][S][L][KC], cmax [B][S][KC], argl int32 [B][S][KC], sp [B][S][V].
+ * The maximum runs over the Lout = L + 2 ((KS-1)/2) - KS + 1 valid positions of nn.Conv1d(padding=(KS-1)/2): L for an odd KS, L - 1
+ * for an even one (Y holds L positions; for an even KS the last one reads a zero past the sentence and never wins).  argl is the
+ * FIRST position that attains the maximum (strict `>` while scanning l = 0 .. Lout-1): past a sentence's length the GRU output
+ * is zero, every all-zero window gives exactly relu(bc[k]), and of such bit-equal positions the lowest index receives the
+ * gradient.  view_p = sp < thr ? 0 : sp (an sp equal to thr is kept).
+ * Limits: KS >= 1, Lout >= 1, KC <= 512; the backward also needs KC % 4 == 0 and (4 V KC + 8 V) * 4 bytes <= 65536 (the LDS its
+ * head kernel requests, i.e. V (KC + 2) <= 4096: V <= 7 at KC = 512).  The backward checks every argument before its first
+ * launch or memset: a refused call writes nothing, whatever the accumulate flags. */
 size_t umpr_cnet_head_fwd_ws_bytes(int B, int S, int L, int KS);
 int umpr_cnet_head_fwd(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl, float thr,
                        int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int32_t* argl, float* sp,

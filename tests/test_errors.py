@@ -126,3 +126,32 @@ def test_second_backward_through_the_gru_raises_instead_of_faulting():
     with pytest.raises(UmprHipError, match="NULL"):
         Lb.call("umpr_embed_gru_bidir_bwd_acc", ids, emb, E, w[1], w[5], lens, order, order, N, L, out.detach(), None, None,
                 *gr, 0, ws, ws.numel() * 4, torch.cuda.current_stream().cuda_stream)
+
+
+@pytest.mark.gpu
+def test_cnet_head_bwd_refuses_before_it_writes():
+    """umpr_cnet_head_bwd checks every argument in front of its first launch or memset: a filter count that is no multiple of
+    4 (--kernel_count 122) and a V x KC whose per-wave partial sums do not fit the 64 KiB of LDS a kernel may request each
+    come back as UmprHipError naming the cause, and the gradient buffers - NaN-filled, with accumulate_dX = accumulate_w = 1 -
+    are still all NaN afterwards.  Refused arguments: no kernel runs."""
+    from umpr_amd._lib import UmprHipError, lib
+    L = lib()
+    dev = torch.device("cuda:0")
+    st = torch.cuda.current_stream().cuda_stream
+    B, S, Lm, KS = 2, 2, 5, 3
+    for KC, V, cause in ((122, 2, "122 filters"), (512, 8, "V = 8 views x KC = 512 filters")):
+        z = lambda *s: torch.zeros(*s, device=dev)
+        nan = lambda *s: torch.full(s, float("nan"), device=dev)
+        X, Wc, Wl = z(B * S, Lm, 128), z(KC, 128, KS), z(V, KC)
+        cmax, argl = z(B, S, KC), torch.zeros(B, S, KC, dtype=torch.int32, device=dev)
+        sp, vp, d_final, d_vp = z(B, S, V), z(B, S, V), z(B, V), z(B, S, V)
+        grads = [nan(B * S, Lm, 128), nan(KC, 128, KS), nan(KC), nan(V, KC), nan(V)]
+        wsb = L.size("umpr_cnet_head_bwd_ws_bytes", B, S, Lm, KC, KS, V)
+        ws = nan(wsb // 4 + 64)
+        with pytest.raises(UmprHipError, match=cause):
+            L.call("umpr_cnet_head_bwd", X, Wc, Wl, cmax, argl, sp, vp, d_final, d_vp, B, S, Lm, KC, KS, V, grads[0], 1, 1,
+                   *grads[1:], ws, wsb, st)
+        assert "cnet_bwd" in L.last_error()
+        torch.cuda.synchronize()
+        for g in grads + [ws]:
+            assert bool(torch.isnan(g).all())

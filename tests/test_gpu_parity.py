@@ -437,6 +437,10 @@ def test_review_merge(L, dev, B):
                                                    (2, 3, 11, 6, 9, 2, 2), (2, 2, 7, 4, 12, 1, 1), (2, 2, 9, 3, 10, 3, 4),
                                                    (2, 2, 70, 3, 66, 2, 3)])
 def test_control(L, dev, B, S_ui, L_ui, S, Lm, V, KS):
+    """_Control against the oracle in fp32, the oracle taking its own decisions.  Which conv position wins an argmax, which
+    sigmoid passes the 0.35 threshold and which side of 0.5 view_score falls on are not pinned here (one wrong route moves dX
+    and dWc by 1e-5 to 1e-3 of their maximum, inside this test's bound); the decisions, the saved tensors and the routing are
+    pinned by tests/test_gpu_control.py against a float64 backward that replays the HIP decisions."""
     from oracle import umpr_ref as R
     from umpr_amd.model import _Control
     from umpr_amd.synthetic import make_param_state

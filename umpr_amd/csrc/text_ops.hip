@@ -1085,6 +1085,11 @@ int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, co
                             const float* sp, const float* view_p, const float* d_final, const float* d_view_p, int B,
                             int S, int L, int KC, int KS, int V, float* dX, int accumulate_dX, int accumulate_w, float* dWc,
                             float* dbc, float* dWl, float* dbl, float* ws, size_t ws_bytes, hipStream_t s) {
+  // every argument check comes before the first launch or memset: a refused call writes nothing
+  UMPR_REQUIRE(KS >= 1 && (KC & 3) == 0 && KC <= 512, "cnet_bwd: kernel size %d / %d filters (a multiple of 4, at most 512)", KS, KC);
+  const size_t head_lds = ((size_t)4 * V * KC + (size_t)8 * V) * sizeof(float);   // cnet_head_bwd_kernel: dW[4][V*KC], db[4][V], dsig[4][V]
+  UMPR_REQUIRE(V >= 1 && head_lds <= 65536, "cnet_bwd: V = %d views x KC = %d filters need %zu bytes of LDS, above the 65536 a kernel may request",
+               V, KC, head_lds);
   UMPR_REQUIRE(ws_bytes >= umpr_cnet_bwd_ws_bytes(B, S, L, KC, KS, V), "cnet_bwd: workspace too small");
   const long R = (long)B * S * L;
   const int CK = D * KS;
@@ -1097,13 +1102,12 @@ int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, co
   float* slab = cs + (size_t)cdiv(R, 256) * KC;
   if (hipMemsetAsync(dY, 0, (size_t)R * KC * sizeof(float), s) != hipSuccess) { umpr_set_error("cnet_bwd: memset"); return -2; }
   CnetHeadBwdParams p{cmax, argl, sp, view_p, Wl, d_final, d_view_p, dY, dWl_part, dbl_part, S, L, KC, V};
-  cnet_head_bwd_kernel<<<B, 256, (4 * V * KC + 8 * V) * sizeof(float), s>>>(p);
+  cnet_head_bwd_kernel<<<B, 256, head_lds, s>>>(p);
   UMPR_LAUNCH_CHECK("cnet_head_bwd");
   colsum_stage2_kernel<<<cdiv(V * KC, 64), 256, 0, s>>>(dWl_part, B, V * KC, dWl, accumulate_w);
   colsum_stage2_kernel<<<cdiv(V, 64), 256, 0, s>>>(dbl_part, B, V, dbl, accumulate_w);
   UMPR_LAUNCH_CHECK("cnet_dWl");
   if (int rc = umpr_colsum(dY, R, KC, KC, dbc, accumulate_w, cs, (size_t)cdiv(R, 256) * KC * sizeof(float), s)) return rc;
-  UMPR_REQUIRE(KS >= 1 && (KC & 3) == 0, "cnet_bwd: kernel size %d / %d filters", KS, KC);
   const int pad = (KS - 1) / 2;
   UmprGemm h;  // dWp[KC][CK] = dY^T win(X)
   h.A = dY; h.lda = KC; h.transA = true; h.B = X; h.ldb = D; h.winB_L = L; h.winB_D = D; h.winB_pad = pad;
