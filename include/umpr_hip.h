@@ -370,6 +370,31 @@ int umpr_adam_step(float* p, const float* g, float* m, float* v, long n, double 
 int umpr_adam_step_dev(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
                        const float* hyper, void* stream);
 
+/* ---- Gradient clipping by global norm (torch.nn.utils.clip_grad_norm_, L2) fused into the optimiser step --------------
+ * umpr_grad_norm: norm = |grad_scale| * sqrt(sum of squares over every element of the n_arenas flat arrays) and
+ * coef = min(1, max_norm / (norm + 1e-6)), both formed in double and rounded once to float.  grads / counts are HOST arrays of
+ * n_arenas (<= 8) device pointers / element counts, read during the call; any float-aligned pointer and any count >= 0 are
+ * accepted.  The scale is grad_scale_dev[0] (device memory: what a captured graph reads) if that pointer is not NULL, the host
+ * value grad_scale otherwise.  Two launches on a fixed grid - squares exact in double, one double partial per workgroup in ws,
+ * one workgroup adds the partials in a fixed order - and no atomics: the result is bit-reproducible and does not depend on the
+ * device.  No allocation, no copy: capture-safe.  ws: umpr_grad_norm_ws_bytes() bytes of device memory.
+ * state: 8 device floats the caller zeroes once; every call writes the first four and advances the counters:
+ *   [COEF] the coefficient (0 if the norm is not finite)   [NORM] the norm of the scaled gradient, before clipping
+ *   [FINITE] 1.0f / 0.0f                                   [MAX_NORM] max_norm as given
+ *   [SEEN] [CLIPPED] [SKIPPED] uint32 counters in the float slots: calls, calls with coef < 1, calls with a non-finite norm. */
+enum { UMPR_CLIP_COEF = 0, UMPR_CLIP_NORM = 1, UMPR_CLIP_FINITE = 2, UMPR_CLIP_MAX_NORM = 3, UMPR_CLIP_SEEN = 4,
+       UMPR_CLIP_CLIPPED = 5, UMPR_CLIP_SKIPPED = 6 };
+size_t umpr_grad_norm_ws_bytes(void);
+int umpr_grad_norm(const float* const* grads, const long* counts, int n_arenas, double max_norm, float grad_scale,
+                   const float* grad_scale_dev /*or NULL*/, double* ws, size_t ws_bytes, float* state, void* stream);
+
+/* umpr_adam_step / umpr_adam_step_dev with the gradient scale multiplied by state[COEF] (one float product of the two scalars:
+ * with COEF == 1 the update is bit-identical to the unclipped entry points).  state[FINITE] == 0 leaves p, m and v untouched. */
+int umpr_adam_step_clip(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
+                        double eps, double weight_decay, long step, double grad_scale, const float* state, void* stream);
+int umpr_adam_step_dev_clip(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
+                            const float* hyper, const float* state, void* stream);
+
 /* ---- evaluate_mse (src/evaluate.py:12-13, `mse_loss(pred, labels, reduction='sum')` accumulated over batches) -----
  * acc[0] += sum_i (pred[i] - label[i])^2, acc[1] += n; acc = two device doubles the caller zeroed once and reads back
  * once after the last batch (the reference's `.item()` per batch is a host sync per batch). */

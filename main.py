@@ -2,6 +2,7 @@
 """Entry point mirroring the reference's main.py (config surface: config.py, run recipes: readme.md:70-92).
 
     python main.py --data_dir synthetic --batch_size 64                       # single MI355X
+    python main.py --data_dir synthetic --learning_rate 1e-3 --grad_clip 5.0  # clip the gradient to a global 2-norm of 5
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
 
 The model / optimiser / train / evaluate drivers are the MI355X-native ones (umpr_amd).  With a data_dir that holds
@@ -166,7 +167,7 @@ def main():
 
 def _main():
     extra = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
-             "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0}
+             "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0}
     Config.extend(extra)
     config = Config()
     rank, local, world = parallel.init_distributed()

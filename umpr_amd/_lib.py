@@ -104,6 +104,10 @@ SIGNATURES = {
     "umpr_adam_step": ("ppppldddddldp", "i"),
     "umpr_sq_err_accumulate": ("pplpp", "i"),
     "umpr_adam_step_dev": ("pppplddd" "pp", "i"),
+    "umpr_grad_norm_ws_bytes": ("", "z"),
+    "umpr_grad_norm": ("ppidfppzpp", "i"),
+    "umpr_adam_step_clip": ("ppppldddddld" "pp", "i"),
+    "umpr_adam_step_dev_clip": ("pppplddd" "ppp", "i"),
     "umpr_debug_poison_lds": ("pp", "i"),
     "umpr_set_gemm_bf16": ("i", "i"),
     "umpr_set_conv_inference": ("i", "i"),

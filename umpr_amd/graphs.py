@@ -73,6 +73,7 @@ class GraphedTrainStep:
         # warm-up (allocations, lazy initialisations) and capture must not change the training state: keep and restore it
         keep = [(g.p.clone(), g.m.clone(), g.v.clone()) for g in opt.groups]
         step0 = opt.step_count
+        clip0 = opt.clip_state.clone() if opt.max_grad_norm > 0.0 else None     # the clipping counters advance in the warm-up too
         model._static_index = self.static_index
         side = torch.cuda.Stream(dev)
         side.wait_stream(torch.cuda.current_stream(dev))
@@ -88,6 +89,8 @@ class GraphedTrainStep:
         with torch.no_grad():
             for g, (p, m, v) in zip(opt.groups, keep):
                 g.p.copy_(p); g.m.copy_(m); g.v.copy_(v)
+            if clip0 is not None:
+                opt.clip_state.copy_(clip0)
         opt.step_count = step0
 
     def _body(self):

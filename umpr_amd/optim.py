@@ -8,6 +8,8 @@ the data-parallel gradient exchange is a handful of large RCCL all-reduces on th
 """
 from __future__ import annotations
 
+import ctypes
+import math
 import os
 import weakref
 
@@ -107,9 +109,25 @@ class _Group:
 
 
 class FusedAdam:
-    """Adam(betas=(0.9,0.999), eps=1e-8) with the reference's grouping; ``lr_decay`` per ``epoch_end()``."""
+    """Adam(betas=(0.9,0.999), eps=1e-8) with the reference's grouping; ``lr_decay`` per ``epoch_end()``.
 
-    def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None):
+    ``max_grad_norm`` > 0 clips the gradient by its global 2-norm inside ``step()``, as ``torch.nn.utils.clip_grad_norm_(...,
+    max_grad_norm)`` between ``backward()`` and ``step()`` would: the norm is that of the gradient the update uses (after
+    ``grad_scale``, before the coupled L2 term), the coefficient is min(1, max_grad_norm / (norm + 1e-6)).  One reduction over the
+    gradient arenas (``umpr_grad_norm``: fixed grid, no atomics, bit-reproducible) leaves the coefficient in device memory and the
+    Adam kernels read it from there: no host round trip, so it also runs inside a captured graph.  A step whose norm is not finite
+    (an inf or NaN anywhere in the gradient) is SKIPPED: parameters and moments stay as they are.  ``step_count`` still advances
+    on a skipped step - the bias corrections are computed on the host, which does not wait for the flag.  While clipping is on the
+    early update of the classifier slice is off (``arm_early``): the coefficient is not known before every gradient exists.
+    0 (the default) is off: the step launches exactly what it launches without this argument."""
+
+    def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None,
+                 max_grad_norm=0.0):
+        max_grad_norm = float(max_grad_norm)
+        if not math.isfinite(max_grad_norm) or max_grad_norm < 0.0:
+            raise ValueError(f"max_grad_norm must be finite and >= 0 (0 turns clipping off), got {max_grad_norm}")
+        self.max_grad_norm = max_grad_norm
+        self._clip = None           # device state of the clipping path, made by the first clipped step
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if order_key is None:
             # the VGG classifier's gradients are produced first in backward and are 89 % of all gradient bytes: put them
@@ -205,7 +223,7 @@ class FusedAdam:
         UMPR_EARLY_ADAM=0 turns it off.  Worth 0.3-0.5 ms per step behind the all-reduce in the RCCL rehearsal (43.16 vs
         43.49 ms fp32, 16.06 vs 16.51 ms bf16); on a single GPU 0.1-0.3 ms in bf16 (9.56 vs 9.71 ms) and nothing in fp32.  Its stream is one more next to main / text / weight-gradient / RCCL:
         umpr_amd/__init__.py sets GPU_MAX_HW_QUEUES, the number of hardware queues they share."""
-        if _EARLY_ADAM == "0":
+        if _EARLY_ADAM == "0" or self.max_grad_norm > 0.0:   # clipping: the coefficient needs every gradient first
             return
         self._early = (float(grad_scale),)
         self._early_done = None
@@ -252,12 +270,67 @@ class FusedAdam:
             ev.record(self._early_stream)
         self._early_done = (lo, hi, ev)
 
+    # ---- clipping by global norm (max_grad_norm > 0) -------------------------------------------------------------------------
+    def _clip_buffers(self):
+        """(state, workspace, arena pointers, arena counts, number of arenas) of the clipping path; the arenas never move, so the
+        two host tables umpr_grad_norm reads are built once."""
+        if self._clip is None:
+            dev = self.groups[0].p.device
+            arenas = self.grad_arenas()
+            ptrs = (ctypes.c_void_p * max(len(arenas), 1))(*[a.data_ptr() for a in arenas])
+            counts = (ctypes.c_long * max(len(arenas), 1))(*[a.numel() for a in arenas])
+            state = torch.zeros(8, dtype=torch.float32, device=dev)
+            ws_bytes = lib().size("umpr_grad_norm_ws_bytes")
+            ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+            self._clip = (state, ws, ws_bytes, ptrs, counts, len(arenas))
+        return self._clip
+
+    @property
+    def clip_state(self):
+        """The 8-float device state umpr_grad_norm maintains (include/umpr_hip.h), or None while clipping is off."""
+        return self._clip_buffers()[0] if self.max_grad_norm > 0.0 else None
+
+    def clip_stats(self):
+        """{"norm", "coef", "clipped", "skipped", "seen"}: the last step's gradient norm (scaled, before clipping) and
+        coefficient, and how many steps were clipped / skipped / taken with clipping on.  Reads device memory, so it
+        SYNCHRONISES: call it where the loop logs, not per step."""
+        if self.max_grad_norm <= 0.0:
+            raise RuntimeError("clip_stats: clipping is off (FusedAdam(max_grad_norm=0))")
+        host = self._clip_buffers()[0].cpu()
+        cnt = host.view(torch.int32)
+        return {"norm": float(host[1]), "coef": float(host[0]), "clipped": int(cnt[5]), "skipped": int(cnt[6]),
+                "seen": int(cnt[4])}
+
+    def _step_clipped(self, grad_scale):
+        state, ws, ws_bytes, ptrs, counts, n_arenas = self._clip_buffers()
+        hyper = getattr(self, "_hyper", None)
+        for g in self.groups:                          # the norm reads every arena: all stale slices are zeroed first
+            for p in g.direct:
+                if getattr(p, "_umpr_fresh", False):   # no backward node wrote it since zero_grad: its gradient is zero
+                    p.grad.zero_()
+                    p._umpr_fresh = False
+        # every group carries the same grad_scale: in graph mode the norm kernel reads the first group's from device memory
+        lib().call("umpr_grad_norm", ctypes.addressof(ptrs), ctypes.addressof(counts), n_arenas, self.max_grad_norm,
+                   float(grad_scale), hyper[0] if hyper is not None else None, ws, ws_bytes, state, stream_ptr())
+        for gi, g in enumerate(self.groups):
+            if not g.numel:
+                continue
+            if hyper is not None:
+                lib().call("umpr_adam_step_dev_clip", g.p, g.g, g.m, g.v, g.numel, self.betas[0], self.betas[1], self.eps,
+                           hyper[gi], state, stream_ptr())
+            else:
+                lib().call("umpr_adam_step_clip", g.p, g.g, g.m, g.v, g.numel, self.lr, self.betas[0], self.betas[1], self.eps,
+                           g.weight_decay, self.step_count, grad_scale, state, stream_ptr())
+
     def step(self, grad_scale=1.0):
         if self.groups[0].p.device.type != "cuda":
             raise RuntimeError("FusedAdam.step launches a HIP kernel: the model must be on a cuda device")
         self.step_count += 1
         wait_for_gradients(self.groups[0].p.device)    # in-place gradients written from a side stream (umpr_amd/streams.py)
         done, self._early_done, self._early = self._early_done, None, None
+        if self.max_grad_norm > 0.0:
+            assert done is None                        # arm_early never armed
+            return self._step_clipped(grad_scale)
         for gi, g in enumerate(self.groups):
             for p in g.direct:
                 if getattr(p, "_umpr_fresh", False):   # no backward node wrote it since zero_grad: its gradient is zero

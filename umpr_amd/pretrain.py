@@ -91,11 +91,13 @@ class PretrainRNet(nn.Module):
 
 
 def pretrain_r_net(word2vec, batches, save_r_net_path=None, *, gru_size=64, learning_rate=0.01, lr_decay=0.99,
-                   l2_regularization=1e-3, train_epochs=10, device="cuda", log=print):
-    """Training loop of pretrain_rnet.py:172-205.  ``batches``: a re-iterable of (u, u_length, i, i_length, target)."""
+                   l2_regularization=1e-3, train_epochs=10, device="cuda", log=print, grad_clip=0.0):
+    """Training loop of pretrain_rnet.py:172-205.  ``batches``: a re-iterable of (u, u_length, i, i_length, target).
+    ``grad_clip`` > 0 (not in the reference): clip the gradient to that global 2-norm inside the optimiser step."""
     from .optim import FusedAdam
+    from .train import clip_note
     model = PretrainRNet(word2vec, gru_hidden=gru_size).to(device)
-    opt = FusedAdam(model, learning_rate, l2_regularization, lr_decay=lr_decay)
+    opt = FusedAdam(model, learning_rate, l2_regularization, lr_decay=lr_decay, max_grad_norm=grad_clip)
     for epoch in range(train_epochs):
         model.train()
         total_loss, total_samples = 0.0, 0
@@ -107,7 +109,7 @@ def pretrain_r_net(word2vec, batches, save_r_net_path=None, *, gru_size=64, lear
             total_loss += loss.item() * len(result)
             total_samples += len(result)
         opt.epoch_end()  # ExponentialLR, stepped per epoch (pretrain_rnet.py:200)
-        log(f"Epoch {epoch:3d}; train loss {total_loss / max(total_samples, 1):.6f}")
+        log(f"Epoch {epoch:3d}; train loss {total_loss / max(total_samples, 1):.6f}" + clip_note(opt))
     if save_r_net_path:
         model.save_r_net(save_r_net_path)
     return model

@@ -84,6 +84,15 @@ def train_step(model, opt: FusedAdam, batch, world=1, reducer=None):
     return pred, loss
 
 
+def clip_note(opt):
+    """'; grad norm ...; clipped a/n, skipped b' for a log line while gradient clipping is on, '' otherwise (the line then
+    stays as it was).  Synchronises (FusedAdam.clip_stats)."""
+    if opt.max_grad_norm <= 0.0:
+        return ""
+    st = opt.clip_stats()
+    return f"; grad norm {st['norm']:.4f}; clipped {st['clipped']}/{st['seen']}, skipped {st['skipped']}"
+
+
 def _shuffle_generator(loader):
     """The torch.Generator that orders a (possibly wrapped) DataLoader's epochs, or None."""
     seen = 0
@@ -100,12 +109,15 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     """main.py:16-61.  Returns (optimiser, saved): `saved` says whether THIS run wrote `model_path`.
     Not in the reference: `config.resume` continues a run exactly - parameters, Adam moments, learning rate, the
     epoch's shuffle order, the position inside the epoch and the dropout counters all come from the checkpoint, so the
-    resumed run visits the batches the uninterrupted run would have visited next."""
+    resumed run visits the batches the uninterrupted run would have visited next.  `config.grad_clip` > 0 clips the gradient to
+    that global 2-norm inside the optimiser step (FusedAdam(max_grad_norm=)); the log lines then carry the last norm and the
+    clipped / skipped counts."""
     log = logger.info if logger else print
     valid_mse = evaluate_mse(model, valid_dataloader)
     log(f'Initial validation mse is {valid_mse:.6f}')
     start = time.perf_counter()
-    opt = FusedAdam(model, config.learning_rate, config.l2_regularization, config.lr_decay)
+    opt = FusedAdam(model, config.learning_rate, config.l2_regularization, config.lr_decay,
+                    max_grad_norm=float(getattr(config, "grad_clip", 0.0)))
     reducer = parallel.GradReducer(opt) if parallel.active() else None
     best_loss, batch_counter, first_epoch, skip, saved = 100, 0, 0, 0, False
     valid_every = int(getattr(config, "valid_every", 500))   # the reference hard-codes 500 (main.py:43)
@@ -133,7 +145,7 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
             if batch_counter % valid_every == 0:
                 valid_mse = evaluate_mse(model, valid_dataloader)
                 log(f'Epoch {epoch:2d}; batch {batch_counter:5d}; train loss {total_loss / max(total_samples, 1):.6f}; '
-                    f'valid mse {valid_mse:.6f}')
+                    f'valid mse {valid_mse:.6f}' + clip_note(opt))
                 if best_loss > valid_mse:        # valid_mse is all-reduced: every rank takes the same branch
                     best_loss = valid_mse
                     if rank == 0:
@@ -145,7 +157,7 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
         opt.epoch_end()
         dt = time.perf_counter() - t0
         log(f'Epoch {epoch:3d} done; train loss {total_loss / max(total_samples, 1):.6f}; '
-            f'{world * total_samples / max(dt, 1e-9):.1f} samples/s')
+            f'{world * total_samples / max(dt, 1e-9):.1f} samples/s' + clip_note(opt))
         if batch_counter > 50000:
             break
     sec = int(time.perf_counter() - start)
