@@ -64,7 +64,12 @@ long umpr_debug_wino_fix_count(void);
  * the tie order torch.sort produced); dst_row [N]: input row n lands in output row dst_row[n] (= sorted_indices[n]
  * for the reference's semantics; must be a permutation of 0..N-1: each output row is written - values up to its length, zeros
  * past it - by the sequence that owns it).  out [N][L][128] (zeros past each length).  saved [2][N][L][4][64] (gates for
- * backward) or NULL for inference. */
+ * backward) or NULL for inference.
+ * Pinned by tests/test_gpu_gru.py against a float64 recurrence: a length of 0 yields an all-zero output row and no gradient; a
+ * length above L is treated as L; `order` and `dst_row` are independent (a sequence's values do not depend on either);
+ * saved[dir][n][t] = (r, z, n, W_hn h + b_hn) is indexed by INPUT row n and is defined only for t < length - the forward leaves
+ * the rest untouched, and no value of saved or dout at t >= length reaches the backward's results.  Every byte of out, of the
+ * gradients and of the workspace that a call uses was written by that call: none of them needs to be cleared. */
 size_t umpr_embed_gru_bidir_ws_bytes(int N, int L, int E);
 int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
                              const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
