@@ -487,6 +487,12 @@ def test_control(L, dev, B, S_ui, L_ui, S, Lm, V, KS):
 
 @pytest.mark.parametrize("B,V,Pc", [(5, 1, 1), (3, 4, 2), (6, 0, 0)])
 def test_head(L, dev, B, V, Pc):
+    """_Head against torch fp32 on the CPU, torch taking its own decisions, with the loss alone back-propagated.  Which side of 0
+    z falls on (the ReLU on the prediction; with fb = 0.7 and labels 1..5 hardly any z is negative here) and the signs of
+    pos_emb - img_emb and neg_emb - img_emb under the abs are not pinned here (one wrong sign on a small element moves a gradient
+    by far less than 1e-3 of its maximum, inside this test's bound), nor are the saved tensors, loss[1] / loss[2], a given d_pred
+    or any batch beyond 6; the decisions, the saved tensors, the d_pred call forms and the batch edges up to the LDS bound of
+    umpr_head_bwd are pinned by tests/test_gpu_head.py against a float64 backward that replays the HIP decisions."""
     from umpr_amd.model import _Head
     g = torch.Generator().manual_seed(B + V)
     rn = lambda *s: torch.randn(*s, generator=g)
