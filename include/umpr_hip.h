@@ -30,7 +30,11 @@ int umpr_device_info(int dev, char* name, int name_len, int* compute_units, size
  * Replaces torch.mm/addmm/Linear call sites on the path (model.py:50,75,120,154-155,167-168; VGG classifier).
  * op(A)(m,k) = transA ? A[k*lda+m] : A[m*lda+k];  op(B)(k,n) = transB ? B[n*ldb+k] : B[k*ldb+n].
  * bias_mode: 0 none, 1 bias[n], 2 bias[m].  act: 0 none, 1 relu, 2 tanh, 3 sigmoid.
- * ws/ws_bytes: optional split-K workspace (used when the grid would not fill the GPU). */
+ * ws/ws_bytes: optional split-K workspace (used when the grid would not fill the GPU).  A workspace too small for the chosen
+ * split is used for as many slabs of M * N floats as fit, one slab or less means no split; nothing is written behind ws_bytes.
+ * K = 0 is accepted and gives C = act(bias + (accumulate ? C : 0)).  lda / ldb / ldc may exceed the row length and the bases
+ * need no alignment (16-byte loads are used only where base, pitch and extent allow them); the gap columns of a C with
+ * ldc > N are never written.  Every element of C[0..M)[0..N) is written by the call. */
 int umpr_gemm_f32(const float* A, long lda, int transA, const float* B, long ldb, int transB, float* C, long ldc,
                   int M, int N, int K, const float* bias, int bias_mode, int act, int accumulate, float alpha,
                   float* ws, size_t ws_bytes, void* stream);
@@ -208,7 +212,15 @@ int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
  * images [n][3][224][224]; params: 32 pointers = 13 x (conv weight [Cout][Cin][3][3], bias) then 3 x (fc weight
  * [out][in], bias) in torchvision order.  acts: activation arena (umpr_vgg16_act_bytes), kept for backward.
  * train!=0 applies Dropout(0.5) after fc1/fc2 with a counter-hash mask from `seed`; use_masks!=0 reads the caller's
- * keep-masks (uint8 [2][n][4096] in `masks`) instead (parity tests).  out [n][1000]. */
+ * keep-masks (uint8 [2][n][4096] in `masks`) instead (parity tests).  out [n][1000].
+ * Generated masks are bytes 0 / 1 and a pure function of (seed, layer, element index): layer j hashes the element index
+ * row * 4096 + column with seed + (j + 1) * 0x9E3779B97F4A7C15, so a row's mask does not depend on n_img and the same seed
+ * gives the same bytes.  Injected masks are read only.  A call writes every byte it uses: the classifier forward all of out,
+ * the fc1 / fc2 regions of the arena and - when dropout runs - the two dropout regions and, when it generates them, the masks
+ * (in eval mode the dropout regions and the masks are not touched); the backward all six classifier gradients and d_pool5;
+ * neither reads workspace bytes it has not written itself.  n_img < 1 and a workspace below the queried size are refused
+ * before anything is launched.  Above 128 images the classifier's products run on the generic GEMM above (in its bf16 mode
+ * under the _bf16 entry points). */
 size_t umpr_vgg16_act_bytes(int n_img);
 size_t umpr_vgg16_fwd_ws_bytes(int n_img);
 size_t umpr_vgg16_ws_bytes(int n_img); /* backward workspace */

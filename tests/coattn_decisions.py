@@ -147,8 +147,10 @@ def runner_up(A64, b, k):
 
 def distances(got, ref):
     """(max |got - ref| / max |ref|, relative L2) in float64.  Where the reference is identically zero - dM at SL = 1,
-    where the softmax over one position is the constant 1 - the only result at distance 0 is exact zero."""
-    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    where the softmax over one position is the constant 1 - the only result at distance 0 is exact zero.  Computed where `ref`
+    lives (the CPU everywhere but for the 103 M-element classifier gradients, whose reference is held on the device)."""
+    ref = ref.detach().double()
+    got = got.detach().to(ref.device).double()
     assert got.shape == ref.shape, (got.shape, ref.shape)
     scale, norm = float(ref.abs().max()), float(ref.norm())
     if scale == 0.0:

@@ -14,6 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import classifier_reference as CR
 from conftest import ROOT, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -226,60 +227,205 @@ class _QLinear(torch.autograd.Function):
         return (gq @ q(w).double()).float(), (gq.t() @ q(x).double()).float(), g.double().sum(0).float()
 
 
-@pytest.mark.parametrize("n", [4, 64])
-def test_classifier_bf16_through_c_abi(L, dev, n):
+CLS_GUARD = 4096            # floats behind every buffer a classifier call writes
+ROW_REL_L2 = 2e-5           # a row of one layer against the rounded-operand product of its own input: fc1's bound, per row
+
+
+def _cls_weights(dev):
+    """the three layers' parameters on the device (randn * (2 / fin)^0.5, biases 0.1 randn): classifier_reference's shared copy"""
+    return CR.device_weights(dev)
+
+
+@pytest.fixture(scope="module")
+def cls_weights(dev):
+    """builds the shared copy before the first classifier case runs, so that no case's own time contains it"""
+    yield _cls_weights(dev)
+    _CLS_POOL.clear()
+
+
+_CLS_POOL = {}
+
+
+def _guarded(dev, numel, pooled=None):
+    """(NaN-filled buffer of numel floats, the NaN guard band behind it).  pooled: carved from one device allocation that only
+    grows (the workspaces: several GB, a different size for every n - a fresh device allocation per case costs more than the case)"""
+    if pooled is None:
+        t = torch.full((numel + CLS_GUARD,), float("nan"), device=dev)
+    else:
+        if pooled not in _CLS_POOL or _CLS_POOL[pooled].numel() < numel + CLS_GUARD:
+            _CLS_POOL.pop(pooled, None)
+            _CLS_POOL[pooled] = torch.empty(numel + CLS_GUARD, device=dev)
+        t = _CLS_POOL[pooled][:numel + CLS_GUARD]
+        t.fill_(float("nan"))
+    return t[:numel], t[numel:]
+
+
+def _row_rel_l2(a, b):
+    a, b = a.double(), b.double()
+    return (a - b).norm(dim=1) / (b.norm(dim=1) + 1e-30)
+
+
+def _classifier_bf16_case(L, dev, n, train, own_decisions=False):
+    """umpr_vgg16_classifier_{fwd,bwd}_compact_bf16 against the same three layers in torch with bf16-rounded operands (train: with
+    injected dropout masks - scaling by 2 is exact in bf16, so the bounds carry over).  out, the fc / drop regions, the gradients,
+    d_pool5 and the workspaces (exactly the queried size) are NaN-filled with a NaN guard band behind each.
+
+    Forward: fc1 (2e-5) and out (1e-3) against the chain of _QLinear layers, and EVERY layer - fc1, fc2, out - row by row against
+    the rounded-operand product of its own HIP input (classifier_reference.layer_forward_bf16) at fc1's bound, 2e-5: each is a
+    single product of rounded operands in which only the fp32 summation order differs, and held per row no batch row of any
+    layer can hide in the norm of the others.  The rows of out against the CHAIN are logged, not asserted: the bf16 re-rounding
+    noise the 1e-3 bound describes reaches 1.0e-3 .. 1.3e-3 on single rows (n = 127; n = 65 train), with every layer pinned per row
+    at 1e-7 of its own input.
+    Backward: the reference (classifier_backward_bf16, the same rounded-operand float64 products as _QLinear.backward) takes its
+    ReLU decisions and layer inputs from the arena the HIP forward wrote.  With the reference's own decisions ONE fc2 unit whose
+    sign lands differently moves that batch row's gradient by 1 / sqrt(2048) = 2e-2 and every gradient below by 2e-2 / sqrt(n):
+    at n = 65, 128, 129 (eval) dW1, db1, dW2, db2 and d_pool5 are then 2.8e-3 .. 4.3e-3 from it with ONE row of d_pool5 at 2.8e-2 ..
+    3.3e-2, all other rows at 1e-4.  d_pool5 is held row by row as well.  own_decisions (n = 4 and 64, where no unit flips): the
+    comparison with autograd through the chain's own forward runs too, with its assertions as they always were."""
+    from umpr_amd.model import _ptr_array
+    tag = f"classifier bf16 n{n}{' train' if train else ''}"
+    g = torch.Generator().manual_seed(11 + n)
+    params = _cls_weights(dev)
+    x = torch.rand(n, 25088, generator=g).to(dev)
+    gout = torch.randn(n, 1000, generator=g).to(dev)
+    mk = (torch.rand(2, n, 4096, generator=g) < 0.5).to(torch.uint8).to(dev) if train else None
+    # reference of the forward: the chain
+    with torch.no_grad():
+        h1 = torch.relu(_QLinear.apply(x, params[0], params[1]))
+        h = h1 * mk[0].float() * 2.0 if train else h1
+        h = torch.relu(_QLinear.apply(h, params[2], params[3]))
+        if train:
+            h = h * mk[1].float() * 2.0
+        ref = _QLinear.apply(h, params[4], params[5])
+    # C ABI
+    nb = L.size("umpr_vgg16_cls_arena_bytes", n)
+    arena, arena_guard = _guarded(dev, nb // 4)
+    arena[: n * 25088] = x.reshape(-1)
+    masks = torch.full((2 * n * 4096 + 4 * CLS_GUARD,), 0xFF, device=dev, dtype=torch.uint8)
+    if train:
+        masks[: 2 * n * 4096] = mk.reshape(-1)
+    out, out_guard = _guarded(dev, n * 1000)
+    wsb = L.size("umpr_vgg16_fwd_ws_bytes", n)
+    ws, ws_guard = _guarded(dev, wsb // 4, pooled="ws")
+    keep, parr = _ptr_array([params[0]] * 26 + params)
+    L.call("umpr_vgg16_classifier_fwd_compact_bf16", parr, n, 0, int(train), 0, arena, masks, out, ws, wsb, st())
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(ws_guard).all()), f"{tag}: guard band of the forward workspace written"   # the backward reuses the pool
+    guards = {"arena": arena_guard, "out": out_guard}
+    del ws, ws_guard
+    out = out.view(n, 1000)
+    regions = arena[n * 25088:].view(4, n, 4096)
+    fc, drop = [regions[0], regions[1]], [regions[2], regions[3]]
+    e1 = rel_l2(fc[0].cpu(), h1.cpu())
+    e = rel_l2(out.cpu(), ref.cpu())
+    assert torch.isfinite(regions[:2]).all()
+    xs = CR.layer_inputs(x, fc, drop, train)
+    rows = {}
+    for j, (nm, got) in enumerate(zip(CR.FWD_NAMES, fc + [out])):
+        own = CR.layer_forward_bf16(xs[j], params[2 * j], params[2 * j + 1], j < 2, device=dev)
+        live = own.norm(dim=1) > 0
+        assert bool((got[~live] == 0).all()), f"{tag}: {nm} has a nonzero row where the reference row is zero"
+        rows[nm] = float(_row_rel_l2(got[live], own[live]).max()) if bool(live.any()) else 0.0
+    log(f"{tag}: fc1 relL2 {e1:.2e} out relL2 {e:.2e} worst row of out against the chain {float(_row_rel_l2(out, ref).max()):.2e} | "
+        "worst row against the layer's own input: " + " ".join(f"{k} {v:.2e}" for k, v in rows.items()))
+    assert torch.isfinite(out).all() and e1 <= 2e-5 and e <= 1e-3
+    assert max(rows.values()) <= ROW_REL_L2, rows
+    if train:
+        assert torch.equal(masks[: 2 * n * 4096].view(2, n, 4096), mk)
+        for j in range(2):
+            assert torch.equal(drop[j], torch.where(mk[j].bool(), 2 * fc[j], torch.zeros((), device=dev)))
+    else:
+        assert bool(torch.isnan(regions[2:]).all()) and bool((masks == 0xFF).all())
+    assert bool((masks[2 * n * 4096:] == 0xFF).all())
+    grads, grad_guards = zip(*[_guarded(dev, p.numel()) for p in params])
+    d_pool5, guards["d_pool5"] = _guarded(dev, n * 25088)
+    wsb2 = L.size("umpr_vgg16_classifier_bwd_ws_bytes", n)
+    ws2, guards["bwd ws"] = _guarded(dev, wsb2 // 4, pooled="ws")
+    keep_g, garr = _ptr_array([grads[0]] * 26 + list(grads))
+    L.call("umpr_vgg16_classifier_bwd_compact_bf16", parr, n, int(train), arena, masks, gout, garr, d_pool5, ws2, wsb2, st())
+    torch.cuda.synchronize()
+    del ws2
+    d_pool5 = d_pool5.view(n, 25088)
+    g64, dx64 = CR.classifier_backward_bf16(x, fc, drop, params, gout, mk, device=dev)
+    bad = {}
+    for i, (gr, r) in enumerate(zip(grads, g64)):
+        e = float((gr.view(r.shape).double() - r).norm() / (r.norm() + 1e-30))
+        log(f"{tag}: d param {i} relL2 {e:.2e}")
+        if not (torch.isfinite(gr).all() and e <= 1e-3):
+            bad[i] = e
+    e = float((d_pool5.double() - dx64).norm() / (dx64.norm() + 1e-30))
+    er = float(_row_rel_l2(d_pool5, dx64).max())
+    log(f"{tag}: d pool5 relL2 {e:.2e} worst row {er:.2e}")
+    assert torch.isfinite(d_pool5).all() and e <= 1e-3 and not bad, (e, bad)
+    assert er <= 1e-3, er
+    guards.update({f"d param {i}": gg for i, gg in enumerate(grad_guards)})
+    written = [k for k, gg in guards.items() if not bool(torch.isnan(gg).all())]
+    assert not written, f"{tag}: guard bands written: {written}"
+    if own_decisions:
+        ps = [p.clone().requires_grad_(True) for p in params]
+        xr = x.clone().requires_grad_(True)
+        h = torch.relu(_QLinear.apply(xr, ps[0], ps[1]))
+        h = torch.relu(_QLinear.apply(h, ps[2], ps[3]))
+        _QLinear.apply(h, ps[4], ps[5]).backward(gout)
+        bad = {}
+        for i, (gr, pr) in enumerate(zip(grads, ps)):
+            e = rel_l2(gr.view(pr.shape), pr.grad)
+            log(f"{tag}: d param {i} relL2 {e:.2e} (autograd through the chain's own forward)")
+            if not (torch.isfinite(gr).all() and e <= 1e-3):
+                bad[i] = e
+        e = rel_l2(d_pool5, xr.grad)
+        log(f"{tag}: d pool5 relL2 {e:.2e} (autograd through the chain's own forward)")
+        assert torch.isfinite(d_pool5).all() and e <= 1e-3 and not bad, (e, bad)
+
+
+@pytest.mark.parametrize("n", [4, 64, 1, 15, 16, 17, 33, 65, 127, 128, 129])
+def test_classifier_bf16_through_c_abi(L, dev, cls_weights, n):
     """umpr_vgg16_classifier_{fwd,bwd}_compact_bf16 (eval mode: no dropout) against the same three layers in torch with
     bf16-rounded operands.  The first layer's output is a single product of rounded operands: only the fp32 summation
     order differs (<= 2e-5 relative L2).  Behind it the ~1e-5 summation noise of a K = 25088 dot product moves a few per
     mille of the activations across a bf16 rounding boundary when the NEXT product rounds them (one bf16 ulp = 4e-3
     each), so outputs and gradients further down agree to ~2e-4 (measured); the bound there is 1e-3, a quarter of one bf16 rounding -
-    a wrong index anywhere in a kernel gives O(1).  n = 64 is the bench batch."""
+    a wrong index anywhere in a kernel gives O(1).  n = 64 is the bench batch; 15 / 16 / 17 are the 16-row steps of fc_dw_b16, 33 /
+    65 the row-tile switches, 127 / 128 the last sizes of fc_small.hip and 129 the generic GEMM in its bf16 mode."""
+    _classifier_bf16_case(L, dev, n, False, own_decisions=n in (4, 64))
+
+
+@pytest.mark.parametrize("n", [17, 65, 129])
+def test_classifier_bf16_train_masks_through_c_abi(L, dev, cls_weights, n):
+    """The same in train mode with injected dropout masks (the backward then reads the drop regions and the mask bytes)."""
+    _classifier_bf16_case(L, dev, n, True)
+
+
+@pytest.mark.parametrize("before", [0, 1])
+def test_classifier_bf16_above_128_rows_keeps_the_threads_gemm_mode(L, dev, cls_weights, before):
+    """At n = 129 the bf16 classifier forward puts the generic GEMM in bf16 mode for its own products only: a plain umpr_gemm_f32
+    call behind it computes the fp32 product when the thread's switch was off before (1e-6 of the unrounded float64 product), and
+    the product of the bf16-rounded operands when it was on (1e-5, as test_gemm_bf16_operands; the two differ by ~3e-3)."""
     from umpr_amd.model import _ptr_array
-    g = torch.Generator().manual_seed(11 + n)
-    dims = [(25088, 4096), (4096, 4096), (4096, 1000)]
-    params = []
-    for fin, fout in dims:
-        params += [(torch.randn(fout, fin, generator=g) * (2.0 / fin) ** 0.5).to(dev),
-                   (torch.randn(fout, generator=g) * 0.1).to(dev)]
-    x = torch.rand(n, 25088, generator=g).to(dev)
-    gout = torch.randn(n, 1000, generator=g).to(dev)
-    # reference
-    ps = [p.clone().requires_grad_(True) for p in params]
-    xr = x.clone().requires_grad_(True)
-    h = torch.relu(_QLinear.apply(xr, ps[0], ps[1]))
-    h = torch.relu(_QLinear.apply(h, ps[2], ps[3]))
-    ref = _QLinear.apply(h, ps[4], ps[5])
-    ref.backward(gout)
-    # C ABI
-    arena = torch.empty(L.size("umpr_vgg16_cls_arena_bytes", n) // 4, device=dev, dtype=torch.float32)
-    arena[: n * 25088] = x.reshape(-1)
-    masks = torch.empty(2, n, 4096, device=dev, dtype=torch.uint8)
-    out = torch.empty(n, 1000, device=dev)
+    n = 129
+    g = torch.Generator().manual_seed(5)
+    params = _cls_weights(dev)
+    arena, _ = _guarded(dev, L.size("umpr_vgg16_cls_arena_bytes", n) // 4)
+    arena[: n * 25088] = torch.rand(n * 25088, generator=g).to(dev)
+    masks = torch.full((2 * n * 4096,), 0xFF, device=dev, dtype=torch.uint8)
+    out, _ = _guarded(dev, n * 1000)
     wsb = L.size("umpr_vgg16_fwd_ws_bytes", n)
-    ws = torch.empty(wsb // 4 + 1, device=dev)
+    ws, _ = _guarded(dev, wsb // 4, pooled="ws")
     keep, parr = _ptr_array([params[0]] * 26 + params)
-    L.call("umpr_vgg16_classifier_fwd_compact_bf16", parr, n, 0, 0, 0, arena, masks, out, ws, wsb, st())
-    h1 = torch.relu(_QLinear.apply(x, params[0], params[1]))
-    e1 = rel_l2(arena[n * 25088: n * 25088 + n * 4096].reshape(n, 4096).cpu(), h1.cpu())
-    e = rel_l2(out.cpu(), ref.detach().cpu())
-    log(f"classifier bf16 n{n}: fc1 relL2 {e1:.2e} out relL2 {e:.2e}")
-    assert torch.isfinite(out).all() and e1 <= 2e-5 and e <= 1e-3
-    grads = [torch.full_like(p, float("nan")) for p in params]
-    d_pool5 = torch.full((n, 25088), float("nan"), device=dev)
-    wsb2 = L.size("umpr_vgg16_classifier_bwd_ws_bytes", n)
-    ws2 = torch.empty(wsb2 // 4 + 1, device=dev)
-    keep_g, garr = _ptr_array([grads[0]] * 26 + grads)
-    L.call("umpr_vgg16_classifier_bwd_compact_bf16", parr, n, 0, arena, masks, gout, garr, d_pool5, ws2, wsb2, st())
+    A, B = torch.randn(70, 40, generator=g).to(dev), torch.randn(40, 50, generator=g).to(dev)
+    C = torch.full((70, 50), float("nan"), device=dev)
+    L.call("umpr_set_gemm_bf16", before)
+    try:
+        L.call("umpr_vgg16_classifier_fwd_compact_bf16", parr, n, 0, 0, 0, arena, masks, out, ws, wsb, st())
+        L.call("umpr_gemm_f32", A, 40, 0, B, 50, 0, C, 50, 70, 50, 40, None, 0, 0, 0, 1.0, None, 0, st())
+    finally:
+        L.call("umpr_set_gemm_bf16", 0)
     torch.cuda.synchronize()
-    bad = {}
-    for i, (gr, pr) in enumerate(zip(grads, ps)):
-        e = rel_l2(gr.cpu(), pr.grad.cpu())
-        log(f"classifier bf16 n{n}: d param {i} relL2 {e:.2e}")
-        if not (torch.isfinite(gr).all() and e <= 1e-3):
-            bad[i] = e
-    e = rel_l2(d_pool5.cpu(), xr.grad.cpu())
-    log(f"classifier bf16 n{n}: d pool5 relL2 {e:.2e}")
-    assert torch.isfinite(d_pool5).all() and e <= 1e-3 and not bad, (e, bad)
+    e_f32 = rel_l2(C.cpu(), (A.double() @ B.double()).cpu())
+    e_b16 = rel_l2(C.cpu(), (q(A).double() @ q(B).double()).cpu())
+    log(f"classifier bf16 n129, gemm mode {before} before: plain gemm behind it relL2 vs fp32 product {e_f32:.2e} vs rounded {e_b16:.2e}")
+    assert torch.isfinite(out).all()
+    assert (e_b16 <= 1e-5 and e_f32 > 1e-4) if before else (e_f32 <= 1e-6 and e_b16 > 1e-4), (e_f32, e_b16)
 
 
 def _vgg_pair(dev, seed):

@@ -126,11 +126,11 @@ def features_backward(images, convs, pools, conv_params, d_pool, block_sizes, mo
     return grads
 
 
-def classifier_backward(pool5, fc, drop, fc_params, d_out, masks=None, p=0.5, dtype=torch.float64):
+def classifier_backward(pool5, fc, drop, fc_params, d_out, masks=None, p=0.5, dtype=torch.float64, device="cpu"):
     """Backward of Linear-ReLU-Dropout-Linear-ReLU-Dropout-Linear.  pool5 [k][F]; fc: the two ReLU outputs; drop: their
     dropout outputs (read only with masks); fc_params [W1, b1, W2, b2, W3, b3]; masks: keep-masks [2][k][hidden] (0/1) or
-    None when no dropout ran.  Returns ([dW1, db1, dW2, db2, dW3, db3], gradient w.r.t. pool5)."""
-    cv = lambda t: t.detach().to("cpu", dtype)   # noqa: E731
+    None when no dropout ran.  Returns ([dW1, db1, dW2, db2, dW3, db3], gradient w.r.t. pool5), computed on `device`."""
+    cv = lambda t: t.detach().to(device, dtype)   # noqa: E731
     grads = [None] * 6
     g = cv(d_out)
     for j in (2, 1, 0):

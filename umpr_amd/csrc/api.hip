@@ -512,10 +512,19 @@ namespace {
 // classifier activations: pool5 input [n][25088], ReLU outputs of fc1 / fc2 and their dropout outputs ([n][4096] each)
 struct ClsActs { const float* pool5; float* fc[2]; float* drop[2]; };
 
+// Above 128 rows umpr_fc_small_ok fails and the classifier's products run on the generic GEMM: under the bf16 entry points they
+// must round their operands there too (before, they silently ran in fp32).  The host thread's own setting is restored.
+struct ClsB16Scope {
+  int prev;
+  explicit ClsB16Scope(int on) : prev(umpr_gemm_b16()) { if (on) umpr_gemm_set_b16(1); }
+  ~ClsB16Scope() { umpr_gemm_set_b16(prev); }
+};
+
 int classifier_fwd_impl(const float* const* params, int n, int train, int use_masks, uint64_t seed, const ClsActs& A,
                         uint8_t* masks, float* out, float* ws, size_t ws_bytes, hipStream_t s, int bf16 = 0) {
   // AdaptiveAvgPool2d(7) is the identity on the 7x7 map a 224x224 image produces
   const float* x = A.pool5;
+  ClsB16Scope b16_scope(bf16);
   for (int j = 0; j < 3; ++j) {
     float* y = j < 2 ? A.fc[j] : out;
     const int act = j < 2 ? UMPR_ACT_RELU : UMPR_ACT_NONE;
@@ -586,6 +595,7 @@ namespace {
 int classifier_bwd_impl(const float* const* params, int n, int train, const ClsActs& A, const uint8_t* masks,
                         const float* d_out, float* const* grads, float* d_pool5, float* ws, size_t ws_bytes, hipStream_t s,
                         int bf16 = 0) {
+  ClsB16Scope b16_scope(bf16);
   float* gA = ws;
   float* gB = ws + (size_t)n * 4096;
   float* scratch = gB + (size_t)n * 4096;
@@ -629,6 +639,7 @@ int classifier_bwd_impl(const float* const* params, int n, int train, const ClsA
 int umpr_vgg16_classifier_bwd(const float* const* params, int n, int train, const float* acts, const uint8_t* masks,
                               const float* d_out, float* const* grads, float* d_pool5, float* ws, size_t ws_bytes,
                               void* stream) {
+  UMPR_REQUIRE(n > 0 && params && acts && grads && d_out && d_pool5, "vgg16_classifier_bwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_full(const_cast<float*>(acts), n), masks, d_out, grads, d_pool5,
                              ws, ws_bytes, S(stream));
@@ -637,6 +648,7 @@ int umpr_vgg16_classifier_bwd(const float* const* params, int n, int train, cons
 int umpr_vgg16_classifier_bwd_compact(const float* const* params, int n, int train, const float* cls_arena,
                                       const uint8_t* masks, const float* d_out, float* const* grads, float* d_pool5,
                                       float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out && d_pool5, "vgg16_classifier_bwd_compact: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd_compact: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_compact(const_cast<float*>(cls_arena), n), masks, d_out, grads,
                              d_pool5, ws, ws_bytes, S(stream));
@@ -648,12 +660,14 @@ int umpr_vgg16_classifier_fwd_compact_bf16(const float* const* params, int n, in
                                            float* cls_arena, uint8_t* masks, float* out, float* ws, size_t ws_bytes,
                                            void* stream) {
   UMPR_REQUIRE(n > 0 && params && cls_arena && out, "vgg16_classifier_fwd_compact_bf16: bad arguments");
+  UMPR_REQUIRE(ws_bytes >= umpr_vgg16_fwd_ws_bytes(n), "vgg16_classifier_fwd_compact_bf16: workspace too small");
   return classifier_fwd_impl(params, n, train, use_masks, seed, cls_acts_compact(cls_arena, n), masks, out, ws, ws_bytes,
                              S(stream), 1);
 }
 int umpr_vgg16_classifier_bwd_compact_bf16(const float* const* params, int n, int train, const float* cls_arena,
                                            const uint8_t* masks, const float* d_out, float* const* grads, float* d_pool5,
                                            float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out && d_pool5, "vgg16_classifier_bwd_compact_bf16: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd_compact_bf16: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_compact(const_cast<float*>(cls_arena), n), masks, d_out, grads,
                              d_pool5, ws, ws_bytes, S(stream), 1);

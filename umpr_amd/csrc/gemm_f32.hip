@@ -247,6 +247,7 @@ void launch_tile(const GemmParams& p, bool ta, bool tb, dim3 grid, hipStream_t s
 // per host thread: products issued while it is set round their operands to bf16 (umpr_set_gemm_bf16, mixed-precision mode)
 static thread_local int t_gemm_b16 = 0;
 void umpr_gemm_set_b16(int on) { t_gemm_b16 = on; }
+int umpr_gemm_b16() { return t_gemm_b16; }
 
 int umpr_gemm(const UmprGemm& g, hipStream_t stream) {
   UMPR_REQUIRE(g.M > 0 && g.N > 0 && g.K >= 0, "gemm: bad shape M=%d N=%d K=%d", g.M, g.N, g.K);

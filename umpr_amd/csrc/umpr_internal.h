@@ -21,6 +21,7 @@ struct UmprGemm {
   int winB_L = 0, winB_D = 1, winB_pad = 0;
 };
 void umpr_gemm_set_b16(int on);
+int umpr_gemm_b16();             // the calling host thread's current setting
 int umpr_gemm(const UmprGemm& g, hipStream_t stream);
 
 // fc_small.hip - batch-sized fully connected layers (register-streaming fp32 MFMA, no LDS)
