@@ -1,8 +1,9 @@
-// Stand-alone reproducer for the run-to-run noise of text_ops.hip's first merge_bwd_dx_kernel ("A kernel that was not
-// reproducible").  The kernel under test (a copy of that kernel) runs on one stream with FIXED inputs, again and again, next to a
+// Stand-alone reproducer for the run-to-run noise of the first review-merge backward kernel, since retired from the library
+// ("A kernel that was not reproducible").  The kernel under test (dx_pipelined below, the only remaining copy of that
+// kernel) runs on one stream with FIXED inputs, again and again, next to a
 // co-runner on a second stream that keeps every CU busy; each result is compared bit for bit with the result of a run on the quiet
 // device.  Co-runners: none / a VALU loop / a bf16 MFMA loop / a streaming copy (memory pressure) / transposed LDS reads.
-// (tools/hazard_repro.py: the same with the LIBRARY's kernels as neighbours - only the bf16 weight gradient triggers it.)
+// (With the LIBRARY's kernels as neighbours only the bf16 weight gradient triggered it: profiles/r03_e_hazard_repro.txt.)
 //   hipcc --offload-arch=gfx950 -O3 -o tools/hazard_repro tools/hazard_repro.hip && tools/hazard_repro [launches]
 #include <hip/hip_runtime.h>
 #include <stdio.h>

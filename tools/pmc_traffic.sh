@@ -14,7 +14,7 @@ done
 python3 - <<'PY'
 import csv, glob, json, os, collections
 R = os.environ['GRAFT_REPO_ROOT']
-fam = lambda n: ('b16_conv_family' if any(k in n for k in ('conv_bf16_kernel', 'conv1_bf16_fwd'))
+fam = lambda n: ('b16_conv_family' if any(k in n for k in ('conv_bf16_m16_kernel', 'conv1_bf16_fwd'))
                  else 'igemm_family' if any(k in n for k in ('conv3x3_igemm', 'wino_', 'wino4_', 'pack_weights_kernel', 'conv3x3_fwd', 'conv3x3_dgrad'))
                  else 'wgrad_family' if ('wgrad' in n) else None)
 out = collections.defaultdict(lambda: collections.defaultdict(float))

@@ -13,13 +13,14 @@
 // reads ([plane][pixel] x 16 B: consecutive lanes = consecutive 16-B slots), the nine taps are an immediate offset on
 // the fragment address (zero VALU in the loop), and the epilogue's bf16 stores are whole 512-B runs per wave-instruction.
 //
-//   conv_bf16_kernel   forward and data gradient: D[cout][pixel] = sum_{tap,c} Wp[tap][cout][c] * X[pixel + off(tap)][c],
-//                      K-loop over (32-channel chunk, tap); weights for one step arrive 3 steps ahead in a 4-deep LDS ring
-//                      (counted vmcnt), the input patch of a chunk serves its 9 taps.  1-D tiles of consecutive flat
-//                      pixels on the narrow maps, 2-D tiles (smaller halo) on the 224 / 112 maps.
-//   wgrad_bf16_kernel  weight gradient: dW[tap][co][ci] = sum_P dY[P][co] * X[P + off(tap)][ci], K = pixels; both MFMA
-//                      operands are K-major in memory, so fragments come from ds_read_b64_tr_b16 (transposing LDS read);
-//                      9 accumulator tiles per wave, split-K over pixel segments into fp32 slabs + deterministic reduce.
+//   conv_bf16_m16_kernel   forward and data gradient: D[cout][pixel] = sum_{tap,c} Wp[tap][cout][c] * X[pixel + off(tap)][c],
+//                          K-loop over (32-channel chunk, tap); weights for one step arrive 3 steps ahead in a 4-deep LDS
+//                          ring (counted vmcnt), the input patch of a chunk serves its 9 taps.  1-D tiles of consecutive
+//                          flat pixels on the narrow maps, 2-D tiles (smaller halo) on the 224 / 112 maps.
+//   wgrad_bf16_m16_kernel  weight gradient: dW[tap][co][ci] = sum_P dY[P][co] * X[P + off(tap)][ci], K = pixels; both MFMA
+//                          operands are K-major in memory, so fragments come from ds_read_b64_tr_b16 (transposing LDS
+//                          read); 9 accumulator tiles per wave, split-K over pixel segments into fp32 slabs +
+//                          deterministic reduce.
 #include "umpr_common.h"
 #include "umpr_internal.h"
 #include <stdlib.h>
@@ -102,227 +103,7 @@ __device__ __forceinline__ void zero_guard_slice(const ConvB16Params& p, int ct,
 
 // W: map width.  TR > 0: 2-D tile of TR rows x TC real columns; TR == 0: 1-D tile of TC consecutive flat pixels.
 // BN output channels per workgroup; WP x WC waves (pixels x channels).
-// ABL (ablation builds for timing only, results wrong): 1 = no per-step vmcnt wait / barrier, 2 = fragments read once,
-// 3 = no DMA in the loop
-template <int W, int TR, int TC, int BN, int WP, int WC, int D = 3, int ABL = 0>
-__global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? 2 : 1)) void conv_bf16_kernel(ConvB16Params p) {
-  constexpr int NW = WP * WC, NT = 64 * NW;
-  constexpr bool TWO_D = TR > 0;
-  constexpr int BM = TWO_D ? TR * TC : TC;
-  constexpr int RW = W + 1;
-  constexpr int LP = TC + 2;                      // 2-D patch row pitch (pixels)
-  constexpr int TS = TWO_D ? LP : RW;             // LDS pixels between the rows a tap's dy selects
-  constexpr int PATCH = TWO_D ? (TR + 2) * LP : BM + 2 * RW + 2;
-  constexpr int PPP = (PATCH + 63) / 64;          // DMA pieces per plane
-  constexpr int PPX = PPP * 64;                   // LDS pixels per plane
-  constexpr int PPC = 4 * PPP;                    // patch pieces per 32-channel chunk
-  constexpr int PPW = (PPC + NW - 1) / NW;        // ... per wave (surplus slots repeat a piece)
-  constexpr int WPS = BN / 16;                    // weight pieces per step (BN x 64 B)
-  constexpr int WPW = (WPS + NW - 1) / NW;
-  constexpr int NB = D + 1;                       // weights arrive D steps ahead in a ring of NB stages
-  constexpr int TPW = BM / WP / 32, TCW = BN / WC / 32;
-  constexpr int WB = BN * 32, PB = 4 * PPX * 8;   // elements per weight stage / patch stage
-  static_assert(BM % (32 * WP) == 0 && BN % (32 * WC) == 0 && (!TWO_D || (W % TC == 0 && TC % 16 == 0)), "tile shape");
-  __shared__ __attribute__((aligned(1024))) bf16_t smem[NB * WB + 2 * PB];
-  bf16_t* const Wb = smem;
-  bf16_t* const Pb = smem + NB * WB;
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wpx = wave / WC, wco = wave % WC;
-  const int r = lane & 31, h = lane >> 5;
-
-  // XCD-aware order: workgroups b, b+8, ... share an XCD.  The weights of one output-channel tile (up to 2.4 MB) are what
-  // every pixel tile re-reads, so an XCD works on ONE channel tile where the tile count divides 8.
-  const int xcd = blockIdx.x & 7;
-  const long slot = blockIdx.x >> 3;
-  int ct; long pt;
-  if (p.nct <= 8 && (8 % p.nct) == 0) { const int g = 8 / p.nct; ct = xcd / g; pt = slot * g + (xcd % g); }
-  else { ct = (int)(slot % p.nct); pt = (slot / p.nct) * 8 + xcd; }
-  if (pt >= p.ntp) return;
-
-  long Q0; int ctile = 0;
-  if (TWO_D) {
-    constexpr int CT = W / TC;
-    const long band = pt / CT;
-    ctile = (int)(pt - band * CT);
-    Q0 = band * TR * RW + 1 + ctile * TC;
-  } else {
-    Q0 = pt * BM;
-  }
-
-  // ---- DMA plan of this wave
-  const int nchunks = p.C / 32;
-  const bf16_t* psrc[PPW]; unsigned pdst[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; ++i) {
-    const int q = (wave + NW * i) % PPC;
-    const int pl = q / PPP, pp = q - pl * PPP;
-    int u = pp * 64 + lane;
-    long gp;
-    if (TWO_D) {
-      if (u > PATCH - 1) u = PATCH - 1;
-      const int a = u / LP, b = u - a * LP;
-      gp = Q0 + (long)(a - 1) * RW + (b - 1);
-    } else {
-      gp = Q0 - RW - 1 + u;
-    }
-    psrc[i] = p.x + ((long)pl * p.xps + gp) * 8;
-    pdst[i] = lds_addr(Pb) + (unsigned)(pl * PPX + pp * 64) * 16u;
-  }
-  const bf16_t* wsrc[WPW]; unsigned wdst[WPW];
-  const bf16_t* wtile = p.wp + (long)ct * nchunks * 9 * WB;
-#pragma unroll
-  for (int i = 0; i < WPW; ++i) {
-    const int q = (wave + NW * i) % WPS;
-    wsrc[i] = wtile + q * 512 + lane * 8;
-    wdst[i] = lds_addr(Wb) + (unsigned)q * 1024u;
-  }
-  const long chunk_stride = 4 * p.xps * 8;        // elements between 32-channel chunks of the input
-  const int S = nchunks * 9;
-  auto issue_w = [&](int s) {                     // stage of step s -> ring slot s % NB (steps past the end repeat the last)
-    const int sc = s < S ? s : S - 1;
-    const unsigned slot_off = (unsigned)(s % NB) * (WB * 2u);
-#pragma unroll
-    for (int i = 0; i < WPW; ++i) glds16(wsrc[i] + (long)sc * WB, wdst[i] + slot_off);
-  };
-  auto issue_p = [&](int c) {                     // patch of chunk c -> buffer c & 1
-    const int cc = c < nchunks ? c : nchunks - 1;
-    const unsigned buf_off = (unsigned)(c & 1) * (PB * 2u);
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) glds16(psrc[i] + cc * chunk_stride, pdst[i] + buf_off);
-  };
-
-  // ---- fragment addresses (bytes inside a stage)
-  unsigned pbo[TPW];
-#pragma unroll
-  for (int j = 0; j < TPW; ++j) {
-    const int k = wpx * (BM / WP) + j * 32 + r;
-    const int idx = TWO_D ? (k / TC + 1) * LP + (k % TC) + 1 : k + RW + 1;
-    pbo[j] = (unsigned)(h * PPX + idx) * 16u;
-  }
-  const unsigned wbo = (unsigned)(h * BN + wco * (BN / WC) + r) * 16u;
-
-  // accumulators start at the bias: D[cout][pixel], register x of a lane is cout (x&3) + 8*(x>>2) + 4*h of the tile
-  f32x16 acc[TCW][TPW];
-#pragma unroll
-  for (int i = 0; i < TCW; ++i) {
-    f32x16 b0;
-#pragma unroll
-    for (int x = 0; x < 16; ++x)
-      b0[x] = p.bias ? p.bias[ct * BN + wco * (BN / WC) + i * 32 + (x & 3) + 8 * (x >> 2) + 4 * h] : 0.f;
-#pragma unroll
-    for (int j = 0; j < TPW; ++j) acc[i][j] = b0;
-  }
-
-  issue_p(0);
-#pragma unroll
-  for (int d = 0; d < D; ++d) issue_w(d);
-  wait_vm<(D - 1) * WPW>();
-  __syncthreads();
-
-  for (int c = 0; c < nchunks; ++c) {
-    const char* pb = reinterpret_cast<const char*>(Pb) + (c & 1) * (PB * 2);
-#pragma unroll
-    for (int t = 0; t < 9; ++t) {
-      const int s = c * 9 + t;
-      if (ABL != 3) {
-        issue_w(s + D);
-        if (t == 0) issue_p(c + 1);
-      }
-      const char* wb = reinterpret_cast<const char*>(Wb) + (s % NB) * (WB * 2);
-      constexpr int dummy = 0; (void)dummy;
-      const int toff = ((t / 3) - 1) * TS + (t % 3) - 1;
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        bf16x8 a[TCW], b[TPW];
-        if (ABL == 2) {
-#pragma unroll
-          for (int i = 0; i < TCW; ++i) { a[i] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(Wb) + wbo + i * 512); asm volatile("" : "+v"(a[i])); }
-#pragma unroll
-          for (int j = 0; j < TPW; ++j) { b[j] = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const char*>(Pb) + pbo[j]); asm volatile("" : "+v"(b[j])); }
-        } else {
-#pragma unroll
-        for (int i = 0; i < TCW; ++i) a[i] = *reinterpret_cast<const bf16x8*>(wb + wbo + (ks * 2 * BN + i * 32) * 16);
-#pragma unroll
-        for (int j = 0; j < TPW; ++j) b[j] = *reinterpret_cast<const bf16x8*>(pb + pbo[j] + (ks * 2 * PPX + toff) * 16);
-        }
-#pragma unroll
-        for (int i = 0; i < TCW; ++i)
-#pragma unroll
-          for (int j = 0; j < TPW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-      }
-      // stage s+1 (and, from the fourth step of a chunk on, the next chunk's patch) must have landed; the younger DMAs
-      // (D-1 weight stages, plus the patch while it may still fly) stay in flight across the barrier
-      if (ABL != 1 && ABL != 3) {
-        if (t < D) wait_vm<(D - 1) * WPW + PPW>(); else wait_vm<(D - 1) * WPW>();
-      }
-      if (ABL != 1) __syncthreads();
-    }
-  }
-  wait_vm<0>();
-
-  // ---- epilogue: ReLU / mask, zero at pads, bf16, 8-B stores that pair up to whole 16-B pixels across the half-waves
-#pragma unroll
-  for (int j = 0; j < TPW; ++j) {
-    const int k = wpx * (BM / WP) + j * 32 + r;
-    const long P = TWO_D ? Q0 + (long)(k / TC) * RW + (k % TC) : Q0 + k;
-    if (P >= p.ptot) continue;
-    const bool real = pf_real<RW>(P, p.H);
-    // all mask words of this pixel first (independent loads in flight together), then the stores: loaded one by one
-    // between the stores, each would wait out a full memory round trip (the compiler cannot move a load above a store
-    // that may alias it) - that cost the 64-channel data gradient 250 us
-    bf16x4 mk[TCW][4];
-    if (p.mask) {
-#pragma unroll
-      for (int i = 0; i < TCW; ++i)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-          const int co = ct * BN + wco * (BN / WC) + i * 32 + 8 * g + 4 * h;
-          mk[i][g] = *reinterpret_cast<const bf16x4*>(p.mask + ((long)(co >> 3) * p.mps + P) * 8 + (co & 7));
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < TCW; ++i) {
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const int co = ct * BN + wco * (BN / WC) + i * 32 + 8 * g + 4 * h;
-        const long o = ((long)(co >> 3) * p.yps + P) * 8 + (co & 7);
-        float v[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * g + e];
-        if (p.relu) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        }
-        if (p.mask) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = (float)mk[i][g][e] > 0.f ? v[e] : 0.f;
-        }
-        bf16x4 out;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) out[e] = (bf16_t)(real ? v[e] : 0.f);
-        *reinterpret_cast<bf16x4*>(p.y + o) = out;
-      }
-    }
-  }
-  zero_guard_slice<BN, NT>(p, ct, pt, tid);
-  if (TWO_D && ctile == 0) {   // column 0 (the zero pad) of this tile's rows: no tile computes it
-    const long row0 = Q0 / RW;
-    for (int e = tid; e < TR * (BN / 8); e += NT) {
-      const int i = e % TR, cb = e / TR;
-      const long P = (row0 + i) * RW;
-      if (P < p.ptot) {
-        bf16x8 z;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) z[q] = (bf16_t)0.f;
-        *reinterpret_cast<bf16x8*>(p.y + ((long)(ct * (BN / 8) + cb) * p.yps + P) * 8) = z;
-      }
-    }
-  }
-}
-
-// The same kernel on v_mfma_f32_16x16x32_bf16: one MFMA covers the whole 32-channel chunk of a tap for a 16 px x 16 ch tile
+// On v_mfma_f32_16x16x32_bf16: one MFMA covers the whole 32-channel chunk of a tap for a 16 px x 16 ch tile
 // (lane group l >> 4 reads plane l >> 4).  Same LDS traffic and MFMA cycles per step as the 32x32x16 form; the guide
 // measures a higher sustained clock for this shape under load (MI355X_MICROARCH.md, DVFS give-back item 7).
 // PP (8-wave workgroups only): ping-pong schedule.  The two waves a SIMD holds (w and w + 4) alternate a LOAD phase (DMA
@@ -330,9 +111,9 @@ __global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? 2 : 1)) void conv_bf1
 // workgroup running one barrier behind the first, so one wave of every SIMD multiplies while its partner reads
 // (MI355X_MICROARCH.md, "Two waves per SIMD").  Ring safety: a stage is overwritten one full step after its last read and
 // every wave's reads are drained (lgkmcnt(0)) before the barrier that ends its load phase.
-template <int W, int TR, int TC, int BN, int WP, int WC, int D = 3, bool PP = false>
-__global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? (TR == 4 ? 3 : 2) : 1)) void conv_bf16_m16_kernel(ConvB16Params p) {
-  constexpr int ABL = 0;
+template <int W, int TR, int TC, int BN, int WP, int WC, bool PP>
+__global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? 2 : 1)) void conv_bf16_m16_kernel(ConvB16Params p) {
+  constexpr int D = 3;                            // weight stages in flight ahead of the step that reads them
   static_assert(!PP || WP * WC == 8, "ping-pong needs two waves per SIMD in one workgroup");
   constexpr int NW = WP * WC, NT = 64 * NW;
   constexpr bool TWO_D = TR > 0;
@@ -491,10 +272,8 @@ __global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? (TR == 4 ? 3 : 2) : 1
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int s = c * 9 + t;
-      if (ABL != 3) {
-        issue_w(s + D);
-        if (t == 0) issue_p(c + 1);
-      }
+      issue_w(s + D);
+      if (t == 0) issue_p(c + 1);
       const char* wb = reinterpret_cast<const char*>(Wb) + (s % NB) * (WB * 2);
       constexpr int dummy = 0; (void)dummy;
       const int toff = ((t / 3) - 1) * TS + (t % 3) - 1;
@@ -511,10 +290,8 @@ __global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? (TR == 4 ? 3 : 2) : 1
       }
       // stage s+1 (and, from the fourth step of a chunk on, the next chunk's patch) must have landed; the younger DMAs
       // (D-1 weight stages, plus the patch while it may still fly) stay in flight across the barrier
-      if (ABL != 1 && ABL != 3) {
-        if (t < D) wait_vm<(D - 1) * WPW + PPW>(); else wait_vm<(D - 1) * WPW>();
-      }
-      if (ABL != 1) __syncthreads();
+      if (t < D) wait_vm<(D - 1) * WPW + PPW>(); else wait_vm<(D - 1) * WPW>();
+      __syncthreads();
     }
   }
   wait_vm<0>();
@@ -1336,34 +1113,20 @@ inline int grid_for(long n, int cap) {
   return (int)(b < 1 ? 1 : b);
 }
 
-// 1 (default): v_mfma_f32_16x16x32_bf16 form, 5-10 % faster per layer on MI355X (profiles/r02_k_m16_ab.txt); 0: 32x32x16 form
-const int g_b16_m16 = umpr_env_int("UMPR_B16_M16", 1);
-
-// UMPR_B16_PP: ping-pong schedule in the 8-wave forward / dgrad kernels.  2 (default): where it measured faster - the
-// 256-channel tiles (wave tile 128 x 64, 32 MFMAs per phase: +8-10 %, 512->512@28 1158 TF) and the 1-D 128-channel tiles
-// (+3-5 %); the 2-D 128-channel tiles of the 112 x 112 maps (16 MFMAs per phase) lose 15 % to the second barrier.
-// 1: everywhere, 0: nowhere (profiles/r02_u_pp_ab.txt).
-const int g_b16_pp = umpr_env_int("UMPR_B16_PP", 2);
-
-template <int W, int TR, int TC, int BN, int WP, int WC, int D = 3, int ABL = 0>
+// Ping-pong schedule in the 8-wave forward / dgrad kernels where it measured faster - the 256-channel tiles (wave tile
+// 128 x 64, 32 MFMAs per phase: +8-10 %, 512->512@28 1158 TF) and the 1-D 128-channel tiles (+3-5 %); the 2-D 128-channel
+// tiles of the 112 x 112 maps (16 MFMAs per phase) lose 15 % to the second barrier (profiles/r02_u_pp_ab.txt).
+template <int W, int TR, int TC, int BN, int WP, int WC>
 void launch_conv(ConvB16Params p, hipStream_t s) {
   constexpr int BM = TR > 0 ? TR * TC : TC;
+  constexpr bool PP = WP * WC == 8 && (BN == 256 || TR == 0);
   if (TR > 0) p.ntp = ((p.rows + TR - 1) / TR) * (W / TC);
   else p.ntp = (p.ptot + BM - 1) / BM;
   p.nct = p.M / BN;
   long blocks;
   if (p.nct <= 8 && (8 % p.nct) == 0) { const int g = 8 / p.nct; blocks = ((p.ntp + g - 1) / g) * 8; }
   else blocks = ((p.ntp + 7) / 8) * 8 * p.nct;
-  if (g_b16_m16 && ABL == 0) {
-    if constexpr (WP * WC == 8) {
-      if (g_b16_pp == 1 || (g_b16_pp == 2 && (BN == 256 || TR == 0))) {
-        conv_bf16_m16_kernel<W, TR, TC, BN, WP, WC, D, true><<<dim3((unsigned)blocks), 64 * WP * WC, 0, s>>>(p);
-        return;
-      }
-    }
-    conv_bf16_m16_kernel<W, TR, TC, BN, WP, WC, D><<<dim3((unsigned)blocks), 64 * WP * WC, 0, s>>>(p);
-  }
-  else conv_bf16_kernel<W, TR, TC, BN, WP, WC, D, ABL><<<dim3((unsigned)blocks), 64 * WP * WC, 0, s>>>(p);
+  conv_bf16_m16_kernel<W, TR, TC, BN, WP, WC, PP><<<dim3((unsigned)blocks), 64 * WP * WC, 0, s>>>(p);
 }
 
 // tile choice per map width and output-channel count:
@@ -1373,40 +1136,16 @@ void launch_conv(ConvB16Params p, hipStream_t s) {
 //                  (K is only 576 deep there) hides behind the other's main loop
 //   14 x 14 maps : 57 pixel tiles only - 128-channel tiles (4 x 57 = 228 workgroups) fill the 256 CUs, 256-channel
 //                  tiles (114) would leave half of them idle
-// UMPR_B16_CFG (A/B runs): tile for the layers with >= 256 output channels.  0: 256 px x 256 ch, 8 waves (one workgroup
-// per CU); 1: 256 x 128, 4 waves of 128 x 64 (80 KB of LDS: two workgroups per CU, their barriers interleave);
-// 2: 512 x 128, 8 waves of 128 x 64
-const int g_b16_cfg = umpr_env_int("UMPR_B16_CFG", 0);
-
-// UMPR_B16_T64=1: the 64-channel output tiles of the 224 / 112 maps take 512 pixels (8 waves, one workgroup per CU) instead of
-// 256 (4 waves, two per CU): half the weight re-reads from L2 per output pixel (A/B)
-const int g_b16_t64 = umpr_env_int("UMPR_B16_T64", 0);
-// UMPR_B16_T3=1: conv1_2 (64 -> 64 at 224x224, K = 576: a workgroup lives for 18 steps) on 4 x 32 = 128-pixel tiles - 48 KB of
-// LDS and <= 170 registers, THREE workgroups per CU, so that two others' main loops cover one's prologue / epilogue (A/B)
-const int g_b16_t3 = umpr_env_int("UMPR_B16_T3", 0);
-
 int conv_bn_for(int M, int W) {
-  if (M % 256 == 0 && W != 14 && g_b16_cfg == 0) return 256;
+  if (M % 256 == 0 && W != 14) return 256;
   return M % 128 == 0 ? 128 : 64;
 }
 
-template <int W, int TR, int TC, int TR2, int TC2>
+template <int W, int TR, int TC>
 int dispatch_conv_w(const ConvB16Params& p, hipStream_t s) {
   const int BN = conv_bn_for(p.M, W);
-  static const int deep = umpr_env_int("UMPR_B16_D", 3);
-  static const int abl = umpr_env_int("UMPR_B16_ABL", 0);
-  if (BN == 256 && W == 28 && abl == 1) launch_conv<W, TR, TC, 256, 2, 4, 3, 1>(p, s);
-  else if (BN == 256 && W == 28 && abl == 2) launch_conv<W, TR, TC, 256, 2, 4, 3, 2>(p, s);
-  else if (BN == 256 && W == 28 && abl == 3) launch_conv<W, TR, TC, 256, 2, 4, 3, 3>(p, s);
-  else if (BN == 256 && deep == 5) launch_conv<W, TR, TC, 256, 2, 4, 5>(p, s);
-  else if (BN == 256) launch_conv<W, TR, TC, 256, 2, 4>(p, s);
-  else if (BN == 128 && p.M % 256 == 0 && W != 14 && g_b16_cfg == 1) launch_conv<W, TR, TC, 128, 2, 2>(p, s);
-  else if (BN == 128 && p.M % 256 == 0 && W != 14 && g_b16_cfg == 2) launch_conv<W, TR2, TC2, 128, 4, 2>(p, s);
+  if (BN == 256) launch_conv<W, TR, TC, 256, 2, 4>(p, s);
   else if (BN == 128) launch_conv<W, TR, TC, 128, 4, 2>(p, s);
-  else if (p.M % 64 == 0 && g_b16_t64 && TR2 > 0) launch_conv<W, TR2, TC2, 64, 8, 1>(p, s);   // 512-pixel tiles, 8 waves
-  else if (p.M % 64 == 0 && W == 224 && g_b16_t3) {   // 128-pixel tiles, three workgroups per CU
-    if constexpr (W == 224) launch_conv<224, 4, 32, 64, 4, 1>(p, s);
-  }
   else if (p.M % 64 == 0) launch_conv<W, TR, TC, 64, 4, 1>(p, s);
   else return -1;
   return 0;
@@ -1495,11 +1234,11 @@ int umpr_conv_bf16_run(const void* x, const float* w, int transposed, const floa
   UmprProfScope prof(transposed ? UMPR_K_B16_DGRAD : UMPR_K_B16_FWD, 2.0 * (double)g.ptot * M * C * 9, s);
   int rc;
   switch (g.W) {
-    case 224: rc = dispatch_conv_w<224, 8, 32, 16, 32>(p, s); break;
-    case 112: rc = dispatch_conv_w<112, 16, 16, 32, 16>(p, s); break;
-    case 56: rc = dispatch_conv_w<56, 0, 256, 0, 512>(p, s); break;
-    case 28: rc = dispatch_conv_w<28, 0, 256, 0, 512>(p, s); break;
-    default: rc = dispatch_conv_w<14, 0, 256, 0, 512>(p, s); break;
+    case 224: rc = dispatch_conv_w<224, 8, 32>(p, s); break;
+    case 112: rc = dispatch_conv_w<112, 16, 16>(p, s); break;
+    case 56: rc = dispatch_conv_w<56, 0, 256>(p, s); break;
+    case 28: rc = dispatch_conv_w<28, 0, 256>(p, s); break;
+    default: rc = dispatch_conv_w<14, 0, 256>(p, s); break;
   }
   UMPR_REQUIRE(rc == 0, "conv_bf16: unsupported channel count %d", M);
   UMPR_LAUNCH_CHECK("conv_bf16");

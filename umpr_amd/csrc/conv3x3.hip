@@ -1000,8 +1000,12 @@ __global__ void maxpool2_bwd_relu_kernel(const float* __restrict__ x, const floa
 }  // namespace
 
 // ---- internal host entry points ------------------------------------------------------------------------------
-static bool g_conv_no_wino = false;  // UMPR_CONV_WINO=0 keeps the deep layers on the direct kernel (A/B runs)
-static int g_conv_bn = 0;  // UMPR_CONV_BN: 0 auto (128x128 bulk + 128x64 tail), 128 or 64 force one tile shape (A/B runs)
+// UMPR_CONV_WINO=0 keeps the deep layers on the direct kernel (A/B runs)
+static bool conv_no_wino() { static const bool v = !umpr_env_on("UMPR_CONV_WINO"); return v; }
+// UMPR_CONV_BN: 0 auto (128x128 bulk + 128x64 tail), 128 or 64 force one tile shape (A/B runs)
+static int conv_bn() { static const int v = umpr_env_int("UMPR_CONV_BN", 0); return v; }
+// UMPR_CONV_V1=1 selects the generic gather kernel (A/B runs)
+static bool conv_force_v1() { static const bool v = umpr_env_int("UMPR_CONV_V1", 0) == 1; return v; }
 // ---- first layer (Cin <= 3): no LDS, no barriers.  K = 27 is too short for the staged kernels (they pad it to a
 // 144-deep stage and become MFMA-bound on zeros); here every wave keeps its weight fragments in registers for the
 // whole launch and walks over 32-pixel tiles: 14 gathered loads per lane (image planes stay in L2), 14 MFMA k-steps
@@ -1069,8 +1073,6 @@ __global__ __launch_bounds__(256) void conv3x3_fwd_c3_kernel(ConvParams p) {
   }
 }
 
-static bool g_conv_force_v1 = false;  // UMPR_CONV_V1=1 selects the generic gather kernel (A/B runs)
-static struct ConvEnvInit { ConvEnvInit() { const char* e = getenv("UMPR_CONV_V1"); g_conv_force_v1 = e && e[0] == '1'; const char* q = getenv("UMPR_CONV_BN"); g_conv_bn = q ? atoi(q) : 0; const char* wq = getenv("UMPR_CONV_WINO"); g_conv_no_wino = wq && wq[0] == '0'; } } g_conv_env_init;
 static bool wino_layer(int H, int W) { return H == W && (W == 56 || W == 28 || W == 14); }
 // 112x112 maps with >= 128 channels on both sides (conv2_2): Winograd in backward only, and only on the F(4x4,3x3) tile -
 // with F(2x2,3x3) the 4x activation-sized transform traffic ate the gain (+1 %); on the larger tile the data gradient and the
@@ -1104,11 +1106,11 @@ size_t umpr_conv3x3_pack_floats(int N, int Cin, int Cout, int H, int W) {
   const size_t c = (size_t)Cin * Cout * 9;                               // plain flip-transpose (generic kernel)
   size_t m = a > b ? a : b;
   if (c > m) m = c;
-  if (wino_bwd_layer(Cin, Cout, H, W) && !g_conv_no_wino) {
+  if (wino_bwd_layer(Cin, Cout, H, W) && !conv_no_wino()) {
     const size_t f = umpr_wino_ws_floats(N, Cin, Cout, H, W, 0), t = umpr_wino_ws_floats(N, Cout, Cin, H, W, 1);
     if (f > m) m = f;
     if (t > m) m = t;
-  } else if (wino_fwd_c21_possible(Cin, Cout, H, W) && !g_conv_no_wino) {
+  } else if (wino_fwd_c21_possible(Cin, Cout, H, W) && !conv_no_wino()) {
     const size_t f = umpr_wino_ws_floats(N, Cin, Cout, H, W, 0);
     if (f > m) m = f;
   }
@@ -1123,7 +1125,7 @@ static bool fwd_wide() {
 // does a TRAINING forward of this layer take the Winograd path (given the scratch umpr_conv3x3_pack_floats asks for)?  The VGG
 // forward keeps the transformed input of such layers for the weight gradient (umpr_wino_v_floats).
 bool umpr_conv3x3_fwd_is_wino(int Cin, int Cout, int H, int W) {
-  return (fwd_wide() ? wino_bwd_layer(Cin, Cout, H, W) || wino_fwd_c21(Cin, Cout, H, W, false) : wino_layer(H, W)) && !g_conv_no_wino && !g_conv_force_v1 && Cin >= 32;
+  return (fwd_wide() ? wino_bwd_layer(Cin, Cout, H, W) || wino_fwd_c21(Cin, Cout, H, W, false) : wino_layer(H, W)) && !conv_no_wino() && !conv_force_v1() && Cin >= 32;
 }
 
 // Forward (transposed = 0):  y[N][Cout] = relu?(conv(x[N][Cin], w) + bias)
@@ -1138,21 +1140,21 @@ int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float
   const long NP = (long)N * H * W;
   // in inference the forward pass takes what the backward pass takes (conv2_2 on the 4x4 tile as well)
   const bool wide = transposed || umpr_wino_inference() || fwd_wide();
-  if ((wide ? wino_bwd_layer(C, M, H, W) || (!transposed && wino_fwd_c21(C, M, H, W, umpr_wino_inference() != 0)) : wino_layer(H, W)) && !g_conv_no_wino && !g_conv_force_v1 && wpack && C >= 32 &&
+  if ((wide ? wino_bwd_layer(C, M, H, W) || (!transposed && wino_fwd_c21(C, M, H, W, umpr_wino_inference() != 0)) : wino_layer(H, W)) && !conv_no_wino() && !conv_force_v1() && wpack && C >= 32 &&
       wpack_floats >= umpr_wino_ws_floats(N, C, M, H, W, transposed)) {
     // Winograd (F(2x2,3x3) forward, F(4x4,3x3) data gradient): 2.25x / 4x fewer MFMA FLOPs; timed under the same family with
     // the direct conv's FLOP count
     UmprProfScope prof(transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
     return umpr_wino_conv3x3(x, w, transposed, bias, mask, y, N, Cin, Cout, H, W, relu, wpack, wpack_floats, s);
   }
-  if (!transposed && Cin <= 3 && Cout == 64 && !mask && !g_conv_force_v1) {
+  if (!transposed && Cin <= 3 && Cout == 64 && !mask && !conv_force_v1()) {
     ConvParams p{x, w, bias, nullptr, y, N, Cin, H, W, Cout, relu, 0, NP};
     UmprProfScope prof(UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
     conv3x3_fwd_c3_kernel<2><<<2048, 256, 0, s>>>(p);
     UMPR_LAUNCH_CHECK("conv3x3_fwd_c3");
     return 0;
   }
-  const bool v2 = H == W && !g_conv_force_v1 && wpack && (W == 224 || W == 112 || W == 56 || W == 28 || W == 14);
+  const bool v2 = H == W && !conv_force_v1() && wpack && (W == 224 || W == 112 || W == 56 || W == 28 || W == 14);
   if (v2) {
     const long total = (long)M * ((C + V2_CC - 1) / V2_CC) * V2_KC;
     UMPR_REQUIRE(wpack_floats >= (size_t)total, "conv3x3: weight scratch too small");
@@ -1162,11 +1164,11 @@ int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float
     UMPR_LAUNCH_CHECK("pack_weights");
     ConvParams p{x, wpack, bias, mask, y, N, C, H, W, M, relu, 0, NP};
     UmprProfScope prof(transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
-    if (W == 224) launch_v2<224>(p, g_conv_bn, s);
-    else if (W == 112) launch_v2<112>(p, g_conv_bn, s);
-    else if (W == 56) launch_v2<56>(p, g_conv_bn, s);
-    else if (W == 28) launch_v2<28>(p, g_conv_bn, s);
-    else launch_v2<14>(p, g_conv_bn, s);
+    if (W == 224) launch_v2<224>(p, conv_bn(), s);
+    else if (W == 112) launch_v2<112>(p, conv_bn(), s);
+    else if (W == 56) launch_v2<56>(p, conv_bn(), s);
+    else if (W == 28) launch_v2<28>(p, conv_bn(), s);
+    else launch_v2<14>(p, conv_bn(), s);
     UMPR_LAUNCH_CHECK("conv3x3_igemm_v2");
     return 0;
   }
@@ -1215,7 +1217,7 @@ static const bool g_wgrad_wino = umpr_env_on("UMPR_WGRAD_WINO");
 static bool wgrad_wino_layer(int Cin, int Cout, int H, int W) {
   // conv2_1 (64 -> 128 at 112x112) as well: the weight-gradient GEMM has a 64-wide input-channel tile
   const bool c21 = wino_112() && H == 112 && W == 112 && Cin >= 64 && Cout >= 128;
-  return g_wgrad_wino && !g_conv_force_v1 && (wino_bwd_layer(Cin, Cout, H, W) || c21) && Cin >= 32 && Cout >= 32;
+  return g_wgrad_wino && !conv_force_v1() && (wino_bwd_layer(Cin, Cout, H, W) || c21) && Cin >= 32 && Cout >= 32;
 }
 
 size_t umpr_conv3x3_wgrad_ws_bytes(int N, int Cin, int Cout, int H, int W) {
@@ -1257,7 +1259,7 @@ int umpr_conv3x3_wgrad(const float* gz, const float* x, float* dw, float* db, in
   dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), splits);
   {
     UmprProfScope prof(UMPR_K_CONV_WGRAD, 2.0 * N * H * W * Cout * Cin * 9, s);
-    if (g_conv_force_v1) conv3x3_wgrad_kernel<<<grid, 256, 0, s>>>(p);
+    if (conv_force_v1()) conv3x3_wgrad_kernel<<<grid, 256, 0, s>>>(p);
     else if (Cin <= 3 && p.R == 2 && p.CW == 16) conv3x3_wgrad_c3_kernel<2, 16><<<grid, 256, 0, s>>>(p);
     else if (p.R == 2 && p.CW == 16) conv3x3_wgrad_v2_kernel<2, 16><<<grid, 256, 0, s>>>(p);
     else if (p.R == 4 && p.CW == 8) conv3x3_wgrad_v2_kernel<4, 8><<<grid, 256, 0, s>>>(p);

@@ -720,60 +720,9 @@ __global__ __launch_bounds__(256) void merge_fwd_kernel(const float* __restrict_
   }
 }
 
-// d_repr_s[m][k] = sum_n dpre[m][n] W_s[n][k],  dpre = d_out (1 - out^2).  grid (cdiv(B, 4), 2 sides); thread: float4 column
-// k4 = tid & 63, reduction quarter nq = tid >> 6 (32 n), four rows m; the quarters meet in LDS.
-// NOT the default (UMPR_MERGE_DX=1 selects it): next to the bf16 weight-gradient kernels of the VGG backward (another stream) this
-// kernel returned, in about one launch of three, sums that were off by a few per cent in the columns of lanes 48..63 and there in
-// the .x / .z components only - with bit-identical inputs, and correct when run again on the quiescent device
-// (tools/check_reproducible.py, round 3).  The ISA is clean (barriers, waitcnts, LDS extents checked); a variant that keeps the
-// quarters in one wave and joins them by shuffles (no LDS exchange) showed the same, a plain one-row loop with dpre in LDS did not:
-// what the failing variants share is hipcc's software-pipelined 8-deep loop (global_load_dwordx4 into registers a v_pk_fma_f32 has
-// just read).  Unexplained beyond that; variant 2 below is what runs (+4 us per UMPR-R step).
-__global__ __launch_bounds__(256) void merge_bwd_dx_kernel(const float* __restrict__ out, const float* __restrict__ d_out,
-                                                           const float* __restrict__ Wu, const float* __restrict__ Wi, int B,
-                                                           float* __restrict__ dru, float* __restrict__ dri) {
-  __shared__ float dp[4][MD];
-  __shared__ float4 part[3][4][64];
-  const int tid = threadIdx.x, k4 = tid & 63, nq = tid >> 6, m0 = blockIdx.x * 4;
-  const float* W = blockIdx.y ? Wi : Wu;
-  float* dr = blockIdx.y ? dri : dru;
-  for (int e = tid; e < 4 * MD; e += 256) {
-    const int m = m0 + e / MD, n = e % MD;
-    float v = 0.f;
-    if (m < B) { const float y = out[(long)m * MD + n]; v = d_out[(long)m * MD + n] * (1.f - y * y); }
-    dp[e / MD][n] = v;
-  }
-  __syncthreads();
-  float4 acc[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) acc[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-  const float4* wp = reinterpret_cast<const float4*>(W + (long)(nq * 32) * MK) + k4;
-#pragma unroll 8
-  for (int i = 0; i < 32; ++i) {
-    const float4 w = wp[(long)i * (MK / 4)];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float d = dp[r][nq * 32 + i];
-      acc[r].x += d * w.x; acc[r].y += d * w.y; acc[r].z += d * w.z; acc[r].w += d * w.w;
-    }
-  }
-  if (nq > 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) part[nq - 1][r][k4] = acc[r];
-  }
-  __syncthreads();
-  if (nq == 0) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      float4 v = acc[r];
-#pragma unroll
-      for (int q = 0; q < 3; ++q) { const float4 o = part[q][r][k4]; v.x += o.x; v.y += o.y; v.z += o.z; v.w += o.w; }
-      if (m0 + r < B) reinterpret_cast<float4*>(dr + (long)(m0 + r) * MK)[k4] = v;
-    }
-  }
-}
-
-// variant 2 (the default): the same sums, one thread per (row, float4 column), a plain loop, no LDS
+// d_repr_s[m][k] = sum_n dpre[m][n] W_s[n][k],  dpre = d_out (1 - out^2).  grid (cdiv(B, 4), 2 sides); one thread per
+// (row, float4 column), a plain loop, no LDS.  "v2": the first, pipelined kernel was not reproducible beside the bf16
+// weight-gradient stream and is retired ("A kernel that was not reproducible"; tools/hazard_repro.hip keeps its loop).
 __global__ __launch_bounds__(256) void merge_bwd_dx_v2_kernel(const float* __restrict__ out, const float* __restrict__ d_out,
                                                               const float* __restrict__ Wu, const float* __restrict__ Wi, int B,
                                                               float* __restrict__ dru, float* __restrict__ dri) {
@@ -902,9 +851,7 @@ int umpr_review_merge_fwd_impl(const float* ru, const float* ri, const float* Wu
 }
 int umpr_review_merge_bwd_impl(const float* ru, const float* ri, const float* Wu, const float* Wi, const float* out,
                                const float* d_out, int B, float* dru, float* dri, float* dWu, float* dWi, hipStream_t s) {
-  static const int dx = umpr_env_int("UMPR_MERGE_DX", 2);     // 1: the pipelined kernel above (see its comment)
-  if (dx == 2) merge_bwd_dx_v2_kernel<<<dim3(cdiv(B, 4), 2), 256, 0, s>>>(out, d_out, Wu, Wi, B, dru, dri);
-  else merge_bwd_dx_kernel<<<dim3(cdiv(B, 4), 2), 256, 0, s>>>(out, d_out, Wu, Wi, B, dru, dri);
+  merge_bwd_dx_v2_kernel<<<dim3(cdiv(B, 4), 2), 256, 0, s>>>(out, d_out, Wu, Wi, B, dru, dri);
   UMPR_LAUNCH_CHECK("merge_bwd_dx");
   merge_bwd_dw_kernel<<<dim3(MD / 4, 2), 256, 0, s>>>(out, d_out, ru, ri, B, dWu, dWi);
   UMPR_LAUNCH_CHECK("merge_bwd_dw");

@@ -6,7 +6,6 @@
 //     wino_weights_kernel      : U = G g G^T (for dgrad on the flipped, channel-transposed kernel), LDS image order
 //     wino_input[_pair]_kernel : x -> V   (HBM bound: reads |x|, writes 4|x|; zero-pads channels / tiles to the GEMM tile)
 //     wino_gemm_dma_kernel     : batched GEMM on v_mfma_f32_32x32x2_f32, operands copied global -> LDS by LDS-DMA
-//                                (wino_gemm_kernel: the same loop staged through registers, UMPR_WINO_DMA=0)
 //     wino_output[_pair]_kernel: M -> y   with the fused epilogue (+bias, ReLU) or (dgrad) * [mask > 0]
 // Data gradient, F(4x4,3x3) where the map is a multiple of 4 (wino4_* kernels, the same GEMM over 36 planes and a quarter of
 //   the tiles: 4x fewer FLOPs, V / M 2.25x instead of 4x the activation), else F(2x2,3x3) as in forward.  The forward pass
@@ -26,7 +25,6 @@ namespace {
 constexpr int WK = 32;    // channels per GEMM stage
 constexpr int WBM = 128;  // output-channel tile
 constexpr int WBN = 128;  // tile-index tile
-constexpr int WLDA = WBM + 4;
 
 // U[xi][mt][s][k][m_local]  (mt = m / 128, s = c / 32, k = c % 32), zero padded in both m and c
 __global__ void wino_weights_kernel(const float* __restrict__ w, float* __restrict__ U, int M, int C, int CinW,
@@ -711,130 +709,8 @@ struct WinoGemmParams {
   int planes;       // 16: F(2x2,3x3), 36: F(4x4,3x3) - the leading dimension of U / V / Mx
 };
 
-// grid.x = 16 * TT * MT, XCD-aware: the MT workgroups that share one V tile get consecutive slots on one XCD
-__global__ __launch_bounds__(256, 2) void wino_gemm_kernel(WinoGemmParams p) {
-  constexpr int LDA = WLDA, LDB = WBN;
-  constexpr int TM = 2, TN = 2;
-  constexpr int KS = WK / 2;                 // 16 MFMA k-steps per stage
-  constexpr int NV = 4;                      // float4 units per thread per operand per stage
-  constexpr int SFLUSH = 4;                  // stages per MFMA accumulation chain (128 k)
-  __shared__ __attribute__((aligned(16))) float As[2][WK * LDA];
-  __shared__ __attribute__((aligned(16))) float Bs[2][WK * LDB];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wm = wave >> 1, wn = wave & 1;
-  const int l31 = lane & 31, half = lane >> 5;
-  const long TT = p.TT;
-  const int xcd = blockIdx.x & 7;
-  const long qq = blockIdx.x >> 3;
-  const int mt = (int)(qq % p.MT);
-  const long bt = (qq / p.MT) * 8 + xcd;     // (xi, t-tile) index
-  if (bt >= p.planes * TT) return;
-  const int xi = (int)(bt / TT);
-  const long t0 = (bt % TT) * WBN;
-  const float* Ub = p.U + (((long)xi * p.MT + mt) * p.S) * (WK * WBM);
-  const float* Vb = p.V + (long)xi * (p.S * WK) * p.Tpad + t0;
-
-  // staging: unit u = tid + 256 v covers row k = u / 32, quad q = u % 32 of a [32][128] operand image, i.e. float
-  // offset 4u in the U image and (k, 4q) in V.  Named registers (no arrays): hipcc spills indexed float4 arrays here.
-  const float* pa = Ub + 4 * tid;
-  const float* pb = Vb + (long)(tid >> 5) * p.Tpad + 4 * (tid & 31);
-  const long bstep = 8 * p.Tpad;
-  float* sa = &As[0][(tid >> 5) * LDA + 4 * (tid & 31)];
-  float* sb = &Bs[0][(tid >> 5) * LDB + 4 * (tid & 31)];
-  float4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
-  auto lda = [&](int v, int s) { return *reinterpret_cast<const float4*>(pa + (long)s * (WK * WBM) + 1024 * v); };
-  auto ldb = [&](int v, int s) { return *reinterpret_cast<const float4*>(pb + (long)s * 4 * bstep + v * bstep); };
-  auto sta = [&](int v, int buf, const float4& r) { *reinterpret_cast<float4*>(sa + buf * (WK * LDA) + 8 * v * LDA) = r; };
-  auto stb = [&](int v, int buf, const float4& r) { *reinterpret_cast<float4*>(sb + buf * (WK * LDB) + 8 * v * LDB) = r; };
-  auto piece = [&](int q, int sn, int nbuf) {   // q = 0..15: 8 loads for stage sn, then 8 stores into buffer nbuf
-    switch (q) {
-      case 0: ra0 = lda(0, sn); break;
-      case 1: ra1 = lda(1, sn); break;
-      case 2: ra2 = lda(2, sn); break;
-      case 3: ra3 = lda(3, sn); break;
-      case 4: rb0 = ldb(0, sn); break;
-      case 5: rb1 = ldb(1, sn); break;
-      case 6: rb2 = ldb(2, sn); break;
-      case 7: rb3 = ldb(3, sn); break;
-      case 8: sta(0, nbuf, ra0); break;
-      case 9: sta(1, nbuf, ra1); break;
-      case 10: sta(2, nbuf, ra2); break;
-      case 11: sta(3, nbuf, ra3); break;
-      case 12: stb(0, nbuf, rb0); break;
-      case 13: stb(1, nbuf, rb1); break;
-      case 14: stb(2, nbuf, rb2); break;
-      default: stb(3, nbuf, rb3); break;
-    }
-  };
-
-  f32x16 acc[TM][TN], tot[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) { acc[i][j][r] = 0.f; tot[i][j][r] = 0.f; }
-
-  const int ns = p.S;
-#pragma unroll
-  for (int q = 0; q < 16; ++q) piece(q, 0, 0);
-  __syncthreads();
-  for (int s0 = 0; s0 < ns; s0 += SFLUSH) {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int s1 = min(ns, s0 + SFLUSH);
-    for (int s = s0; s < s1; ++s) {
-      const int cur = s & 1;
-      const int sn = min(s + 1, ns - 1);
-      const float* as = As[cur] + half * LDA + wm * 64 + l31;
-      const float* bs = Bs[cur] + half * LDB + wn * 64 + l31;
-      float a[2][TM], b[2][TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) a[0][i] = as[i * 32];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) b[0][j] = bs[j * 32];
-#pragma unroll
-      for (int kk = 0; kk < KS; ++kk) {
-        const int cb = kk & 1, nb = cb ^ 1;
-        const int k1 = kk + 1;
-#pragma unroll
-        for (int m = 0; m < TM * TN; ++m) {
-          const int i = m / TN, j = m % TN;
-          acc[i][j] = mfma32(a[cb][i], b[cb][j], acc[i][j]);
-          if (m == 0 && k1 < KS) {
-#pragma unroll
-            for (int ii = 0; ii < TM; ++ii) a[nb][ii] = as[2 * k1 * LDA + ii * 32];
-          }
-          if (m == 1 && k1 < KS) {
-#pragma unroll
-            for (int jj = 0; jj < TN; ++jj) b[nb][jj] = bs[2 * k1 * LDB + jj * 32];
-          }
-          if (m == 3) piece(kk, sn, cur ^ 1);   // one staging piece per k-step
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
-      __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) tot[i][j] += acc[i][j];
-  }
-  float* Mb = p.Mx + ((long)xi * p.Mpad + mt * WBM) * p.Tpad + t0;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r)
-        Mb[(long)(wm * 64 + i * 32 + mfma_row(r, lane)) * p.Tpad + wn * 64 + j * 32 + l31] = tot[i][j][r];
-}
-
-// Same GEMM with the operand tiles copied global -> LDS by the LDS-DMA path (global_load_lds_dwordx4: no staging
+// grid.x = planes * TT * MT, XCD-aware: the MT workgroups that share one V tile get consecutive slots on one XCD.
+// The operand tiles are copied global -> LDS by the LDS-DMA path (global_load_lds_dwordx4: no staging
 // registers, no ds_write, no address VALU).  Both stage images are lane-linear: U is stored in image order, and a V
 // stage is 32 rows of 128 contiguous floats, so one wave-instruction (64 lanes x 16 B) fills two unpadded 512-B rows.
 // Unpadded rows are conflict-free for the fragment reads (32 consecutive floats per half-wave).
@@ -842,16 +718,16 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // FOLD: how the MFMA accumulation chains are folded into the running total.  In a Winograd GEMM the accumulation rounding is
 // the dominant error of the whole convolution (CPU ablation, round 3: with exact accumulation the 4x4 tile's result is 2-3e-7
 // rms from float64, like the direct kernel; with one fp32 chain over all channels 1e-6): the outputs are differences of plane
-// values ~20x their own size, so every eps of a partial sum counts 20-fold.  0: chains of 128 channels, fp32 total (rounds 1-2:
-// 9.2e-7 measured on the 4x4 tile); 1: chains of one 32-channel stage, fp32 total; 2: chains of one stage, FLOAT64 total (the
-// fold's cvt + v_add_f64 run under the other wave's MFMAs).
-template <int SK, int OCC, int FOLD>
-__global__ __launch_bounds__(256, OCC) void wino_gemm_dma_kernel(WinoGemmParams p) {
+// values ~20x their own size, so every eps of a partial sum counts 20-fold.  Chains are one 32-channel stage long; 1: fp32
+// total; 2: FLOAT64 total (the fold's cvt + v_add_f64 run under the other wave's MFMAs).
+template <int FOLD>
+__global__ __launch_bounds__(256, 2) void wino_gemm_dma_kernel(WinoGemmParams p) {
+  constexpr int SK = WK;                // channels per stage
   constexpr int LD = 128;
   constexpr int TM = 2, TN = 2;
   constexpr int KS = SK / 2;            // MFMA k-steps per stage
   constexpr int NP = SK / 8;            // 1-KiB DMA pieces per wave, operand and stage
-  constexpr int SFLUSH = FOLD == 0 ? 128 / SK : 1;      // stages per MFMA accumulation chain
+  constexpr int SFLUSH = 1;             // stages per MFMA accumulation chain
   typedef typename std::conditional<FOLD == 2, double, float>::type tot_t;
   __shared__ __attribute__((aligned(1024))) float As[2][SK * LD];
   __shared__ __attribute__((aligned(1024))) float Bs[2][SK * LD];
@@ -961,8 +837,6 @@ __global__ __launch_bounds__(256, OCC) void wino_gemm_dma_kernel(WinoGemmParams 
         Mb[(long)(wm * 64 + i * 32 + mfma_row(r, lane)) * p.Tpad + wn * 64 + j * 32 + l31] = (float)tot[i][j][r];
 }
 
-const int g_wino_dma = umpr_env_int("UMPR_WINO_DMA", 1);   // 0 off, 1: 32-deep stages, 2: 16-deep stages at 3 waves/SIMD
-
 inline int nblk(long n, int cap) {
   long b = (n + 255) / 256;
   if (b > cap) b = cap;
@@ -1037,29 +911,12 @@ size_t umpr_wino_ws_floats(int N, int C, int M, int H, int W, int transposed) {
   return a > b ? a : b;
 }
 
-// Image chunking: V and M (each 4x the activation they transform) are written by one kernel and read back by the next.
-// With the whole batch in one pass (411 MB + 822 MB at 56x56x128->256, batch 64) every one of those bytes goes to HBM and
-// comes back; a chunk whose V + M stay under the 256 MiB Infinity Cache is re-read on die
-// (MI355X_MICROARCH.md, Infinity Cache: a line stays resident while the bytes touched between two uses fit).
-// UMPR_WINO_CHUNK_MB = budget for V + M of one chunk (0 = whole batch in one pass, the default).
-// Measured (batch 64, fp32 step): 0 -> 42.5 ms, 224 -> 45.3, 160 -> 46.5, 96 -> 50.7: the smaller GEMMs and the extra
-// launches cost more than on-die re-reads give back, so it stays an experiment switch (profiles/README.md, r02_n).
-static const long g_wino_chunk_mb = (long)umpr_env_int("UMPR_WINO_CHUNK_MB", 0);
-static int wino_chunk_images(int N, long floats_per_image) {
-  if (g_wino_chunk_mb <= 0) return N;
-  long nc = (g_wino_chunk_mb << 20) / (floats_per_image * 4);
-  if (nc < 1) nc = 1;
-  if (nc >= N) return N;
-  const int parts = (int)((N + nc - 1) / nc);          // equal parts: no small tail chunk
-  return (N + parts - 1) / parts;
-}
-
 // floats of the forward V of a layer whose weight gradient can read it back (0: the layer does not qualify): training forward
 // and weight gradient both on the 4x4 tile over the same tile grid, and the two GEMMs' channel paddings agree
 size_t umpr_wino_v_floats(int N, int Cin, int Cout, int H, int W) {
   if (umpr_wino_f4_mode() < 2 || !wino_f4_shape(H, W) || (H % 4) != 0 || (W % 4) != 0) return 0;
   static const int on = umpr_env_int("UMPR_WINO_V_REUSE", 1);
-  if (!on || g_wino_chunk_mb > 0) return 0;
+  if (!on) return 0;
   const long S = (Cin + WK - 1) / WK;
   const long bnc = Cin <= 64 ? 64 : WBN;
   if (S * WK != (Cin + bnc - 1) / bnc * bnc) return 0;
@@ -1067,32 +924,13 @@ size_t umpr_wino_v_floats(int N, int Cin, int Cout, int H, int W) {
   return (size_t)36 * S * WK * wino_tpad(T);
 }
 
-static int wino_conv3x3_pass(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
-                             int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, hipStream_t s,
-                             bool weights_ready);
-
 // forward (transposed = 0) or data gradient (transposed = 1), same contract as umpr_conv3x3_run
 int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
                       int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, hipStream_t s) {
-  const int M = transposed ? Cin : Cout, C = transposed ? Cout : Cin;
-  UMPR_REQUIRE(ws_floats >= umpr_wino_ws_floats(N, C, M, H, W, transposed), "winograd: workspace too small");
-  const int nc = wino_chunk_images(N, (long)16 * (C + M) * (H / 2) * (W / 2));
-  for (int n0 = 0; n0 < N; n0 += nc) {
-    const int n = N - n0 < nc ? N - n0 : nc;
-    // U sits at the start of the workspace and does not depend on the chunk size: transformed once
-    if (int rc = wino_conv3x3_pass(x + (size_t)n0 * C * H * W, w, transposed, bias, mask ? mask + (size_t)n0 * M * H * W : nullptr,
-                                   y + (size_t)n0 * M * H * W, n, Cin, Cout, H, W, relu, ws, ws_floats, s, n0 > 0)) return rc;
-  }
-  return 0;
-}
-
-static int wino_conv3x3_pass(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
-                             int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, hipStream_t s,
-                             bool weights_ready) {
-  UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd: odd map %dx%d", H, W);
   const int M = transposed ? Cin : Cout;
   const int C = transposed ? Cout : Cin;
   UMPR_REQUIRE(ws_floats >= umpr_wino_ws_floats(N, C, M, H, W, transposed), "winograd: workspace too small");
+  UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd: odd map %dx%d", H, W);
   const bool f4 = wino_f4_map(H, W, transposed);
   const int planes = f4 ? 36 : 16;
   const long T = f4 ? (long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long)N * (H / 2) * (W / 2);
@@ -1110,11 +948,9 @@ static int wino_conv3x3_pass(const float* x, const float* w, int transposed, con
                  "winograd: the V slot does not fit this forward (%d -> %d at %dx%d)", Cin, Cout, H, W);
     V = t_v_slot;
   }
-  if (!weights_ready) {
-    if (f4) wino4_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed, wino4_consts());
-    else wino_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed);
-    UMPR_LAUNCH_CHECK("wino_weights");
-  }
+  if (f4) wino4_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed, wino4_consts());
+  else wino_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed);
+  UMPR_LAUNCH_CHECK("wino_weights");
   const long TT = (T + WBN - 1) / WBN;
   // decision fix-up (training forward on the 4x4 tile only): counter in the 64 spare floats behind Mx, list in V once the GEMM
   // has consumed it
@@ -1158,12 +994,9 @@ static int wino_conv3x3_pass(const float* x, const float* w, int transposed, con
   const long groups = (planes * TT + 7) / 8 * 8;
   {
     UmprProfScope prof(UMPR_K_WINO_GEMM, 2.0 * planes * (double)M * C * T, s);
-    static const int fold = umpr_env_int("UMPR_WINO_FOLD", 1);   // measured (4x4 tile, rms of rms y): 0: 9.2e-7, 1: 6.0e-7 at the same speed, 2: 5.4e-7 for -9 % GEMM rate
-    if (g_wino_dma == 2) wino_gemm_dma_kernel<16, 3, 0><<<(unsigned)(groups * MT), 256, 0, s>>>(p);
-    else if (g_wino_dma && fold == 2) wino_gemm_dma_kernel<32, 2, 2><<<(unsigned)(groups * MT), 256, 0, s>>>(p);
-    else if (g_wino_dma && fold == 1) wino_gemm_dma_kernel<32, 2, 1><<<(unsigned)(groups * MT), 256, 0, s>>>(p);
-    else if (g_wino_dma) wino_gemm_dma_kernel<32, 2, 0><<<(unsigned)(groups * MT), 256, 0, s>>>(p);
-    else wino_gemm_kernel<<<(unsigned)(groups * MT), 256, 0, s>>>(p);
+    static const int fold = umpr_env_int("UMPR_WINO_FOLD", 1);   // measured (4x4 tile, rms of rms y): 1: 6.0e-7, 2: 5.4e-7 for -9 % GEMM rate
+    if (fold == 2) wino_gemm_dma_kernel<2><<<(unsigned)(groups * MT), 256, 0, s>>>(p);
+    else wino_gemm_dma_kernel<1><<<(unsigned)(groups * MT), 256, 0, s>>>(p);
   }
   UMPR_LAUNCH_CHECK("wino_gemm");
   if (f4 && fix) {
@@ -1728,25 +1561,10 @@ size_t umpr_wino_wgrad_ws_floats(int N, int Cin, int Cout, int H, int W) {
          (size_t)g.Mpad * (g.Tpad / 64) + 64;
 }
 
-static int wino_wgrad_pass(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
-                           int accumulate, float* ws, size_t ws_floats, hipStream_t s);
-
 int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
                     int accumulate, float* ws, size_t ws_floats, hipStream_t s) {
   UMPR_REQUIRE(ws_floats >= umpr_wino_wgrad_ws_floats(N, Cin, Cout, H, W), "winograd wgrad: workspace too small");
-  const int nc = wino_chunk_images(N, (long)16 * (Cin + Cout) * (H / 2) * (W / 2));
-  for (int n0 = 0; n0 < N; n0 += nc) {   // chunks accumulate in image order: fixed summation order
-    const int n = N - n0 < nc ? N - n0 : nc;
-    if (int rc = wino_wgrad_pass(dy + (size_t)n0 * Cout * H * W, x + (size_t)n0 * Cin * H * W, dw, db, n, Cin, Cout, H, W,
-                                 accumulate || n0 > 0, ws, ws_floats, s)) return rc;
-  }
-  return 0;
-}
-
-static int wino_wgrad_pass(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
-                           int accumulate, float* ws, size_t ws_floats, hipStream_t s) {
   UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd wgrad: odd map %dx%d", H, W);
-  UMPR_REQUIRE(ws_floats >= umpr_wino_wgrad_ws_floats(N, Cin, Cout, H, W), "winograd wgrad: workspace too small");
   const WinoWgradGeom g = wino_wgrad_geom(N, Cin, Cout, H, W);
   float* Gy = ws;
   float* V = Gy + (size_t)g.planes * g.Mpad * g.Tpad;
