@@ -3,7 +3,9 @@
 the GPU must not fork+exec another GPU program on this pool).  Runs, one after the other so that few processes share the card:
   * six test_conv3x3 cases with UMPR_WINO_F4=0 and again with =1 (the switch is read when the library loads; default 2),
   * tools/check_exchange_world1.py (gradient exchange on the RCCL backend at world size 1),
-  * ten model-level oracle comparisons of the text path with UMPR_POISON_WS=1 (workspaces pre-filled with NaN bytes).
+  * ten model-level oracle comparisons of the text path with UMPR_POISON_WS=1 (workspaces pre-filled with NaN bytes),
+  * the VGG feature entry points at exact workspace size with UMPR_WGRAD_STREAM=0 (read when the library loads); the run leaves
+    its gradient digests beside the logs for tests/test_gpu_workspace_layouts.py to compare with the side-stream run.
 This launcher itself never touches the GPU.  Each job writes gpurun_out/<name>.log; the exit codes go to
 gpurun_out/gpu_children.rc as `<name> <rc>` lines."""
 import os
@@ -27,6 +29,9 @@ def main():
     jobs.append(("poison_ws_check", dict(env, UMPR_POISON_WS="1"),
                  [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-x", "-m", "gpu", "-p",
                   "no:cacheprovider", "-k", "umpr_r_golden or umpr_r_small_batches or kernel_size_and_sentence or embedding_widths"]))
+    jobs.append(("wgrad_stream0_check", dict(env, UMPR_WGRAD_STREAM="0"),
+                 [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_workspace_layouts.py"), "-q", "-x", "-m", "gpu",
+                  "-p", "no:cacheprovider", "-k", "test_vgg_features_at_exact_workspace_size"]))
     with open(os.path.join(OUT, "gpu_children.rc"), "w") as rcf:
         for name, e, cmd in jobs:
             with open(os.path.join(OUT, name + ".log"), "w") as f:

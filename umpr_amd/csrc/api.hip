@@ -21,8 +21,6 @@ void umpr_set_error(const char* fmt, ...) {
 namespace {
 // UMPR_FC_SMALL=0: batch-sized-M products stay on the tiled GEMM (A/B runs)
 const bool g_fc_small = umpr_env_on("UMPR_FC_SMALL");
-// UMPR_MERGE_SMALL=0: linear_u / linear_i of the review merge on the fc kernels above (two launches forward, five backward)
-const bool g_merge_small = umpr_env_on("UMPR_MERGE_SMALL");
 struct ProfRec { hipEvent_t e0, e1; int family; double work; };
 bool g_prof_on = false;
 std::vector<ProfRec> g_prof;
@@ -30,6 +28,8 @@ std::vector<ProfRec> g_prof_pool;
 double g_prof_ms[UMPR_K_COUNT] = {0}, g_prof_work[UMPR_K_COUNT] = {0};
 long g_prof_n[UMPR_K_COUNT] = {0};
 }  // namespace
+// UMPR_MERGE_SMALL=0: linear_u / linear_i of the review merge on the fc kernels above (two launches forward, five backward)
+bool umpr_merge_small() { static const bool on = umpr_env_on("UMPR_MERGE_SMALL"); return on; }
 UmprProfScope::UmprProfScope(int family, double work, hipStream_t s) : idx(-1), stream(s) {
   if (!g_prof_on) return;
   ProfRec r;
@@ -46,7 +46,6 @@ UmprProfScope::~UmprProfScope() {
 
 namespace {
 inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
-constexpr int D = 128, H = 64, G3 = 192, AT = 64;
 
 // VGG16-D geometry (torchvision cfg "D"): 13 convs in 5 blocks, a 2x2 max pool after each block
 constexpr int kConvPerBlock[5] = {2, 3 - 1, 3, 3, 3};  // 2,2,3,3,3
@@ -130,15 +129,25 @@ long umpr_debug_wino_fix_count(void) { return umpr_wino_last_fix_count(); }
 // split-K slabs of the dW_ih product ([384][Ep] each, two slabs per unit): 256 units = up to 128 splits of the [384 x Ep] x N*L
 // product (64 left its 3 x 64 = 192 workgroups walking 800 reduction steps each at GloVe-50d: 42 us at batch 32)
 constexpr size_t kSlabs = 256;
-size_t umpr_embed_gru_bidir_ws_bytes(int N, int L, int E) {
-  const size_t tiles = umpr_gru_tiles(N);
-  // gx / dgx [N*L*384] + dWhh slabs + bias slabs + split-K slab for dW_ih (forward: the stacked input weights) + the
-  // stacked [384][Ep] weight gradient + the gathered embedding rows [N*L][Ep]; Ep = E rounded up to 4 floats (16-B rows)
-  const size_t Ep = (size_t)((E + 3) & ~3);
-  return ((size_t)N * L * 384 + tiles * 2 * G3 * H + tiles * 2 * 2 * G3 + (size_t)kSlabs * G3 * Ep + (size_t)2 * G3 * Ep +
-          (size_t)N * L * Ep) * sizeof(float);
-}
 namespace {
+// Workspace of the embedding + GRU entry points for rows of `pitch` floats
+struct GruWs {
+  float *gx, *wslab, *bslab;   // [N*L][384] input projections (backward: dgx); per-tile slabs of the dW_hh and of the bias gradients
+  float* kslab; size_t kslab_bytes;   // split-K slabs of the dW_ih product
+  float *stacked, *rows;              // the stacked [384][pitch] weight gradient; the gathered embedding rows [N*L][pitch]
+  float *wst, *bst;   // forward only, ON the split-K slabs on purpose: the stacked input weights [384][pitch] and biases [384]
+  size_t bytes;
+};
+GruWs gru_ws(float* base, int N, int L, int pitch) {
+  Carve c(base, sizeof(float));
+  const size_t tiles = umpr_gru_tiles(N);
+  GruWs w;
+  w.gx = c.take<float>((size_t)N * L * 384); w.wslab = c.take<float>(tiles * 2 * G3 * H); w.bslab = c.take<float>(tiles * 2 * 2 * G3);
+  w.wst = c.at<float>(c.off); w.bst = c.at<float>(c.off + (size_t)2 * G3 * pitch * sizeof(float));
+  w.kslab_bytes = kSlabs * G3 * pitch * sizeof(float); w.kslab = c.take<float>(kSlabs * G3 * pitch);
+  w.stacked = c.take<float>((size_t)2 * G3 * pitch); w.rows = c.take<float>((size_t)N * L * pitch); w.bytes = c.off;
+  return w;
+}
 // The token rows of the embedding table, gathered ONCE into a contiguous [N*L][E] matrix (one wave per row, whole 1200-B rows)
 // instead of inside the projection GEMM, whose 128 x 128 tiles fetched 64-B pieces of random rows of the 480 MB table stage
 // by stage and three times over (one per column tile): 228 us for 260 MB at E = 300.  UMPR_EMB_GATHER=0: gather in the GEMM.
@@ -181,10 +190,7 @@ __global__ __launch_bounds__(256) void unstack_dwih_kernel(const float* __restri
   float* dst = row < G3 ? df + (long)row * E + c : dr + (long)(row - G3) * E + c;
   *dst = accumulate ? *dst + v : v;
 }
-inline int emb_pitch(int E) { return g_emb_gather ? (E + 3) & ~3 : E; }
-float* gathered_rows(float* ws, int N, int L, int Ep) {
-  return ws + (size_t)N * L * 384 + (size_t)umpr_gru_tiles(N) * (2 * G3 * H + 2 * 2 * G3) + (size_t)kSlabs * G3 * Ep + (size_t)2 * G3 * Ep;
-}
+inline int emb_pitch(int E) { return g_emb_gather ? (E + 3) & ~3 : E; }   // the pitch the entry points carve with
 int gather_rows(const int64_t* ids, const float* emb, int E, int Ep, float* out, long rows, hipStream_t s) {
   long blocks = (rows + 3) / 4;
   if (blocks > 16384) blocks = 16384;
@@ -194,6 +200,8 @@ int gather_rows(const int64_t* ids, const float* emb, int E, int Ep, float* out,
 }
 }  // namespace
 
+// the size is that of rows of E rounded up to 4 floats (16-B rows), also where UMPR_EMB_GATHER=0 carves with a pitch of E
+size_t umpr_embed_gru_bidir_ws_bytes(int N, int L, int E) { return gru_ws(nullptr, N, L, (E + 3) & ~3).bytes; }
 int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
                              const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
                              const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
@@ -201,21 +209,21 @@ int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
                              float* out, float* saved, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(N > 0 && L > 0 && E > 0, "embed_gru: bad shape N=%d L=%d E=%d", N, L, E);
   UMPR_REQUIRE(ws_bytes >= (size_t)N * L * 384 * sizeof(float), "embed_gru: workspace too small");
-  float* gx = ws;
+  const int Ep = emb_pitch(E);
+  const GruWs W = gru_ws(ws, N, L, Ep);
+  float* gx = W.gx;
   // gx[:, 0:192 | 192:384] = emb[ids] [W_ih_f ; W_ih_r]^T + [b_ih_f ; b_ih_r]: ONE gather-GEMM for both directions (the
   // embedding rows are fetched once instead of twice, and N = 384 fills three 128-column tiles where 192 wasted half of
-  // its second one).  The stacked [384][E] weight / [384] bias live behind gx in the workspace.
+  // its second one).  The stacked [384][Ep] weight / [384] bias live on the backward's slab area.
   if (ws_bytes >= umpr_embed_gru_bidir_ws_bytes(N, L, E)) {
-    const int Ep = emb_pitch(E);
-    float* wst = gx + (size_t)N * L * 384 + (size_t)umpr_gru_tiles(N) * (2 * G3 * H + 2 * 2 * G3);   // the dW_ih slab area
-    float* bst = wst + (size_t)2 * G3 * Ep;
+    float *wst = W.wst, *bst = W.bst;
     const hipStream_t s = S(stream);
     // stack the two directions' input weights and biases: one launch
     stack_wih_kernel<<<cdiv(2 * G3 * Ep, 256), 256, 0, s>>>(w_ih_f, w_ih_r, b_ih_f, b_ih_r, E, Ep, wst, bst);
     UMPR_LAUNCH_CHECK("stack_wih");
     UmprGemm g;
     if (g_emb_gather) {
-      float* xg = gathered_rows(ws, N, L, Ep);
+      float* xg = W.rows;
       if (int rc = gather_rows(ids, emb, E, Ep, xg, (long)N * L, s)) return rc;
       g.A = xg; g.lda = Ep;
     } else {
@@ -244,11 +252,9 @@ int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E, co
                                  int accumulate, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(dout != nullptr && out != nullptr && saved != nullptr, "embed_gru_bwd: dout / out / saved must not be NULL");
   UMPR_REQUIRE(ws_bytes >= umpr_embed_gru_bidir_ws_bytes(N, L, E), "embed_gru_bwd: workspace too small");
-  const int tiles = umpr_gru_tiles(N);
-  float* dgx = ws;
-  float* wslab = dgx + (size_t)N * L * 384;
-  float* bslab = wslab + (size_t)tiles * 2 * G3 * H;
-  float* kslab = bslab + (size_t)tiles * 2 * 2 * G3;
+  const int tiles = umpr_gru_tiles(N), Ep = emb_pitch(E);
+  const GruWs W = gru_ws(ws, N, L, Ep);
+  float *dgx = W.gx, *wslab = W.wslab, *bslab = W.bslab;
   if (int rc = umpr_gru_bptt(dout, out, saved, w_hh_f, w_hh_r, lengths, order, dst_row, dgx, wslab, bslab, N, L, S(stream)))
     return rc;
   float* dwhh[2] = {dw_hh_f, dw_hh_r};
@@ -267,19 +273,18 @@ int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E, co
   }
   {  // [dW_ih_f ; dW_ih_r] [384][E] = dgx^T emb[ids]: one split-K gather-GEMM for both directions, then rows 0..191 /
      // 192..383 are copied (or added) to their parameters' gradients
-    const int Ep = emb_pitch(E);
-    float* stacked = kslab + (size_t)kSlabs * G3 * Ep;
+    float* stacked = W.stacked;
     UmprGemm g;
     g.A = dgx; g.lda = 384; g.transA = true;
     if (g_emb_gather) {
-      float* xg = gathered_rows(ws, N, L, Ep);
+      float* xg = W.rows;
       if (int rc = gather_rows(ids, emb, E, Ep, xg, (long)N * L, S(stream))) return rc;
       g.B = xg; g.ldb = Ep;
     } else {
       g.B = emb; g.ldb = E; g.gatherB = ids;
     }
-    g.C = stacked; g.ldc = Ep; g.M = 2 * G3; g.N = Ep; g.K = N * L; g.split_k = 0; g.ws = kslab;   // (tail columns: zeros)
-    g.ws_bytes = (size_t)kSlabs * G3 * Ep * sizeof(float);
+    g.C = stacked; g.ldc = Ep; g.M = 2 * G3; g.N = Ep; g.K = N * L; g.split_k = 0; g.ws = W.kslab;   // (tail columns: zeros)
+    g.ws_bytes = W.kslab_bytes;
     if (int rc = umpr_gemm(g, S(stream))) return rc;
     unstack_dwih_kernel<<<cdiv(2 * G3 * E, 256), 256, 0, S(stream)>>>(stacked, E, Ep, dwih[0], dwih[1], accumulate);
     UMPR_LAUNCH_CHECK("unstack_dwih");
@@ -338,7 +343,7 @@ int umpr_snet_bwd(const float* X, const float* Ms, const float* Ws, const float*
 // ------------------------------------------------------------------------------------------------ merge
 int umpr_review_merge_fwd(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, int B,
                           float* out, void* stream) {
-  if (g_merge_small && B <= 256) return umpr_review_merge_fwd_impl(repr_u, repr_i, W_u, W_i, B, out, nullptr, S(stream));
+  if (umpr_merge_small() && B <= 256) return umpr_review_merge_fwd_impl(repr_u, repr_i, W_u, W_i, B, out, nullptr, S(stream));
   if (g_fc_small && umpr_fc_small_ok(B, D, 2 * D)) {
     // batch-sized M: the register-streaming kernels (no LDS stage, no barrier per k-tile) instead of one workgroup of
     // the tiled GEMM walking 16 k-tiles one global round trip at a time (35 us -> 4 us at B = 32)
@@ -356,7 +361,7 @@ int umpr_review_merge_bwd(const float* repr_u, const float* repr_i, const float*
                           const float* out, const float* d_out, int B, float* d_repr_u, float* d_repr_i, float* dW_u,
                           float* dW_i, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(ws_bytes >= umpr_review_merge_bwd_ws_bytes(B), "review_merge_bwd: workspace too small");
-  if (g_merge_small && B <= 256)   // tanh' folded into the two kernels
+  if (umpr_merge_small() && B <= 256)   // tanh' folded into the two kernels
     return umpr_review_merge_bwd_impl(repr_u, repr_i, W_u, W_i, out, d_out, B, d_repr_u, d_repr_i, dW_u, dW_i, S(stream));
   float* dpre = ws;
   if (int rc = umpr_tanh_bwd(out, d_out, dpre, (long)B * D, S(stream))) return rc;
@@ -438,17 +443,35 @@ size_t vgg_scratch_bytes(int n) {
   fcs *= sizeof(float);
   return align_up(slab > fcs ? slab : fcs, 256);
 }
-// scratch of the data-gradient convs (packed weights / Winograd buffers): as large as the forward scratch
-static size_t wt_floats(int n) { return vgg_scratch_bytes(n) / sizeof(float); }
+// Workspace of the feature backward: [3 rotating gradient slots] (largest activation each) [wt: scratch of the data-gradient
+// convs (packed weights / Winograd buffers), as large as the forward scratch][scratch of the weight gradients]
+struct VggFeatBwdWs { float *slot[3], *wt, *scratch; size_t wt_floats, scratch_bytes, bytes; };
+VggFeatBwdWs vgg_feat_bwd_ws(float* base, int n) {
+  Carve c(base, sizeof(float));
+  VggFeatBwdWs w;
+  w.scratch_bytes = vgg_scratch_bytes(n); w.wt_floats = w.scratch_bytes / sizeof(float);
+  for (int k = 0; k < 3; ++k) w.slot[k] = c.take<float>((size_t)n * 64 * 224 * 224);
+  w.wt = c.take<float>(w.wt_floats); w.scratch = c.take<float>(w.wt_floats); w.bytes = c.off;
+  return w;
+}
+// Workspace of the classifier backward: [gA][gB] (the two alternating gradient rows [n][4096]) [scratch]
+struct VggClsBwdWs { float *gA, *gB, *scratch; size_t scratch_bytes, bytes; };
+VggClsBwdWs vgg_cls_bwd_ws(float* base, int n) {
+  Carve c(base, sizeof(float));
+  const size_t sb = vgg_scratch_bytes(n);
+  return VggClsBwdWs{c.take<float>((size_t)n * 4096), c.take<float>((size_t)n * 4096), c.take<float>(sb / sizeof(float)), sb, c.off};
+}
+// Workspace of umpr_vgg16_bwd: [d_pool5][stage], the stage workspace being the feature backward's (the larger of the two)
+struct VggBwdWs { float *d_pool5, *stage; size_t prefix, bytes; };
+VggBwdWs vgg_bwd_ws(float* base, int n) {
+  Carve c(base, sizeof(float));
+  float* d_pool5 = c.take<float>((size_t)n * 25088);
+  return VggBwdWs{d_pool5, c.at<float>(c.off), c.off, c.off + vgg_feat_bwd_ws(nullptr, n).bytes};
+}
 }  // namespace
 
 size_t umpr_vgg16_fwd_ws_bytes(int n_img) { return vgg_scratch_bytes(n_img); }
-
-size_t umpr_vgg16_ws_bytes(int n_img) {
-  // [d_pool5][3 rotating gradient slots] (largest activation each) [packed weights][scratch]
-  const size_t big = (size_t)n_img * 64 * 224 * 224;
-  return ((size_t)n_img * 25088 + 3 * big + wt_floats(n_img)) * sizeof(float) + vgg_scratch_bytes(n_img);
-}
+size_t umpr_vgg16_ws_bytes(int n_img) { return vgg_bwd_ws(nullptr, n_img).bytes; }
 
 size_t umpr_conv3x3_pack_bytes(int N, int Cin, int Cout, int H_, int W) {
   return umpr_conv3x3_pack_floats(N, Cin, Cout, H_, W) * sizeof(float);
@@ -513,18 +536,13 @@ namespace {
 struct ClsActs { const float* pool5; float* fc[2]; float* drop[2]; };
 
 // Above 128 rows umpr_fc_small_ok fails and the classifier's products run on the generic GEMM: under the bf16 entry points they
-// must round their operands there too (before, they silently ran in fp32).  The host thread's own setting is restored.
-struct ClsB16Scope {
-  int prev;
-  explicit ClsB16Scope(int on) : prev(umpr_gemm_b16()) { if (on) umpr_gemm_set_b16(1); }
-  ~ClsB16Scope() { umpr_gemm_set_b16(prev); }
-};
+// must round their operands there too (before, they silently ran in fp32): UmprB16Scope.
 
 int classifier_fwd_impl(const float* const* params, int n, int train, int use_masks, uint64_t seed, const ClsActs& A,
                         uint8_t* masks, float* out, float* ws, size_t ws_bytes, hipStream_t s, int bf16 = 0) {
   // AdaptiveAvgPool2d(7) is the identity on the 7x7 map a 224x224 image produces
   const float* x = A.pool5;
-  ClsB16Scope b16_scope(bf16);
+  UmprB16Scope b16_scope(bf16);
   for (int j = 0; j < 3; ++j) {
     float* y = j < 2 ? A.fc[j] : out;
     const int act = j < 2 ? UMPR_ACT_RELU : UMPR_ACT_NONE;
@@ -585,9 +603,7 @@ int umpr_vgg16_fwd(const float* images, const float* const* params, int n, int t
   return umpr_vgg16_classifier_fwd(params, n, train, use_masks, seed, acts, masks, out, ws, ws_bytes, stream);
 }
 
-size_t umpr_vgg16_classifier_bwd_ws_bytes(int n_img) {
-  return (size_t)2 * n_img * 4096 * sizeof(float) + vgg_scratch_bytes(n_img);
-}
+size_t umpr_vgg16_classifier_bwd_ws_bytes(int n_img) { return vgg_cls_bwd_ws(nullptr, n_img).bytes; }
 
 // d_pool5 [n][25088] receives the gradient w.r.t. the pooled feature map; grads: the 32-pointer array (only the six
 // classifier entries 26..31 are written).
@@ -595,13 +611,10 @@ namespace {
 int classifier_bwd_impl(const float* const* params, int n, int train, const ClsActs& A, const uint8_t* masks,
                         const float* d_out, float* const* grads, float* d_pool5, float* ws, size_t ws_bytes, hipStream_t s,
                         int bf16 = 0) {
-  ClsB16Scope b16_scope(bf16);
-  float* gA = ws;
-  float* gB = ws + (size_t)n * 4096;
-  float* scratch = gB + (size_t)n * 4096;
-  const size_t slab_bytes = vgg_scratch_bytes(n);
+  UmprB16Scope b16_scope(bf16);
+  const VggClsBwdWs W = vgg_cls_bwd_ws(ws, n);
   const float* g = d_out;  // gradient w.r.t. the current layer's output
-  float* cur = gA; float* oth = gB;
+  float* cur = W.gA; float* oth = W.gB;
   for (int j = 2; j >= 0; --j) {
     const int fin = kFc[j][0], fout = kFc[j][1];
     const float* xin = j == 0 ? A.pool5 : (train ? A.drop[j - 1] : A.fc[j - 1]);
@@ -623,11 +636,11 @@ int classifier_bwd_impl(const float* const* params, int n, int train, const ClsA
     if (int rc = umpr_colsum_rows(g, n, fout, fout, grads[27 + 2 * j], 0, s)) return rc;
     float* dxo = j == 0 ? d_pool5 : cur;
     if (small) {  // dx[n][fin] = g W
-      if (int rc = umpr_fc_small_dx(g, params[26 + 2 * j], dxo, n, fout, fin, scratch, slab_bytes, s, bf16)) return rc;
+      if (int rc = umpr_fc_small_dx(g, params[26 + 2 * j], dxo, n, fout, fin, W.scratch, W.scratch_bytes, s, bf16)) return rc;
     } else {
       UmprGemm d;
       d.A = g; d.lda = fout; d.B = params[26 + 2 * j]; d.ldb = fin; d.C = dxo; d.ldc = fin; d.M = n;
-      d.N = fin; d.K = fout; d.split_k = 0; d.ws = scratch; d.ws_bytes = slab_bytes;
+      d.N = fin; d.K = fout; d.split_k = 0; d.ws = W.scratch; d.ws_bytes = W.scratch_bytes;
       if (int rc = umpr_gemm(d, s)) return rc;
     }
     g = dxo; float* t = cur; cur = oth; oth = t;
@@ -673,10 +686,7 @@ int umpr_vgg16_classifier_bwd_compact_bf16(const float* const* params, int n, in
                              d_pool5, ws, ws_bytes, S(stream), 1);
 }
 
-size_t umpr_vgg16_features_bwd_ws_bytes(int n_img) {
-  const size_t big = (size_t)n_img * 64 * 224 * 224;
-  return (3 * big + wt_floats(n_img)) * sizeof(float) + vgg_scratch_bytes(n_img);
-}
+size_t umpr_vgg16_features_bwd_ws_bytes(int n_img) { return vgg_feat_bwd_ws(nullptr, n_img).bytes; }
 
 // Library-owned side stream for the weight-gradient kernels of the VGG backward (one per process: one GPU per process).
 namespace {
@@ -698,6 +708,30 @@ struct WgradSide {
 };
 WgradSide g_wside;
 const bool g_wgrad_side = umpr_env_on("UMPR_WGRAD_STREAM");
+// The side-stream schedule of both VGG feature backwards.  The weight gradient of a layer depends only on that layer's output
+// gradient, not on the data-gradient chain that continues below it: it runs on a side stream, so that its MFMA work fills the
+// HBM-bound phases of the chain (pool backward, Winograd transforms) on the caller's stream.  The gradient buffers rotate through
+// three slots: a slot is rewritten two layers after it was produced, behind a wait for the wgrad that read it.
+// UMPR_WGRAD_STREAM=0: no side stream and no events - a straight line on the caller's stream.
+struct WgradSchedule {
+  hipStream_t s; bool side; hipStream_t sw;   // the caller's stream; whether there is a side stream; where the wgrads go
+  int reader[3] = {-1, -1, -1}, nxt = 0;      // reader: layer whose side-stream wgrad still reads the slot
+  explicit WgradSchedule(hipStream_t s_) : s(s_), side(g_wgrad_side && g_wside.init()), sw(side ? g_wside.stream : s_) {}
+  int claim() {   // next slot to write on the caller's stream
+    const int k = nxt; nxt = (nxt + 1) % 3;
+    if (side && reader[k] >= 0) { (void)hipStreamWaitEvent(s, g_wside.done[reader[k]], 0); reader[k] = -1; }
+    return k;
+  }
+  void wgrad_may_start(int ci) {   // `s` has enqueued the output gradient of layer ci
+    if (side) { (void)hipEventRecord(g_wside.ready[ci], s); (void)hipStreamWaitEvent(sw, g_wside.ready[ci], 0); }
+  }
+  void wgrad_enqueued(int ci, int slot) {   // the wgrad of layer ci is on `sw` and reads `slot`
+    if (side) { (void)hipEventRecord(g_wside.done[ci], sw); reader[slot] = ci; }
+  }
+  void finish() {   // `s` owns the results again: every weight gradient is complete behind this wait
+    if (side) (void)hipStreamWaitEvent(s, g_wside.done[0], 0);
+  }
+};
 // host callback after the kernels of one VGG block's backward have been enqueued (data parallel: the caller starts that
 // block's gradient exchange while the blocks below are still being computed)
 umpr_block_callback g_block_cb = nullptr;
@@ -711,82 +745,53 @@ void* umpr_vgg16_wgrad_stream(void) {
 
 int umpr_vgg16_features_bwd(const float* images, const float* const* params, int n, const float* acts,
                             const float* d_pool5, float* const* grads, float* ws, size_t ws_bytes, void* stream) {
-  UMPR_REQUIRE(ws_bytes >= umpr_vgg16_features_bwd_ws_bytes(n), "vgg16_features_bwd: workspace too small");
+  const VggFeatBwdWs W = vgg_feat_bwd_ws(ws, n);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "vgg16_features_bwd: workspace too small");
   const VggLayout L = vgg_layout(n);
   hipStream_t s = S(stream);
-  const size_t big = (size_t)n * 64 * 224 * 224;
-  float* buf[3] = {ws, ws + big, ws + 2 * big};
-  float* wt = buf[2] + big;
-  float* scratch = wt + wt_floats(n);
-  const size_t slab_bytes = vgg_scratch_bytes(n);
-  // The weight gradient of a layer depends only on that layer's output gradient, not on the data-gradient chain that
-  // continues below it: it runs on a side stream, so that its MFMA work fills the HBM-bound phases of the chain
-  // (pool backward, Winograd transforms) on the caller's stream.  The gradient buffers rotate through three slots:
-  // a slot is rewritten two layers after it was produced, behind a wait for the wgrad that read it.
-  const bool side = g_wgrad_side && g_wside.init();
-  hipStream_t sw = side ? g_wside.stream : s;
-  int slot_reader[3] = {-1, -1, -1};   // layer whose side-stream wgrad still reads the slot
-  int nxt = 0;
-  auto claim = [&]() -> float* {       // next slot to write on the caller's stream
-    const int k = nxt; nxt = (nxt + 1) % 3;
-    if (side && slot_reader[k] >= 0) { (void)hipStreamWaitEvent(s, g_wside.done[slot_reader[k]], 0); slot_reader[k] = -1; }
-    return buf[k];
-  };
-  const float* g = d_pool5;
-  int gslot = -1;                      // slot index holding g (-1: the caller's d_pool5)
+  WgradSchedule sched(s);
+  const float* g = d_pool5; int gslot = -1;   // gslot: slot index holding g (-1: the caller's d_pool5)
   int ci = 12;
   for (int b = 4; b >= 0; --b) {
     const int hw = L.conv_hw[ci];
     // pool backward + ReLU mask of the conv output feeding it -> gradient w.r.t. the conv pre-activation
-    float* cur = claim();
-    if (int rc = umpr_maxpool2_bwd_relu_impl(acts + L.conv_off[ci], g, cur, (long)n * kBlockCh[b], hw, hw, s)) return rc;
-    g = cur; gslot = (nxt + 2) % 3;
+    int cs = sched.claim();
+    if (int rc = umpr_maxpool2_bwd_relu_impl(acts + L.conv_off[ci], g, W.slot[cs], (long)n * kBlockCh[b], hw, hw, s)) return rc;
+    g = W.slot[cs]; gslot = cs;
     for (int j = kConvPerBlock[b] - 1; j >= 0; --j, --ci) {
       const int cin = L.conv_cin[ci], cout = L.conv_cout[ci];
       const float* xin = ci == 0 ? images : (j == 0 ? acts + L.pool_off[b - 1] : acts + L.conv_off[ci - 1]);
-      if (side) {
-        (void)hipEventRecord(g_wside.ready[ci], s);
-        (void)hipStreamWaitEvent(sw, g_wside.ready[ci], 0);
-      }
+      sched.wgrad_may_start(ci);
       if (L.v_floats[ci]) umpr_wino_set_v_slot(const_cast<float*>(acts) + L.v_off[ci], L.v_floats[ci]);   // written by the forward
-      const int rcw = umpr_conv3x3_wgrad(g, xin, grads[2 * ci], grads[2 * ci + 1], n, cin, cout, hw, hw, 0, scratch,
-                                         slab_bytes, sw);
+      const int rcw = umpr_conv3x3_wgrad(g, xin, grads[2 * ci], grads[2 * ci + 1], n, cin, cout, hw, hw, 0, W.scratch,
+                                         W.scratch_bytes, sched.sw);
       umpr_wino_set_v_slot(nullptr, 0);
       if (rcw) return rcw;
-      if (side) {
-        (void)hipEventRecord(g_wside.done[ci], sw);
-        slot_reader[gslot] = ci;
-      }
+      sched.wgrad_enqueued(ci, gslot);
       if (ci == 0) break;
       // input came straight from a conv+ReLU (j > 0): mask by it; from a pool (j == 0): the pool backward masks
       const float* mask = j > 0 ? xin : nullptr;
-      cur = claim();
-      if (int rc = umpr_conv3x3_run(g, params[2 * ci], 1, nullptr, mask, cur, n, cin, cout, hw, hw, 0, wt, wt_floats(n), s))
+      cs = sched.claim();
+      if (int rc = umpr_conv3x3_run(g, params[2 * ci], 1, nullptr, mask, W.slot[cs], n, cin, cout, hw, hw, 0, W.wt, W.wt_floats, s))
         return rc;
-      g = cur; gslot = (nxt + 2) % 3;
+      g = W.slot[cs]; gslot = cs;
     }
     if (g_block_cb) g_block_cb(b, g_block_user);   // every weight-gradient kernel of block b is enqueued (on sw)
     if (ci == 0 && b == 0) break;
   }
-  if (side) {  // the caller's stream owns the results again: every weight gradient is complete behind this wait
-    hipEvent_t& last = g_wside.done[0];
-    (void)hipStreamWaitEvent(s, last, 0);
-  }
+  sched.finish();
   return 0;
 }
 
 int umpr_vgg16_bwd(const float* images, const float* const* params, int n, int train, const float* acts,
                    const uint8_t* masks, const float* d_out, float* const* grads, float* ws, size_t ws_bytes,
                    void* stream) {
-  UMPR_REQUIRE(ws_bytes >= umpr_vgg16_ws_bytes(n), "vgg16_bwd: workspace too small (%zu < %zu)", ws_bytes,
-               umpr_vgg16_ws_bytes(n));
-  // d_pool5 lives at the front of the workspace; the stage workspaces follow it
-  float* d_pool5 = ws;
-  float* rest = ws + (size_t)n * 25088;
-  const size_t rest_bytes = ws_bytes - (size_t)n * 25088 * sizeof(float);
-  if (int rc = umpr_vgg16_classifier_bwd(params, n, train, acts, masks, d_out, grads, d_pool5, rest, rest_bytes, stream))
+  const VggBwdWs W = vgg_bwd_ws(ws, n);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "vgg16_bwd: workspace too small (%zu < %zu)", ws_bytes, W.bytes);
+  const size_t rest_bytes = ws_bytes - W.prefix;
+  if (int rc = umpr_vgg16_classifier_bwd(params, n, train, acts, masks, d_out, grads, W.d_pool5, W.stage, rest_bytes, stream))
     return rc;
-  return umpr_vgg16_features_bwd(images, params, n, acts, d_pool5, grads, rest, rest_bytes, stream);
+  return umpr_vgg16_features_bwd(images, params, n, acts, W.d_pool5, grads, W.stage, rest_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ bf16 path
@@ -843,14 +848,23 @@ int b16_pack_all(const VggB16Layout& L, const float* const* params, int transpos
   }
   return umpr_conv_bf16_pack_all(w, cin, cout, width, 12, transposed, wpack, P.off + 1, s);
 }
-size_t b16_wgrad_ws_bytes(int n) {
-  const VggB16Layout L = vgg_b16_layout(n);
+size_t b16_wgrad_ws_bytes(const VggB16Layout& L) {
   size_t m = umpr_conv1_bf16_wgrad_ws_bytes();
   for (int i = 1; i < 13; ++i) {
     const size_t b = umpr_wgrad_bf16_ws_bytes(L.geo[L.conv_block[i]], L.conv_cin[i], L.conv_cout[i]);
     if (b > m) m = b;
   }
   return align_up(m, 1024);
+}
+// Workspace of the bf16 feature backward: [3 rotating gradient slots][packed weights][wgrad slabs]
+struct VggB16BwdWs { char* slot[3]; char* wpack; float* slabs; size_t slab_bytes, bytes; };
+VggB16BwdWs vgg_b16_bwd_ws(void* base, const VggB16Layout& L) {
+  Carve c(base, 1);
+  VggB16BwdWs w;
+  for (int k = 0; k < 3; ++k) w.slot[k] = c.take<char>(align_up(umpr_pf_bytes(L.geo[0], 64), 1024));
+  w.wpack = c.take<char>(b16_pack_bytes());
+  w.slab_bytes = b16_wgrad_ws_bytes(L); w.slabs = reinterpret_cast<float*>(c.take<char>(w.slab_bytes)); w.bytes = c.off;
+  return w;
 }
 inline char* BP(void* p) { return static_cast<char*>(p); }
 inline const char* CBP(const void* p) { return static_cast<const char*>(p); }
@@ -893,11 +907,7 @@ int umpr_maxpool2_bf16_bwd_relu(const void* x, const void* dy, void* dx, int N, 
 size_t umpr_vgg16_bf16_act_bytes(int n_img) { return vgg_b16_layout(n_img).total; }
 // forward scratch: [packed weights]
 size_t umpr_vgg16_bf16_fwd_ws_bytes(int n_img) { (void)n_img; return b16_pack_bytes(); }
-// backward scratch: [3 rotating gradient slots][packed weights][wgrad slabs]
-size_t umpr_vgg16_bf16_bwd_ws_bytes(int n_img) {
-  const size_t slot = align_up(umpr_pf_bytes(umpr_pf(n_img, 224, 224), 64), 1024);
-  return 3 * slot + b16_pack_bytes() + b16_wgrad_ws_bytes(n_img);
-}
+size_t umpr_vgg16_bf16_bwd_ws_bytes(int n_img) { return vgg_b16_bwd_ws(nullptr, vgg_b16_layout(n_img)).bytes; }
 
 // Convolutional stage in bf16 (activations kept in `acts` for the backward pass); pool5 [n][25088] fp32 out, in the
 // NCHW flatten order the classifier's fc1 expects (torchvision: x.flatten(1) of [n][512][7][7]).
@@ -936,67 +946,48 @@ int umpr_vgg16_bf16_features_fwd(const float* images, const float* const* params
 
 int umpr_vgg16_bf16_features_bwd(const float* images, const float* const* params, int n, const void* acts,
                                  const float* d_pool5, float* const* grads, void* ws, size_t ws_bytes, void* stream) {
-  UMPR_REQUIRE(ws_bytes >= umpr_vgg16_bf16_bwd_ws_bytes(n), "vgg16_bf16_features_bwd: workspace too small");
   const VggB16Layout L = vgg_b16_layout(n);
+  const VggB16BwdWs W = vgg_b16_bwd_ws(ws, L);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "vgg16_bf16_features_bwd: workspace too small");
   hipStream_t s = S(stream);
-  const size_t slot = align_up(umpr_pf_bytes(umpr_pf(n, 224, 224), 64), 1024);
-  char* buf[3] = {BP(ws), BP(ws) + slot, BP(ws) + 2 * slot};
-  void* wpack = BP(ws) + 3 * slot;
-  float* slabs = reinterpret_cast<float*>(BP(ws) + 3 * slot + b16_pack_bytes());
-  const size_t slab_bytes = b16_wgrad_ws_bytes(n);
-  // weight gradients on the library's side stream, exactly as in the fp32 path (umpr_vgg16_features_bwd): `ready[ci]`
-  // gates the wgrad of layer ci behind its output gradient, `done[ci]` gates the reuse of that gradient's slot
-  const bool side = g_wgrad_side && g_wside.init();
-  hipStream_t sw = side ? g_wside.stream : s;
-  int slot_reader[3] = {-1, -1, -1};
-  int nxt = 0;
-  auto claim = [&]() -> int {
-    const int k = nxt; nxt = (nxt + 1) % 3;
-    if (side && slot_reader[k] >= 0) { (void)hipStreamWaitEvent(s, g_wside.done[slot_reader[k]], 0); slot_reader[k] = -1; }
-    return k;
-  };
+  char* const* buf = W.slot;
+  WgradSchedule sched(s);   // weight gradients on the library's side stream, exactly as in the fp32 path
   const B16Packs PK = b16_packs();
-  if (int rc = b16_pack_all(L, params, 1, wpack, s)) return rc;
+  if (int rc = b16_pack_all(L, params, 1, W.wpack, s)) return rc;
   // gradient w.r.t. the pooled 7x7 map arrives in fp32 NCHW order from the classifier
-  int gs = claim();
+  int gs = sched.claim();
   if (int rc = umpr_nchw_to_cb8(d_pool5, buf[gs], L.pool_geo[4], 512, s)) return rc;
   int ci = 12;
   for (int b = 4; b >= 0; --b) {
     // pool backward + ReLU mask of the conv output that fed the pool -> gradient w.r.t. that conv's pre-activation
-    int cs = claim();
+    int cs = sched.claim();
     if (int rc = umpr_maxpool2_bf16_bwd_run(CBP(acts) + L.conv_off[ci], buf[gs], buf[cs], L.geo[b], L.pool_geo[b],
                                             kBlockCh[b], s)) return rc;
     gs = cs;
     for (int j = kConvPerBlock[b] - 1; j >= 0; --j, --ci) {
       const int cin = L.conv_cin[ci], cout = L.conv_cout[ci];
-      if (side) {
-        (void)hipEventRecord(g_wside.ready[ci], s);
-        (void)hipStreamWaitEvent(sw, g_wside.ready[ci], 0);
-      }
+      sched.wgrad_may_start(ci);
       if (ci == 0) {
-        if (int rc = umpr_conv1_bf16_wgrad(buf[gs], images, grads[0], grads[1], L.geo[0], 0, slabs, slab_bytes, sw)) return rc;
+        if (int rc = umpr_conv1_bf16_wgrad(buf[gs], images, grads[0], grads[1], L.geo[0], 0, W.slabs, W.slab_bytes, sched.sw)) return rc;
       } else {
         const void* xin = j == 0 ? CBP(acts) + L.pool_off[b - 1] : CBP(acts) + L.conv_off[ci - 1];
-        if (int rc = umpr_wgrad_bf16_run(buf[gs], xin, grads[2 * ci], grads[2 * ci + 1], L.geo[b], cin, cout, 0, slabs,
-                                         slab_bytes, sw)) return rc;
+        if (int rc = umpr_wgrad_bf16_run(buf[gs], xin, grads[2 * ci], grads[2 * ci + 1], L.geo[b], cin, cout, 0, W.slabs,
+                                         W.slab_bytes, sched.sw)) return rc;
       }
-      if (side) {
-        (void)hipEventRecord(g_wside.done[ci], sw);
-        slot_reader[gs] = ci;
-      }
+      sched.wgrad_enqueued(ci, gs);
       if (ci == 0) break;
       const void* xin = j == 0 ? CBP(acts) + L.pool_off[b - 1] : CBP(acts) + L.conv_off[ci - 1];
       // the input came straight from a conv+ReLU (j > 0): mask by it; from a pool (j == 0): the pool backward masks
       const void* mask = j > 0 ? xin : nullptr;
-      cs = claim();
+      cs = sched.claim();
       if (int rc = umpr_conv_bf16_run(buf[gs], nullptr, 1, nullptr, mask, buf[cs], L.geo[b], cin, cout, 0,
-                                      BP(wpack) + PK.off[ci], PK.total - PK.off[ci], s)) return rc;
+                                      W.wpack + PK.off[ci], PK.total - PK.off[ci], s)) return rc;
       gs = cs;
     }
     if (g_block_cb) g_block_cb(b, g_block_user);   // every weight-gradient kernel of block b is enqueued (on sw)
     if (ci == 0 && b == 0) break;
   }
-  if (side) (void)hipStreamWaitEvent(s, g_wside.done[0], 0);   // every weight gradient is complete behind this wait
+  sched.finish();
   return 0;
 }
 

@@ -11,7 +11,6 @@
 
 namespace {
 
-constexpr int D = 128;   // 2 * gru_size
 
 struct ScoreParams {
   const float* T;   // [B][SL][128] = G_i M
@@ -485,52 +484,58 @@ __global__ __launch_bounds__(256) void coattn_bwd_rows_kernel(BwdRowsParams p) {
   }
 }
 
+// forward workspace: per-tile partial maxima of the score matrix and their positions, [B][nblk][SL] each, over the columns
+// (cpart | apart) and over the rows (rpart | arpart); nblk = cdiv(SL, 64) score tiles per side
+struct CoattnFwdWs { float* cpart; int* apart; float* rpart; int* arpart; size_t bytes; };
+CoattnFwdWs coattn_fwd_ws(float* base, int B, int SL) {
+  Carve c(base, sizeof(float));
+  const size_t n = (size_t)B * cdiv(SL, 64) * SL;
+  return CoattnFwdWs{c.take<float>(n), c.take<int>(n), c.take<float>(n), c.take<int>(n), c.off};
+}
+// backward workspace: dSc | dSr [B*SL] | dT [B*SL][128] | split-K slab of the dM product
+struct CoattnBwdWs { float *dSc, *dSr, *dT, *slab; size_t slab_bytes, bytes; };
+CoattnBwdWs coattn_bwd_ws(float* base, int B, int SL) {
+  Carve c(base, sizeof(float));
+  const size_t n = (size_t)B * SL, nslab = (size_t)512 * D * D;
+  return CoattnBwdWs{c.take<float>(n), c.take<float>(n), c.take<float>(n * D), c.take<float>(nslab), nslab * sizeof(float), c.off};
+}
+
 }  // namespace
 
-// workspace floats needed by forward: T [B*SL*128] + colmax_part [B*nblk*SL] + argcol_part (int) [B*nblk*SL]
-size_t umpr_coattn_fwd_ws_bytes(int B, int SL) {
-  const int nblk = cdiv(SL, 64);
-  return ((size_t)B * nblk * SL * 4) * sizeof(float);
-}
+size_t umpr_coattn_fwd_ws_bytes(int B, int SL) { return coattn_fwd_ws(nullptr, B, SL).bytes; }
 
 int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                          float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax, int* argcol,
                          float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores) {
   UMPR_REQUIRE(B > 0 && SL > 0, "coattn: bad shape");
-  UMPR_REQUIRE(ws_bytes >= umpr_coattn_fwd_ws_bytes(B, SL), "coattn: workspace too small");
+  const CoattnFwdWs W = coattn_fwd_ws(ws, B, SL);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "coattn: workspace too small");
   const int nblk = cdiv(SL, 64);
   UmprGemm g;
   g.A = Gi; g.lda = D; g.B = M; g.ldb = D; g.C = T; g.ldc = D; g.M = B * SL; g.N = D; g.K = D;
   if (int rc = umpr_gemm(g, s)) return rc;
   // one 64 x 64 score tile per workgroup: nblk^2 * B workgroups instead of nblk * B serial tile loops
   const int ksplit = nblk;
-  float* cpart = ws;
-  int* apart = reinterpret_cast<int*>(ws + (size_t)B * nblk * SL);
-  float* rpart = ws + (size_t)2 * B * nblk * SL;
-  int* arpart = reinterpret_cast<int*>(ws + (size_t)3 * B * nblk * SL);
-  ScoreParams sp{T, Gu, rpart, arpart, cpart, apart, SL, nblk, ksplit};
+  ScoreParams sp{T, Gu, W.rpart, W.arpart, W.cpart, W.apart, SL, nblk, ksplit};
   if (bf16_scores) coattn_scores_bf16_kernel<<<dim3(nblk, B, ksplit), 256, 0, s>>>(sp);
   else coattn_scores_kernel<<<dim3(nblk, B, ksplit), 256, 0, s>>>(sp);
   UMPR_LAUNCH_CHECK("coattn_scores");
-  FinishParams fp{Gu, Gi, cpart, apart, nblk, rpart, arpart, ksplit, rowmax, argrow, colmax, argcol, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, SL};
+  FinishParams fp{Gu, Gi, W.cpart, W.apart, nblk, W.rpart, W.arpart, ksplit, rowmax, argrow, colmax, argcol, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, SL};
   coattn_finish_kernel<<<dim3(B, 2), 1024, SL * sizeof(float), s>>>(fp);
   UMPR_LAUNCH_CHECK("coattn_finish");
   return 0;
 }
 
-// backward: needs dSc,dSr [B*SL] each + dT [B*SL*128] in ws; split-K slab for dM after that
-size_t umpr_coattn_bwd_ws_bytes(int B, int SL) {
-  return ((size_t)B * SL * 2 + (size_t)B * SL * D + (size_t)512 * D * D) * sizeof(float);
-}
+size_t umpr_coattn_bwd_ws_bytes(int B, int SL) { return coattn_bwd_ws(nullptr, B, SL).bytes; }
 
 int umpr_coattn_bwd_impl(const float* Gu, const float* Gi, const float* M, const float* T, const float* soft_u,
                          const float* soft_i, const float* colmax, const int* argcol, const float* rowmax,
                          const int* argrow, const float* d_atte_u, long ld_du, const float* d_atte_i, long ld_di,
                          const float* d_soft_u, const float* d_soft_i, int B, int SL, float* dGu, float* dGi, float* dM,
                          int accumulate, float* ws, size_t ws_bytes, hipStream_t s) {
-  UMPR_REQUIRE(ws_bytes >= umpr_coattn_bwd_ws_bytes(B, SL), "coattn_bwd: workspace too small");
-  float* dSc = ws; float* dSr = ws + (size_t)B * SL; float* dT = dSr + (size_t)B * SL;
-  float* slab = dT + (size_t)B * SL * D;
+  const CoattnBwdWs W = coattn_bwd_ws(ws, B, SL);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "coattn_bwd: workspace too small");
+  float *dSc = W.dSc, *dSr = W.dSr, *dT = W.dT;
   BwdPrepParams pp{Gu, Gi, d_atte_u, ld_du, d_atte_i, ld_di, d_soft_u, d_soft_i, soft_u, soft_i, colmax, rowmax, dSc, dSr, SL};
   coattn_bwd_prep_kernel<<<dim3(B, 2), 1024, SL * sizeof(float), s>>>(pp);
   UMPR_LAUNCH_CHECK("coattn_bwd_prep");
@@ -545,6 +550,6 @@ int umpr_coattn_bwd_impl(const float* Gu, const float* Gi, const float* M, const
   // dM = G_i^T dT   (K = B*SL, split-K)
   UmprGemm h;
   h.A = Gi; h.lda = D; h.transA = true; h.B = dT; h.ldb = D; h.C = dM; h.ldc = D; h.M = D; h.N = D; h.K = B * SL;
-  h.split_k = 0; h.ws = slab; h.ws_bytes = (size_t)512 * D * D * sizeof(float);
+  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes;
   return umpr_gemm(h, s);
 }

@@ -14,9 +14,6 @@
 
 namespace {
 
-constexpr int H = 64;      // hidden size (config.gru_size)
-constexpr int G3 = 192;    // 3*H
-
 struct GruFwdParams {
   const float* gx;       // [N][L][384] = W_ih x + b_ih for (fwd | reverse)
   const float* whh[2];   // [192][64]

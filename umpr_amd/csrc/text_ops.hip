@@ -7,8 +7,6 @@
 
 namespace {
 
-constexpr int D = 128;  // 2u
-constexpr int AT = 64;  // self_atte_size
 
 __device__ float block_sum4(float v, float* red) {
   v = wave_sum(v);
@@ -961,18 +959,25 @@ int umpr_snet_fwd_impl(const float* X, const float* Ms, const float* Ws, const f
   return 0;
 }
 
-size_t umpr_snet_bwd_ws_bytes_impl(int B, int S, int L) {
-  return ((size_t)B * S * L * AT + ((size_t)B * S + 3) / 4 * AT + (size_t)512 * AT * D) * sizeof(float);
+// S-Net backward workspace: dPre [B*S*L][64] | partial sums of dWs, one row per workgroup of four sentences | split-K slab of dMs
+struct SnetBwdWs { float *dPre, *dWs_part, *slab; size_t slab_bytes, bytes; };
+static SnetBwdWs snet_bwd_ws(float* base, int B, int S, int L) {
+  Carve c(base, sizeof(float));
+  SnetBwdWs w{c.take<float>((size_t)B * S * L * AT), c.take<float>(((size_t)B * S + 3) / 4 * AT), c.take<float>((size_t)512 * AT * D),
+              (size_t)512 * AT * D * sizeof(float), c.off};
+  return w;
 }
+size_t umpr_snet_bwd_ws_bytes_impl(int B, int S, int L) { return snet_bwd_ws(nullptr, B, S, L).bytes; }
 
 int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const float* U, const float* P,
                        const float* wsum, const float* self_atte, const float* d_senti, long ld_ds,
                        const float* d_self_atte, int B, int S, int L, int wl, float* dX, float* dMs, float* dWs,
                        float* d_word_soft, float* ws, size_t ws_bytes, hipStream_t s) {
-  UMPR_REQUIRE(ws_bytes >= umpr_snet_bwd_ws_bytes_impl(B, S, L), "snet_bwd: workspace too small");
+  const SnetBwdWs W = snet_bwd_ws(ws, B, S, L);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "snet_bwd: workspace too small");
   const long nsent = (long)B * S;
   const int nwg = (int)((nsent + 3) / 4);
-  float* dPre = ws; float* dWs_part = ws + (size_t)B * S * L * AT; float* slab = dWs_part + (size_t)nwg * AT;
+  float *dPre = W.dPre, *dWs_part = W.dWs_part;
   SnetBwdParams p{X, U, Ws, P, wsum, self_atte, d_senti, ld_ds, d_self_atte, dX, dPre, dWs_part, d_word_soft, wl, S, L};
   if (L <= 64) snet_pool_bwd_kernel<1><<<nwg, 256, 0, s>>>(p, nsent);
   else if (L <= 128) snet_pool_bwd_kernel<2><<<nwg, 256, 0, s>>>(p, nsent);
@@ -984,7 +989,7 @@ int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const f
   if (int rc = umpr_gemm(g, s)) return rc;
   UmprGemm h;  // dMs = dPre^T X
   h.A = dPre; h.lda = AT; h.transA = true; h.B = X; h.ldb = D; h.C = dMs; h.ldc = D; h.M = AT; h.N = D; h.K = R;
-  h.split_k = 0; h.ws = slab; h.ws_bytes = (size_t)512 * AT * D * sizeof(float);
+  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes;
   if (int rc = umpr_gemm(h, s)) return rc;
   colsum_stage2_kernel<<<1, 1024, 0, s>>>(dWs_part, nwg, AT, dWs, 0);
   UMPR_LAUNCH_CHECK("snet_dWs");
@@ -1021,12 +1026,17 @@ int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, co
   return 0;
 }
 
-size_t umpr_cnet_bwd_ws_bytes(int B, int S, int L, int KC, int KS, int V) {
-  const size_t R = (size_t)B * S * L;
-  // dY + dWp + Wq (window-ordered weight gradient / transposed weight) + head partials + split-K slab
-  return (R * KC + 2 * (size_t)KC * D * KS + (size_t)B * V * KC + (size_t)B * V + (size_t)cdiv(R, 256) * KC +
-          (size_t)512 * KC * D * KS) * sizeof(float);
+// C-Net head backward workspace: dY [R][KC], R = B*S*L | dWp [KC][KS*D] window-ordered weight gradient | Wq [KS*KC][D] transposed
+// weight | per-sample partial sums of the head's gradients [B][V*KC], [B][V] | column-sum partials of dY | split-K slab of dWp
+struct CnetBwdWs { float *dY, *dWp, *Wq, *dWl_part, *dbl_part, *cs, *slab; size_t cs_bytes, slab_bytes, bytes; };
+static CnetBwdWs cnet_bwd_ws(float* base, int B, int S, int L, int KC, int KS, int V) {
+  Carve c(base, sizeof(float));
+  const size_t R = (size_t)B * S * L, CK = (size_t)D * KS, ncs = (size_t)cdiv(R, 256) * KC, nslab = (size_t)512 * KC * CK;
+  CnetBwdWs w{c.take<float>(R * KC), c.take<float>(KC * CK), c.take<float>(KC * CK), c.take<float>((size_t)B * V * KC),
+              c.take<float>((size_t)B * V), c.take<float>(ncs), c.take<float>(nslab), ncs * sizeof(float), nslab * sizeof(float), c.off};
+  return w;
 }
+size_t umpr_cnet_bwd_ws_bytes(int B, int S, int L, int KC, int KS, int V) { return cnet_bwd_ws(nullptr, B, S, L, KC, KS, V).bytes; }
 
 int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, const float* cmax, const int* argl,
                             const float* sp, const float* view_p, const float* d_final, const float* d_view_p, int B,
@@ -1037,16 +1047,11 @@ int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, co
   const size_t head_lds = ((size_t)4 * V * KC + (size_t)8 * V) * sizeof(float);   // cnet_head_bwd_kernel: dW[4][V*KC], db[4][V], dsig[4][V]
   UMPR_REQUIRE(V >= 1 && head_lds <= 65536, "cnet_bwd: V = %d views x KC = %d filters need %zu bytes of LDS, above the 65536 a kernel may request",
                V, KC, head_lds);
-  UMPR_REQUIRE(ws_bytes >= umpr_cnet_bwd_ws_bytes(B, S, L, KC, KS, V), "cnet_bwd: workspace too small");
+  const CnetBwdWs W = cnet_bwd_ws(ws, B, S, L, KC, KS, V);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "cnet_bwd: workspace too small");
   const long R = (long)B * S * L;
   const int CK = D * KS;
-  float* dY = ws;
-  float* dWp = dY + R * KC;                              // [KC][CK] in window order
-  float* Wq = dWp + (size_t)KC * CK;                     // [KS*KC][D]
-  float* dWl_part = Wq + (size_t)KC * CK;
-  float* dbl_part = dWl_part + (size_t)B * V * KC;
-  float* cs = dbl_part + (size_t)B * V;
-  float* slab = cs + (size_t)cdiv(R, 256) * KC;
+  float *dY = W.dY, *dWp = W.dWp, *Wq = W.Wq, *dWl_part = W.dWl_part, *dbl_part = W.dbl_part;
   if (hipMemsetAsync(dY, 0, (size_t)R * KC * sizeof(float), s) != hipSuccess) { umpr_set_error("cnet_bwd: memset"); return -2; }
   CnetHeadBwdParams p{cmax, argl, sp, view_p, Wl, d_final, d_view_p, dY, dWl_part, dbl_part, S, L, KC, V};
   cnet_head_bwd_kernel<<<B, 256, head_lds, s>>>(p);
@@ -1054,12 +1059,12 @@ int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, co
   colsum_stage2_kernel<<<cdiv(V * KC, 64), 256, 0, s>>>(dWl_part, B, V * KC, dWl, accumulate_w);
   colsum_stage2_kernel<<<cdiv(V, 64), 256, 0, s>>>(dbl_part, B, V, dbl, accumulate_w);
   UMPR_LAUNCH_CHECK("cnet_dWl");
-  if (int rc = umpr_colsum(dY, R, KC, KC, dbc, accumulate_w, cs, (size_t)cdiv(R, 256) * KC * sizeof(float), s)) return rc;
+  if (int rc = umpr_colsum(dY, R, KC, KC, dbc, accumulate_w, W.cs, W.cs_bytes, s)) return rc;
   const int pad = (KS - 1) / 2;
   UmprGemm h;  // dWp[KC][CK] = dY^T win(X)
   h.A = dY; h.lda = KC; h.transA = true; h.B = X; h.ldb = D; h.winB_L = L; h.winB_D = D; h.winB_pad = pad;
   h.C = dWp; h.ldc = CK; h.M = KC; h.N = CK; h.K = (int)R;
-  h.split_k = 0; h.ws = slab; h.ws_bytes = (size_t)512 * KC * CK * sizeof(float);
+  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes;
   if (int rc = umpr_gemm(h, s)) return rc;
   cnet_weight_order_kernel<<<nblocks((long)KC * CK), 256, 0, s>>>(dWp, dWc, KC, D, KS, 2, accumulate_w);
   cnet_weight_order_kernel<<<nblocks((long)KC * CK), 256, 0, s>>>(Wc, Wq, KC, D, KS, 1, 0);
@@ -1081,12 +1086,15 @@ int umpr_gate_fwd_impl(const float* sa, const float* w, const float* bias, const
   UMPR_LAUNCH_CHECK("gate_fwd");
   return 0;
 }
-size_t umpr_gate_bwd_ws_bytes(int B) { return (size_t)B * (D + 1) * sizeof(float); }
+struct GateBwdWs { float *dw_part, *db_part; size_t bytes; };   // per-sample partial sums of dw [B][128] | of db [B]
+static GateBwdWs gate_bwd_ws(float* base, int B) { Carve c(base, sizeof(float)); return GateBwdWs{c.take<float>((size_t)B * D), c.take<float>(B), c.off}; }
+size_t umpr_gate_bwd_ws_bytes(int B) { return gate_bwd_ws(nullptr, B).bytes; }
 int umpr_gate_bwd_impl(const float* sa, const float* w, const float* view_p, const float* c_out, const float* senti,
                        const float* vs, const float* d_pp, const float* d_pn, int B, int S, int V, float* d_sa,
                        float* d_view_p, float* d_c_out, float* dw, float* db, float* ws, size_t ws_bytes, hipStream_t s) {
-  UMPR_REQUIRE(ws_bytes >= umpr_gate_bwd_ws_bytes(B), "gate_bwd: workspace too small");
-  float* dw_part = ws; float* db_part = ws + (size_t)B * D;
+  const GateBwdWs W = gate_bwd_ws(ws, B);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "gate_bwd: workspace too small");
+  float *dw_part = W.dw_part, *db_part = W.db_part;
   GateBwdParams p{sa, w, view_p, c_out, senti, vs, d_pp, d_pn, d_sa, d_view_p, d_c_out, dw_part, db_part, S, V};
   gate_bwd_kernel<<<B, 64, (2 * V + S) * sizeof(float), s>>>(p);
   UMPR_LAUNCH_CHECK("gate_bwd");

@@ -5,29 +5,15 @@
 // allocations and an autograd node each) needs longer than that to enqueue them; here the stages are issued back to back from
 // C++ into ONE caller-owned arena (everything the backward pass reads) and one scratch buffer.  The stage functions are the
 // per-stage entry points of api.hip, unchanged: these wrappers only carve buffers and call them in order.
+#include <algorithm>
+
 #include "umpr_common.h"
 #include "umpr_internal.h"
 #include "../../include/umpr_hip.h"
 
 namespace {
 
-constexpr int D = 128, H = 64, AT = 64;
-
-struct Carve {   // hands out 256-byte aligned pieces of one buffer; with base == nullptr it only measures
-  char* base; size_t off = 0;
-  explicit Carve(void* b) : base(static_cast<char*>(b)) {}
-  template <typename T> T* take(size_t n) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += (n * sizeof(T) + 255) / 256 * 256;
-    return p;
-  }
-};
-
-struct B16Scope {   // the text path's GEMM-shaped products on the bf16 pipe while alive (per host thread)
-  int on;
-  explicit B16Scope(int o) : on(o) { if (on) umpr_gemm_set_b16(1); }
-  ~B16Scope() { if (on) umpr_gemm_set_b16(0); }
-};
+constexpr size_t kAlign = 256;   // every piece of an arena or of a workspace prefix starts on a 256-byte boundary
 
 struct SnetSaved { float *U, *P, *wsum, *sa; };
 SnetSaved take_snet(Carve& c, long B, long S, long L) {
@@ -44,7 +30,7 @@ struct ReviewArena {
   size_t bytes;
 };
 ReviewArena review_arena(void* base, long B, long S, long L) {
-  Carve c(base);
+  Carve c(base, kAlign);
   const long N = B * S, SL = S * L;
   ReviewArena a;
   a.gru_out = c.take<float>(2 * N * L * D);
@@ -60,8 +46,6 @@ ReviewArena review_arena(void* base, long B, long S, long L) {
   return a;
 }
 
-size_t max2(size_t a, size_t b) { return a > b ? a : b; }
-
 // ---- ControlNet arena ---------------------------------------------------------------------------------------------
 struct HeadSaved { float *cmax, *sp, *vp, *fin; int32_t* argl; };
 struct ControlArena {
@@ -71,7 +55,7 @@ struct ControlArena {
   size_t bytes;
 };
 ControlArena control_arena(void* base, long B, long S_ui, long L_ui, long S, long L, long KC, long V) {
-  Carve c(base);
+  Carve c(base, kAlign);
   const long Nui = B * S_ui, N = B * S;
   ControlArena a;
   a.gru_ui = c.take<float>(Nui * L_ui * D);
@@ -87,6 +71,44 @@ ControlArena control_arena(void* base, long B, long S_ui, long L_ui, long S, lon
   a.senti = c.take<float>(B * S_ui); a.vs = c.take<float>(B * V);
   a.bytes = c.off;
   return a;
+}
+
+// ---- workspaces: [the buffers that live across stages][the stage workspace: the largest any stage asks for, + 256] ------
+// umpr_review_net_bwd (the forward hands the whole buffer to its stages); dG is also the GRUs' dout
+struct ReviewWs { float *dG, *d_repr_u, *d_repr_i, *ds_u, *ds_i, *stage; size_t prefix, bytes; };
+ReviewWs review_ws(void* base, int B, int S, int L, int E) {
+  Carve c(base, kAlign);
+  const long N = (long)B * S, SL = (long)S * L;
+  ReviewWs w;
+  w.dG = c.take<float>(2 * N * L * D);
+  w.d_repr_u = c.take<float>(B * 2 * D); w.d_repr_i = c.take<float>(B * 2 * D);
+  w.ds_u = c.take<float>(B * SL); w.ds_i = c.take<float>(B * SL);
+  w.stage = c.at<float>(c.off); w.prefix = c.off;
+  w.bytes = c.off + 256 + std::max({umpr_embed_gru_bidir_ws_bytes((int)(2 * N), L, E), umpr_coattention_fwd_ws_bytes(B, (int)SL),
+                                    umpr_coattention_bwd_ws_bytes(B, (int)SL), umpr_snet_bwd_ws_bytes(B, S, L),
+                                    umpr_review_merge_bwd_ws_bytes(B)});
+  return w;
+}
+struct ControlWs {
+  float *dX_ui, *dX_pair, *d_sa, *d_vp, *d_cout;   // dX_*: the two GRUs' dout
+  float* zero_senti;   // zero d_senti of the control S-Net (its sentiment output is unused, model.py:185)
+  float* Y;            // forward scratch: Y of a C-Net head, then - on purpose - the control S-Net's unused sentiment output
+  float* stage; size_t prefix, bytes;
+};
+ControlWs control_ws(void* base, int B, int S_ui, int L_ui, int S, int L, int E, int KC, int KS, int V) {
+  Carve c(base, kAlign);
+  const long Nui = (long)B * S_ui, N = (long)B * S;
+  ControlWs w;
+  w.dX_ui = c.take<float>(Nui * L_ui * D); w.dX_pair = c.take<float>(2 * N * L * D);
+  w.d_sa = c.take<float>(B * S_ui * D); w.d_vp = c.take<float>(B * S_ui * V); w.d_cout = c.take<float>(B * V);
+  w.zero_senti = c.take<float>(B * D);
+  w.Y = c.take<float>((long)B * (S_ui > S ? S_ui : S) * (L_ui > L ? L_ui : L) * KC);
+  w.stage = c.at<float>(c.off); w.prefix = c.off;
+  w.bytes = c.off + 256 + std::max({umpr_embed_gru_bidir_ws_bytes((int)(2 * N), L, E), umpr_embed_gru_bidir_ws_bytes((int)Nui, L_ui, E),
+                                    umpr_cnet_head_fwd_ws_bytes(B, S_ui, L_ui, KS), umpr_cnet_head_fwd_ws_bytes(B, S, L, KS),
+                                    umpr_cnet_head_bwd_ws_bytes(B, S_ui, L_ui, KC, KS, V), umpr_cnet_head_bwd_ws_bytes(B, S, L, KC, KS, V),
+                                    umpr_snet_bwd_ws_bytes(B, S_ui, L_ui), umpr_control_gate_bwd_ws_bytes(B)});
+  return w;
 }
 
 // UMPR_POISON_WS=1 (debugging aid): every entry point below first fills its workspace - and the forward ones their arena - with
@@ -123,19 +145,7 @@ int umpr_concat_ids(const int64_t* ids_u, const int64_t* ids_i, long n_each, int
 
 // ------------------------------------------------------------------------------------------------------ ReviewNet
 size_t umpr_review_net_arena_bytes(int B, int S, int L) { return review_arena(nullptr, B, S, L).bytes; }
-size_t umpr_review_net_ws_bytes(int B, int S, int L, int E) {
-  const long N = (long)B * S, SL = (long)S * L;
-  Carve c(nullptr);
-  c.take<float>(2 * N * L * D);   // dG (also the GRUs' dout)
-  c.take<float>(B * 2 * D); c.take<float>(B * 2 * D);   // d_repr_u, d_repr_i
-  c.take<float>(B * SL); c.take<float>(B * SL);         // d_soft_u, d_soft_i
-  size_t stage = umpr_embed_gru_bidir_ws_bytes((int)(2 * N), L, E);
-  stage = max2(stage, umpr_coattention_fwd_ws_bytes(B, (int)SL));
-  stage = max2(stage, umpr_coattention_bwd_ws_bytes(B, (int)SL));
-  stage = max2(stage, umpr_snet_bwd_ws_bytes(B, S, L));
-  stage = max2(stage, umpr_review_merge_bwd_ws_bytes(B));
-  return c.off + stage + 256;
-}
+size_t umpr_review_net_ws_bytes(int B, int S, int L, int E) { return review_ws(nullptr, B, S, L, E).bytes; }
 
 // params: w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, M, Ms_u, Ws_u, Ms_i, Ws_i, W_u, W_i
 int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
@@ -146,7 +156,7 @@ int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const 
   if (poison(ws, ws_bytes, stream) || poison(arena, umpr_review_net_arena_bytes(B, S, L), stream)) return -2;
   const ReviewArena A = review_arena(arena, B, S, L);
   const int N = B * S, SL = S * L;
-  B16Scope b16(b16_gemm);
+  UmprB16Scope b16(b16_gemm);
   if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], lengths, order, order,
                                         2 * N, L, A.gru_out, need_grad ? A.gru_saved : nullptr, ws, ws_bytes, stream)) return rc;
   const float* gru_u = A.gru_out;
@@ -156,8 +166,7 @@ int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const 
                                                                          A.argrow, ws, ws_bytes, stream)) return rc;
   if (int rc = umpr_snet_fwd(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D, 2 * D, stream)) return rc;
   if (int rc = umpr_snet_fwd(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D, 2 * D, stream)) return rc;
-  static const bool merge_small = umpr_env_on("UMPR_MERGE_SMALL");
-  if (B <= 256 && merge_small)   // one kernel writes the caller's tensor and the arena's copy for backward
+  if (B <= 256 && umpr_merge_small())   // one kernel writes the caller's tensor and the arena's copy for backward
     return umpr_review_merge_fwd_impl(A.repr_u, A.repr_i, P[13], P[14], B, out, A.merged, static_cast<hipStream_t>(stream));
   if (int rc = umpr_review_merge_fwd(A.repr_u, A.repr_i, P[13], P[14], B, A.merged, stream)) return rc;
   if (hipMemcpyAsync(out, A.merged, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) != hipSuccess) {
@@ -172,23 +181,18 @@ int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const 
                         const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
                         float* const* G, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(ids_pair && emb && P && G && lengths && order && arena && d_out, "review_net_bwd: bad arguments");
-  UMPR_REQUIRE(ws_bytes >= umpr_review_net_ws_bytes(B, S, L, E), "review_net_bwd: workspace too small");
+  const ReviewWs W = review_ws(ws, B, S, L, E);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "review_net_bwd: workspace too small");
   if (poison(ws, ws_bytes, stream)) return -2;
   const ReviewArena A = review_arena(const_cast<void*>(arena), B, S, L);
   const long N = (long)B * S, SL = (long)S * L;
-  Carve c(ws);
-  float* dG = c.take<float>(2 * N * L * D);
-  float* d_repr_u = c.take<float>(B * 2 * D);
-  float* d_repr_i = c.take<float>(B * 2 * D);
-  float* ds_u = c.take<float>(B * SL);
-  float* ds_i = c.take<float>(B * SL);
-  float* sws = reinterpret_cast<float*>(static_cast<char*>(static_cast<void*>(ws)) + c.off);
-  const size_t swsb = ws_bytes - c.off;
+  float *dG = W.dG, *d_repr_u = W.d_repr_u, *d_repr_i = W.d_repr_i, *ds_u = W.ds_u, *ds_i = W.ds_i;
+  float* sws = W.stage; const size_t swsb = ws_bytes - W.prefix;
   const float* gru_u = A.gru_out;
   const float* gru_i = A.gru_out + (size_t)N * L * D;
   float* dGu = dG;
   float* dGi = dG + (size_t)N * L * D;
-  B16Scope b16(b16_gemm);
+  UmprB16Scope b16(b16_gemm);
   debug_sync(0);
   if (int rc = umpr_review_merge_bwd(A.repr_u, A.repr_i, P[13], P[14], A.merged, d_out, B, d_repr_u, d_repr_i, G[13], G[14], sws, swsb, stream)) return rc;
   debug_sync(1);
@@ -210,23 +214,7 @@ size_t umpr_control_net_arena_bytes(int B, int S_ui, int L_ui, int S, int L, int
   return control_arena(nullptr, B, S_ui, L_ui, S, L, KC, V).bytes;
 }
 size_t umpr_control_net_ws_bytes(int B, int S_ui, int L_ui, int S, int L, int E, int KC, int KS, int V) {
-  const long Nui = (long)B * S_ui, N = (long)B * S;
-  Carve c(nullptr);
-  c.take<float>(Nui * L_ui * D);     // dX_ui (the ui GRU's dout)
-  c.take<float>(2 * N * L * D);      // dX_u, dX_i (the pair GRU's dout)
-  c.take<float>(B * S_ui * D);       // d_self_atte
-  c.take<float>(B * S_ui * V);       // d_view_p
-  c.take<float>(B * V);              // d_c_out
-  c.take<float>(B * D);              // zero d_senti of the control S-Net (its sentiment output is unused, model.py:185)
-  c.take<float>((long)B * (S_ui > S ? S_ui : S) * (L_ui > L ? L_ui : L) * KC);   // Y of a C-Net head (forward scratch)
-  size_t stage = max2(umpr_embed_gru_bidir_ws_bytes((int)(2 * N), L, E), umpr_embed_gru_bidir_ws_bytes((int)Nui, L_ui, E));
-  stage = max2(stage, umpr_cnet_head_fwd_ws_bytes(B, S_ui, L_ui, KS));
-  stage = max2(stage, umpr_cnet_head_fwd_ws_bytes(B, S, L, KS));
-  stage = max2(stage, umpr_cnet_head_bwd_ws_bytes(B, S_ui, L_ui, KC, KS, V));
-  stage = max2(stage, umpr_cnet_head_bwd_ws_bytes(B, S, L, KC, KS, V));
-  stage = max2(stage, umpr_snet_bwd_ws_bytes(B, S_ui, L_ui));
-  stage = max2(stage, umpr_control_gate_bwd_ws_bytes(B));
-  return c.off + stage + 256;
+  return control_ws(nullptr, B, S_ui, L_ui, S, L, E, KC, KS, V).bytes;
 }
 
 // params: the C-Net GRU's eight (as above), Wc [KC][128][KS], bc, Wl [V][KC], bl, Ms, Ws, ssW [128], ssb [1]
@@ -235,20 +223,19 @@ int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
                          int S_ui, int L_ui, int S, int L, int KC, int KS, int V, float thr, int b16_gemm, int need_grad, void* arena,
                          float* c_u, float* c_i, float* prefer_pos, float* prefer_neg, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(ids_ui && ids_pair && emb && P && arena && c_u && c_i && prefer_pos && prefer_neg, "control_net_fwd: bad arguments");
-  UMPR_REQUIRE(ws_bytes >= umpr_control_net_ws_bytes(B, S_ui, L_ui, S, L, E, KC, KS, V), "control_net_fwd: workspace too small");
+  const ControlWs W = control_ws(ws, B, S_ui, L_ui, S, L, E, KC, KS, V);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "control_net_fwd: workspace too small");
   if (poison(ws, ws_bytes, stream) || poison(arena, umpr_control_net_arena_bytes(B, S_ui, L_ui, S, L, KC, V), stream)) return -2;
   const ControlArena A = control_arena(arena, B, S_ui, L_ui, S, L, KC, V);
   const long Nui = (long)B * S_ui, N = (long)B * S;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  B16Scope b16(b16_gemm);
+  UmprB16Scope b16(b16_gemm);
   if (int rc = umpr_embed_gru_bidir_fwd(ids_ui, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_ui, ord_ui, ord_ui, (int)Nui,
                                         L_ui, A.gru_ui, need_grad ? A.saved_ui : nullptr, ws, ws_bytes, stream)) return rc;
   if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_pair, ord_pair, ord_pair,
                                         (int)(2 * N), L, A.gru_pair, need_grad ? A.saved_pair : nullptr, ws, ws_bytes, stream)) return rc;
-  Carve c(ws);
-  float* Y = c.take<float>((long)B * (S_ui > S ? S_ui : S) * (L_ui > L ? L_ui : L) * KC);
-  float* sws = reinterpret_cast<float*>(static_cast<char*>(static_cast<void*>(ws)) + c.off);
-  const size_t swsb = ws_bytes - c.off;
+  float* Y = W.Y;   // (the GRUs above used the whole buffer)
+  float* sws = W.stage; const size_t swsb = ws_bytes - W.prefix;
   const float* X[3] = {A.gru_ui, A.gru_pair, A.gru_pair + (size_t)N * L * D};
   const int ss[3] = {S_ui, S, S}, ll[3] = {L_ui, L, L};
   for (int q = 0; q < 3; ++q)
@@ -272,21 +259,15 @@ int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
                          const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* ws, size_t ws_bytes,
                          void* stream) {
   UMPR_REQUIRE(ids_ui && ids_pair && emb && P && G && arena && d_cu && d_ci && d_pp && d_pn, "control_net_bwd: bad arguments");
-  UMPR_REQUIRE(ws_bytes >= umpr_control_net_ws_bytes(B, S_ui, L_ui, S, L, E, KC, KS, V), "control_net_bwd: workspace too small");
+  const ControlWs W = control_ws(ws, B, S_ui, L_ui, S, L, E, KC, KS, V);
+  UMPR_REQUIRE(ws_bytes >= W.bytes, "control_net_bwd: workspace too small");
   if (poison(ws, ws_bytes, stream)) return -2;
   const ControlArena A = control_arena(const_cast<void*>(arena), B, S_ui, L_ui, S, L, KC, V);
   const long Nui = (long)B * S_ui, N = (long)B * S;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  Carve c(ws);
-  float* dX_ui = c.take<float>(Nui * L_ui * D);
-  float* dX_pair = c.take<float>(2 * N * L * D);
-  float* d_sa = c.take<float>(B * S_ui * D);
-  float* d_vp = c.take<float>(B * S_ui * V);
-  float* d_cout = c.take<float>(B * V);
-  float* zero_senti = c.take<float>(B * D);
-  float* sws = reinterpret_cast<float*>(static_cast<char*>(static_cast<void*>(ws)) + c.off);
-  const size_t swsb = ws_bytes - c.off;
-  B16Scope b16(b16_gemm);
+  float *dX_ui = W.dX_ui, *dX_pair = W.dX_pair, *d_sa = W.d_sa, *d_vp = W.d_vp, *d_cout = W.d_cout, *zero_senti = W.zero_senti;
+  float* sws = W.stage; const size_t swsb = ws_bytes - W.prefix;
+  UmprB16Scope b16(b16_gemm);
   if (hipMemsetAsync(zero_senti, 0, (size_t)B * D * sizeof(float), s) != hipSuccess) { umpr_set_error("control_net_bwd: memset"); return -2; }
   if (int rc = umpr_control_gate_bwd(A.sn.sa, P[14], A.h[0].vp, A.h[0].fin, A.senti, A.vs, d_pp, d_pn, B, S_ui, V, d_sa, d_vp, d_cout,
                                      G[14], G[15], sws, swsb, stream)) return rc;

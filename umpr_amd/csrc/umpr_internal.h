@@ -23,6 +23,24 @@ struct UmprGemm {
 void umpr_gemm_set_b16(int on);
 int umpr_gemm_b16();             // the calling host thread's current setting
 int umpr_gemm(const UmprGemm& g, hipStream_t stream);
+// The generic GEMM's products on the bf16 pipe while alive, where `on`; the host thread's own setting is restored on exit.
+struct UmprB16Scope {
+  int prev;
+  explicit UmprB16Scope(int on) : prev(umpr_gemm_b16()) { if (on) umpr_gemm_set_b16(1); }
+  ~UmprB16Scope() { umpr_gemm_set_b16(prev); }
+};
+
+constexpr int D = 128, H = 64, G3 = 192, AT = 64;   // text path: token feature 2 * gru_size, gru_size, its 3 gates, self_atte_size
+bool umpr_merge_small();   // UMPR_MERGE_SMALL=0: the review merge on the fc kernels / the generic GEMM (api.hip)
+
+// Workspaces: ONE function (base, shape...) -> layout describes a scratch buffer; its size entry point returns
+// layout(nullptr, ...).bytes and its user reads the pointers of layout(ws, ...), so the two cannot disagree.
+struct Carve {   // hands out pieces of one buffer, each rounded up to `align` bytes; with base == nullptr it only measures
+  char* base; size_t align, off = 0;
+  Carve(void* b, size_t a) : base(static_cast<char*>(b)), align(a) {}
+  template <typename T> T* at(size_t o) const { return base ? reinterpret_cast<T*>(base + o) : nullptr; }
+  template <typename T> T* take(size_t n) { T* p = at<T>(off); off += (n * sizeof(T) + align - 1) / align * align; return p; }
+};
 
 // fc_small.hip - batch-sized fully connected layers (register-streaming fp32 MFMA, no LDS)
 bool umpr_fc_small_ok(int M, int N, int K);

@@ -893,21 +893,30 @@ static inline bool wino_f4_map(int H, int W, int transposed) {
   return umpr_wino_f4_mode() >= need && wino_f4_shape(H, W);
 }
 
-// workspace: U [P][MT*128][S*32] + V [P][S*32][Tpad] + M [P][MT*128][Tpad]  (floats);  P = 16 planes over 2x2 tiles, or
-// 36 planes over 4x4 tiles where the map allows F(4x4,3x3)
+// Geometry and workspace of one Winograd convolution: 16 planes over 2x2 tiles, or 36 planes over 4x4 tiles where the map
+// allows F(4x4,3x3).  Offsets in floats:  U [planes][MT*128][S*32] | V [planes][S*32][Tpad] | M [planes][MT*128][Tpad] |
+// 64 words for the fix-up counter | on the 4x4 tile, one word of tie bits per tile (the word in front of them, inside the 64:
+// the input's largest magnitude).  The fix-up LIST aliases the V region on purpose: it is free once the GEMM has read it, or at
+// once when V itself lives in the caller's slot.
+struct WinoConvGeom { int planes, MT, S; long T, Tpad; bool edge; size_t v_floats, U, V, M, count, tie, floats; };
+static WinoConvGeom wino_conv_geom(int N, int C, int M, int H, int W, bool f4) {
+  WinoConvGeom g;
+  g.planes = f4 ? 36 : 16; g.edge = f4 && ((H % 4) != 0 || (W % 4) != 0);
+  g.T = f4 ? (long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long)N * (H / 2) * (W / 2);
+  g.Tpad = wino_tpad(g.T); g.MT = (M + WBM - 1) / WBM; g.S = (C + WK - 1) / WK;
+  g.v_floats = (size_t)g.planes * g.S * WK * g.Tpad;
+  g.U = 0; g.V = (size_t)g.planes * g.MT * WBM * g.S * WK; g.M = g.V + g.v_floats;
+  g.count = g.M + (size_t)g.planes * g.MT * WBM * g.Tpad; g.tie = g.count + 16;
+  g.floats = g.count + 64 + (f4 ? g.Tpad : 0);
+  return g;
+}
 size_t umpr_wino_ws_floats(int N, int C, int M, int H, int W, int transposed) {
-  const long MT = (M + WBM - 1) / WBM, S = (C + WK - 1) / WK;
-  auto layout = [&](bool f4) {
-    const long T = f4 ? (long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long)N * (H / 2) * (W / 2);
-    const long Tpad = wino_tpad(T);
-    return (size_t)(f4 ? 36 : 16) * (MT * WBM * S * WK + S * WK * Tpad + MT * WBM * Tpad) + 64 + (f4 ? Tpad : 0);   // + fix-up counter and per-tile tie bits
-  };
   const bool map4 = wino_f4_shape(H, W);
   const int mode = umpr_wino_f4_mode();
-  if (!map4 || mode == 0) return layout(false);
-  if (transposed) return layout(true);
+  if (!map4 || mode == 0) return wino_conv_geom(N, C, M, H, W, false).floats;
+  if (transposed) return wino_conv_geom(N, C, M, H, W, true).floats;
   // forward: the 2x2 tile (mode 1 training; in mode 2 the layers a max-pool follows) or the 4x4 one (mode 2; inference)
-  const size_t a = layout(false), b = layout(true);
+  const size_t a = wino_conv_geom(N, C, M, H, W, false).floats, b = wino_conv_geom(N, C, M, H, W, true).floats;
   return a > b ? a : b;
 }
 
@@ -932,19 +941,13 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
   UMPR_REQUIRE(ws_floats >= umpr_wino_ws_floats(N, C, M, H, W, transposed), "winograd: workspace too small");
   UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd: odd map %dx%d", H, W);
   const bool f4 = wino_f4_map(H, W, transposed);
-  const int planes = f4 ? 36 : 16;
-  const long T = f4 ? (long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long)N * (H / 2) * (W / 2);
-  const bool edge = f4 && ((H % 4) != 0 || (W % 4) != 0);
-  const long Tpad = wino_tpad(T);
-  const int MT = (M + WBM - 1) / WBM, S = (C + WK - 1) / WK;
-  float* U = ws;
-  float* V = U + (size_t)planes * MT * WBM * S * WK;
-  float* Mx = V + (size_t)planes * S * WK * Tpad;
-  float* list_region = V;        // the fix-up list lives in the workspace's V region (free once the GEMM has read it, or at once
-                                 // when V itself lives in the caller's slot)
+  const WinoConvGeom G = wino_conv_geom(N, C, M, H, W, f4);
+  const int planes = G.planes, MT = G.MT, S = G.S;
+  const long T = G.T, Tpad = G.Tpad; const bool edge = G.edge;
+  float *U = ws + G.U, *V = ws + G.V, *Mx = ws + G.M, *list_region = ws + G.V;
   if (t_v_slot && !transposed) {
     const size_t vfl = umpr_wino_v_floats(N, Cin, Cout, H, W);
-    UMPR_REQUIRE(f4 && !t_wino_infer && vfl > 0 && vfl == (size_t)planes * S * WK * Tpad && t_v_slot_floats >= vfl,
+    UMPR_REQUIRE(f4 && !t_wino_infer && vfl > 0 && vfl == G.v_floats && t_v_slot_floats >= vfl,
                  "winograd: the V slot does not fit this forward (%d -> %d at %dx%d)", Cin, Cout, H, W);
     V = t_v_slot;
   }
@@ -952,8 +955,7 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
   else wino_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed);
   UMPR_LAUNCH_CHECK("wino_weights");
   const long TT = (T + WBN - 1) / WBN;
-  // decision fix-up (training forward on the 4x4 tile only): counter in the 64 spare floats behind Mx, list in V once the GEMM
-  // has consumed it
+  // decision fix-up (training forward on the 4x4 tile only)
   // tau = kappa * 2^-24 * S.  The tile's error is ~9e-7 rms of rms(y) and S ~ 20 |y|, so kappa = 8 is ~8 standard deviations for a
   // typical output (CPU emulation, tools/wino_flip_sim.py: kappa 8, 32 and 128 fix the same decisions); the list grows in
   // proportion - 6e-6 of the outputs on the golden fixtures' images, 3e-3 on the benchmark's i.i.d.-noise images, whose deep
@@ -963,14 +965,13 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
   WinoFix fx{nullptr, nullptr, 0u, 0.f, nullptr};
   unsigned int* tie_bits = nullptr;
   if (fix) {
-    fx.count = reinterpret_cast<unsigned int*>(Mx + (size_t)planes * MT * WBM * Tpad);
+    fx.count = reinterpret_cast<unsigned int*>(ws + G.count);
     fx.list = reinterpret_cast<unsigned int*>(list_region);
-    const size_t vfl = (size_t)planes * S * WK * Tpad;
-    fx.cap = (unsigned)(vfl < (size_t)0x7fffffff ? vfl : (size_t)0x7fffffff);
+    fx.cap = (unsigned)(G.v_floats < (size_t)0x7fffffff ? G.v_floats : (size_t)0x7fffffff);
     fx.kappa_eps = (float)kappa * 5.9604644775390625e-08f;
     UMPR_REQUIRE((long)N * M * H * W < 0xffffffffL, "winograd fix-up: output tensor too large for 32-bit element indices");
-    if (t_wino_pool_follows) {   // one word per tile behind the counter (umpr_wino_ws_floats reserves Tpad + 64 floats there)
-      tie_bits = fx.count + 16;   // tie_bits[-1]: the input's largest magnitude
+    if (t_wino_pool_follows) {
+      tie_bits = reinterpret_cast<unsigned int*>(ws + G.tie);   // tie_bits[-1]: the input's largest magnitude
       if (hipMemsetAsync(tie_bits - 1, 0, (size_t)(T + 1) * sizeof(unsigned int), s) != hipSuccess) { umpr_set_error("winograd fix-up: memset"); return -2; }
       UMPR_REQUIRE(((long)N * C * H * W) % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "winograd fix-up: unaligned input");
       wino_absmax_kernel<<<nblk((long)N * C * H * W / 4, 1024), 256, 0, s>>>(x, (long)N * C * H * W / 4, tie_bits - 1);
@@ -1508,7 +1509,9 @@ __global__ void wino_wgrad_finish_kernel(const float* __restrict__ P, int splits
 constexpr int kWinoWgradTargetWgs = 1024;
 static const int g_wino_wgrad_rounds = umpr_env_int("UMPR_WINO_WGRAD_ROUNDS", 1);   // 0: the plain 1024-workgroup target
 
-struct WinoWgradGeom { long T, Tpad; int MT, CT, Mpad, Cpad, stages, splits, stages_per_split, planes, bnc; };
+// workspace (offsets in floats): Gy [planes][Mpad][Tpad] | V [planes][Cpad][Tpad] | P [splits][planes][Mpad][Cpad] | BP, the bias
+// partials [Mpad][Tpad / 64] (+ 64)
+struct WinoWgradGeom { long T, Tpad; int MT, CT, Mpad, Cpad, stages, splits, stages_per_split, planes, bnc; size_t Gy, V, P, BP, floats; };
 WinoWgradGeom wino_wgrad_geom(int N, int Cin, int Cout, int H, int W) {
   WinoWgradGeom g;
   // padded 14x14 maps stay on F(3x3,2x2): a quarter of the tiles is too short a reduction for the split-K GEMM and the 36-plane
@@ -1548,28 +1551,21 @@ WinoWgradGeom wino_wgrad_geom(int N, int Cin, int Cout, int H, int W) {
   if (splits < 1) splits = 1;
   g.stages_per_split = (g.stages + splits - 1) / splits;
   g.splits = (g.stages + g.stages_per_split - 1) / g.stages_per_split;
+  g.Gy = 0; g.V = (size_t)g.planes * g.Mpad * g.Tpad; g.P = g.V + (size_t)g.planes * g.Cpad * g.Tpad;
+  g.BP = g.P + (size_t)g.planes * g.splits * g.Mpad * g.Cpad; g.floats = g.BP + (size_t)g.Mpad * (g.Tpad / 64) + 64;
   return g;
 }
 
 }  // namespace
 
-// workspace: Gy [planes][Mpad][Tpad] + V [planes][Cpad][Tpad] + P [splits][planes][Mpad][Cpad] + bias partials [Mpad][Tpad / 64]
-// (floats)
-size_t umpr_wino_wgrad_ws_floats(int N, int Cin, int Cout, int H, int W) {
-  const WinoWgradGeom g = wino_wgrad_geom(N, Cin, Cout, H, W);
-  return (size_t)g.planes * ((size_t)g.Mpad * g.Tpad + (size_t)g.Cpad * g.Tpad + (size_t)g.splits * g.Mpad * g.Cpad) +
-         (size_t)g.Mpad * (g.Tpad / 64) + 64;
-}
+size_t umpr_wino_wgrad_ws_floats(int N, int Cin, int Cout, int H, int W) { return wino_wgrad_geom(N, Cin, Cout, H, W).floats; }
 
 int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
                     int accumulate, float* ws, size_t ws_floats, hipStream_t s) {
-  UMPR_REQUIRE(ws_floats >= umpr_wino_wgrad_ws_floats(N, Cin, Cout, H, W), "winograd wgrad: workspace too small");
-  UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd wgrad: odd map %dx%d", H, W);
   const WinoWgradGeom g = wino_wgrad_geom(N, Cin, Cout, H, W);
-  float* Gy = ws;
-  float* V = Gy + (size_t)g.planes * g.Mpad * g.Tpad;
-  float* P = V + (size_t)g.planes * g.Cpad * g.Tpad;
-  float* BP = P + (size_t)g.planes * g.splits * g.Mpad * g.Cpad;     // per-wave bias partial sums of the dy transform
+  UMPR_REQUIRE(ws_floats >= g.floats, "winograd wgrad: workspace too small");
+  UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd wgrad: odd map %dx%d", H, W);
+  float *Gy = ws + g.Gy, *V = ws + g.V, *P = ws + g.P, *BP = ws + g.BP;   // BP: per-wave bias partial sums of the dy transform
   const bool f4 = g.planes == 36;
   // rows m >= Cout of Gy are never written: every P element is a dot product of ONE Gy row with ONE V row, so garbage
   // stays in rows of P that the finish kernel does not read.
