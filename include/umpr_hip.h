@@ -366,6 +366,19 @@ int umpr_photo_fetch_u8(const uint8_t* packed, size_t packed_bytes, const umpr_p
                         const int32_t* dst_slot, int n_photos, int dst_h, int dst_w, uint8_t* store, long n_slots, float* out,
                         void* stream);
 
+/* ---- device-resident VGG features (umpr_amd/photos.py::FeatureStore) -----------------------------------------------------------
+ * With a frozen VGG (--freeze_vgg) the F floats the stack yields for a photo are a constant of the run.  `store` (device memory)
+ * holds n_slots rows of F fp32; `fresh` [n_fresh][F] holds the rows the VGG has just computed for the photos the store lacks.
+ * out [n][F]: row i = store[src_slot[i]] if src_slot[i] >= 0, else fresh[fresh_row[i]] (several photos may name one fresh row: the
+ * same photo twice in a batch); if dst_slot[i] >= 0 the same row is also written to store[dst_slot[i]].  A bit-exact copy in
+ * 16-byte groups.  fresh_row, src_slot and dst_slot are HOST memory (n entries each), read and validated during the call and
+ * carried in the kernel arguments, 64 photos per launch.  Refused without launching, `out` and `store` untouched: a slot outside
+ * [0, n_slots), a photo with both or neither of src_slot / fresh_row, a fresh_row outside [0, n_fresh), one dst_slot given twice,
+ * a dst_slot that a photo of the same call reads, a null store with a slot in use, F not a positive multiple of 4, fresh / store /
+ * out not 16-byte aligned.  No allocation or copy: capture-safe. */
+int umpr_feature_fetch_f32(const float* fresh, int n_fresh, const int32_t* fresh_row, const int32_t* src_slot,
+                           const int32_t* dst_slot, int n, int F, float* store, long n_slots, float* out, void* stream);
+
 /* ---- R-Net pre-training head (pretrain/pretrain_rnet.py:147-169): result = sigmoid(Linear(K -> 1)(att)),
  * loss = BCELoss(mean)(result, target) with torch's log clamp at -100.  att rows at att + b*ld (K = 256: [atte_u;atte_i]
  * as umpr_coattention_fwd leaves them).  ws: B floats.  Backward follows ATen's binary_cross_entropy_backward

@@ -3,6 +3,8 @@
 
     python main.py --data_dir synthetic --batch_size 64                       # single MI355X
     python main.py --data_dir synthetic --learning_rate 1e-3 --grad_clip 5.0  # clip the gradient to a global 2-norm of 5
+    python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
+                                                                                  # for every photo kept in 1 GB of HBM
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
 
 The model / optimiser / train / evaluate drivers are the MI355X-native ones (umpr_amd).  With a data_dir that holds
@@ -69,7 +71,8 @@ class _Collate:
     def __init__(self, ignore_photos, rank=0, world=1, store=None):
         self.ignore_photos = ignore_photos
         self.shard = (rank, world) if world > 1 else None
-        self.store = store          # a PhotoStore's index (--photo_store_gb): photos the store holds are not decoded
+        self.store = store          # a PhotoStore's or FeatureStore's index (--photo_store_gb, --feature_store_gb): photos the
+                                    # store holds are not decoded
 
     def __call__(self, samples):
         from umpr_amd.data import batch_loader
@@ -104,12 +107,21 @@ def run_real(config, rank, world, log):
     w2v = Word2vec(config.word2vec_file)
     # --photo_store_gb X: this rank keeps every resized photo it has decoded in X GB of device memory (150 528 B per photo, no
     # eviction) and decodes it once per run instead of once per epoch and validation pass (umpr_amd/photos.py::PhotoStore)
+    # --freeze_vgg True --feature_store_gb X: the store keeps what the frozen VGG makes of a photo instead (4 000 B per photo): a
+    # resident photo is neither decoded nor resized nor run through the VGG (umpr_amd/photos.py::FeatureStore)
     store = None
-    if config.photo_store_gb > 0 and not config.review_net_only:
+    if config.feature_store_gb > 0 and not config.review_net_only:
+        from umpr_amd.photos import FeatureStore
+        store = FeatureStore(config.device, capacity_bytes=int(config.feature_store_gb * 1e9))
+        log(f'Feature store: {store.slots} slots of {store.slot_bytes} B ({store.slots * store.slot_bytes / 1e9:.2f} GB) on '
+            f'{config.device}' + ('; it replaces the photo store (--photo_store_gb): a photo whose features are resident is '
+                                  'never resized' if config.photo_store_gb > 0 else ''))
+    elif config.photo_store_gb > 0 and not config.review_net_only:
         from umpr_amd.photos import PhotoStore
         store = PhotoStore(config.device, capacity_bytes=int(config.photo_store_gb * 1e9))
         log(f'Photo store: {store.slots} slots of {store.slot_bytes} B ({store.slots * store.slot_bytes / 1e9:.2f} GB) on '
             f'{config.device}')
+    store_name = 'Feature store' if config.feature_store_gb > 0 else 'Photo store'
     known = lambda data: store and store.register(data.photo_paths())
     collate = _Collate(config.review_net_only, rank, world, store.index if store else None)
     workers = max(0, int(getattr(config, "loader_workers", 0)))
@@ -133,7 +145,7 @@ def run_real(config, rank, world, log):
         valid_dlr = ShardedLoader(DataLoader(valid_data, batch_size=config.batch_size, **dl), rank, world)
         _, saved = training(train_dlr, valid_dlr, model, config, model_path, logger=logger, world=world, rank=rank)
         if store:
-            log(f'Photo store after training: {store.stats()}')
+            log(f'{store_name} after training: {store.stats()}')
     if config.test_only or saved:
         load_checkpoint(model_path, model, map_location=config.device)
         log(f'Testing the checkpoint {model_path}')
@@ -145,7 +157,7 @@ def run_real(config, rank, world, log):
     test_dlr = ShardedLoader(DataLoader(test_data, batch_size=config.batch_size, **dl), rank, world)
     log(f"Test end, test mse is {evaluate_mse(model, test_dlr):.6f}")
     if store:
-        log(f'Photo store after the test: {store.stats()}')
+        log(f'{store_name} after the test: {store.stats()}')
 
 
 def main():
@@ -165,11 +177,27 @@ def main():
         raise
 
 
+# options the reference does not have
+EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
+                 "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
+                 "freeze_vgg": False, "feature_store_gb": 0.0}
+
+
+def check_flags(config):
+    """Refuses, at start-up, combinations of options that cannot work."""
+    if not isinstance(config.freeze_vgg, bool):
+        sys.exit(f"--freeze_vgg takes True or False, got {config.freeze_vgg!r}")
+    if config.feature_store_gb < 0:
+        sys.exit(f"--feature_store_gb must be >= 0, got {config.feature_store_gb}")
+    if config.feature_store_gb > 0 and not config.freeze_vgg:
+        sys.exit("--feature_store_gb needs --freeze_vgg True: the store keeps the VGG's output for every photo, which is a constant "
+                 "of the run only while the VGG does not train")
+
+
 def _main():
-    extra = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
-             "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0}
-    Config.extend(extra)
+    Config.extend(EXTRA_OPTIONS)
     config = Config()
+    check_flags(config)
     rank, local, world = parallel.init_distributed()
     if not torch.cuda.is_available():
         sys.exit("main.py needs an MI355X: the UMPR hot path has no CPU fallback (use the reference for CPU runs)")

@@ -12,6 +12,12 @@ count (default 0,4,8) whole epochs of the gpu form with the store off (twice: th
 forms alternating; then end-to-end training, fp32 and bf16, store off and warm, beside bench.py's resident-batch rate.
 
     python tools/bench_loader.py --items 2000 --photo_store_gb 1
+
+With `--freeze_vgg True` it measures the frozen VGG and the feature store (umpr_amd/photos.py::FeatureStore, capacity
+`--feature_store_gb`, default 1): per arithmetic mode and worker count, end-to-end training epochs with the VGG trainable (photo
+store warm), frozen without a store, frozen with the photo store warm, frozen with the feature store cold, and frozen with it warm.
+
+    python tools/bench_loader.py --items 2000 --freeze_vgg True --workers 0,4
 """
 import argparse
 import functools
@@ -65,10 +71,16 @@ def main():
     ap.add_argument("--workers", default=None, help="default 0,4,8,12; 0,4,8 with --photo_store_gb")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--photo_store_gb", type=float, default=0.0, help="measure the photo store with this capacity")
+    ap.add_argument("--freeze_vgg", type=lambda t: t == "True", default=False, help="True: measure the frozen VGG")
+    ap.add_argument("--feature_store_gb", type=float, default=0.0, help="capacity of the feature store (with --freeze_vgg True; "
+                    "default 1)")
     a = ap.parse_args()
-    a.workers = a.workers or ("0,4,8" if a.photo_store_gb > 0 else "0,4,8,12")
-    a.users = a.users or (max(200, a.items // 2) if a.photo_store_gb > 0 else 200)
-    resident = resident_rates(a.batch) if a.photo_store_gb > 0 else None
+    if a.feature_store_gb > 0 and not a.freeze_vgg:
+        sys.exit("--feature_store_gb needs --freeze_vgg True")
+    stores = a.photo_store_gb > 0 or a.freeze_vgg
+    a.workers = a.workers or ("0,4,8" if stores else "0,4,8,12")
+    a.users = a.users or (max(200, a.items // 2) if stores else 200)
+    resident = resident_rates(a.batch) if a.photo_store_gb > 0 and not a.freeze_vgg else None
     from torch.utils.data import DataLoader
     from main import _Collate
     from umpr_amd.config import Config
@@ -83,6 +95,8 @@ def main():
         print(f"corpus: {n} reviews -> {len(ds)} samples, Dataset built in {time.perf_counter() - t0:.2f} s", flush=True)
         photo = ds[0][3][0][0]
         per_photo(photo)
+        if a.freeze_vgg:
+            return frozen_vgg(a, ds, cfg, w2v)
         if a.photo_store_gb > 0:
             return photo_store(a, ds, cfg, w2v, resident)
         forms = {"host": functools.partial(batch_loader, ignore_photos=False, resize_on_gpu=False), "gpu": _Collate(False)}
@@ -139,6 +153,87 @@ def main():
             print(f"end to end (CSV + JPEG decode + collate + H2D + train step), {form} form, {w} workers: "
                   f"{k * a.batch / dt:.1f} samples/s ({1e3 * dt / k:.1f} ms per step)", flush=True)
             del it, dl, model, opt
+
+
+def _loader(a, ds, w, store):
+    from torch.utils.data import DataLoader
+    from main import _Collate
+    kw = dict(collate_fn=_Collate(False, store=store.index if store else None), num_workers=w, pin_memory=True)
+    if w:
+        kw.update(prefetch_factor=2, persistent_workers=True)
+    return DataLoader(ds, batch_size=a.batch, shuffle=True, drop_last=True, **kw)
+
+
+def _epoch(a, dl, step=None):
+    """samples/s of one epoch of `dl`, timed from the first batch's arrival (which leaves the workers' start out)."""
+    it = iter(dl)
+    first = next(it)
+    if step:
+        step(first)
+    t0 = time.perf_counter()
+    k = 0
+    for b in it:
+        if step:
+            step(b)
+        k += 1
+    torch.cuda.synchronize()
+    return k * a.batch / (time.perf_counter() - t0)
+
+
+def frozen_vgg(a, ds, cfg, w2v):
+    """End-to-end training epochs of `ds` (CSV + JPEG decode + collate + H2D + train step): the VGG trainable with the photo store
+    warm, frozen without a store (the loader decodes every photo: on few workers that, not the GPU, sets the rate), frozen with the
+    photo store warm (the same loader work as the trainable leg: the difference is the VGG alone), frozen with the feature store
+    cold (the epoch that fills it) and warm.  Every leg runs one warm-up epoch first (allocator, workspaces, first-use setup, the
+    worker pool's start) - except the cold epoch, which can only happen once: its model has run epochs before, and its worker
+    pool has served one loader-only epoch, which makes nothing resident."""
+    from umpr_amd.model import UMPR
+    from umpr_amd.optim import FusedAdam
+    from umpr_amd.photos import FeatureStore, PhotoStore
+    from umpr_amd.train import train_step
+    if not torch.cuda.is_available():
+        sys.exit("--freeze_vgg needs an MI355X")
+    dev = torch.device("cuda:0")
+    paths = list(ds.photo_paths())
+    print(f"an epoch: {len(ds) // a.batch} batches of {a.batch}, {len(set(paths) - {'unknown'})} distinct photos", flush=True)
+    for dtype in ("fp32", "bf16"):
+        cfg.dtype = dtype
+        for w in [int(x) for x in a.workers.split(",")]:
+            rates = {}
+
+            def leg(freeze):
+                cfg.freeze_vgg = freeze
+                torch.manual_seed(0)
+                model = UMPR(cfg, w2v.embedding).to(dev)
+                opt = FusedAdam(model, cfg.learning_rate, cfg.l2_regularization, cfg.lr_decay)
+                return model, opt, (lambda b: train_step(model, opt, b))
+
+            model, opt, step = leg(False)
+            store = PhotoStore(dev, capacity_bytes=int((a.photo_store_gb or 1.0) * 1e9)).register(paths)
+            dl = _loader(a, ds, w, store)
+            _epoch(a, dl, step)
+            rates["trainable, photo store warm"] = _epoch(a, dl, step)
+            del model, opt, step, dl, store
+            model, opt, step = leg(True)
+            dl = _loader(a, ds, w, None)
+            _epoch(a, dl, step)
+            rates["frozen, no store"] = _epoch(a, dl, step)
+            del dl
+            store = PhotoStore(dev, capacity_bytes=int((a.photo_store_gb or 1.0) * 1e9)).register(paths)
+            dl = _loader(a, ds, w, store)
+            _epoch(a, dl, step)
+            rates["frozen, photo store warm"] = _epoch(a, dl, step)
+            del dl, store
+            store = FeatureStore(dev, capacity_bytes=int((a.feature_store_gb or 1.0) * 1e9)).register(paths)
+            dl = _loader(a, ds, w, store)
+            _epoch(a, dl)
+            rates["frozen, feature store cold"] = _epoch(a, dl, step)
+            rates["frozen, feature store warm"] = _epoch(a, dl, step)
+            print(f"end to end, {dtype}, {w:2d} workers: " + ", ".join(f"{k} {v:.1f} samples/s" for k, v in rates.items()),
+                  flush=True)
+            print(f"    feature store: {store.stats()}", flush=True)
+            del model, opt, step, dl, store
+    cfg.freeze_vgg = False
 
 
 def photo_store(a, ds, cfg, w2v, resident):

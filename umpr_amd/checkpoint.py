@@ -42,6 +42,8 @@ def load_checkpoint(path, model, opt=None, map_location="cpu"):
     state_dict file (e.g. ``torch.save(reference_model.state_dict(), path)`` written on the reference side)."""
     ck = torch.load(path, map_location=map_location, weights_only=True)
     sd = ck["model"] if isinstance(ck, dict) and "model" in ck and isinstance(ck["model"], dict) else ck
+    if opt is not None and isinstance(ck, dict) and "optimizer" in ck:
+        opt.check_state_dict(ck["optimizer"])       # e.g. moments of a trainable VGG for a frozen one: before anything is overwritten
     model.load_state_dict(sd)
     if opt is not None:
         if isinstance(ck, dict) and "optimizer" in ck:

@@ -176,6 +176,33 @@ __global__ __launch_bounds__(kThreads) void photo_fetch_u8_kernel(HitChunk chunk
   if (blockIdx.x == gridDim.x - 1 && tid < n - nvec) o[nvec + tid] = lut[s[nvec + tid]];
 }
 
+// ---- device-resident VGG features (umpr_amd/photos.py::FeatureStore) ---------------------------------------------------------------
+// With a frozen VGG the F = 1000 floats behind a photo are a constant of the run: a slot holds them, and a resident photo costs one
+// row copy instead of a resize and a VGG forward.
+
+struct FeatRow {
+  int src_slot;          // >= 0: the row is read from this slot of the store
+  int fresh_row;         // else: from this row of `fresh`
+  int dst_slot;          // >= 0: the row is also written to this slot
+};
+struct FeatChunk {
+  FeatRow r[kPhotoChunk];
+};
+
+// out[row] = store[src_slot] or fresh[fresh_row], and the same 16-byte groups to store[dst_slot]: one uint4 per thread, blockIdx.y
+// = row of the chunk (its record is a wave-uniform kernel-argument load).  The host has checked that no dst_slot of the call is
+// read or written twice, so the launch has no ordering of its own to keep.
+__global__ __launch_bounds__(kThreads) void feature_fetch_f32_kernel(FeatChunk chunk, int nvec, const uint4* __restrict__ fresh,
+                                                                     uint4* store, uint4* __restrict__ out) {
+  const int j = blockIdx.x * kThreads + threadIdx.x;
+  if (j >= nvec) return;
+  const FeatRow r = chunk.r[blockIdx.y];
+  const uint4* s = r.src_slot >= 0 ? store + (size_t)r.src_slot * nvec : fresh + (size_t)r.fresh_row * nvec;
+  const uint4 v = s[j];
+  out[(size_t)blockIdx.y * nvec + j] = v;
+  if (r.dst_slot >= 0) store[(size_t)r.dst_slot * nvec + j] = v;
+}
+
 }  // namespace
 
 extern "C" int umpr_photo_resize_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc, int n_photos,
@@ -302,6 +329,54 @@ extern "C" int umpr_photo_fetch_u8(const uint8_t* packed, size_t packed_bytes, c
         photo_fetch_u8_kernel<false><<<grid, kThreads, 0, s>>>(hit, n, store, slot_bytes, o);
       UMPR_LAUNCH_CHECK("photo_fetch_u8 (fetch)");
     }
+  }
+  return 0;
+}
+
+extern "C" int umpr_feature_fetch_f32(const float* fresh, int n_fresh, const int32_t* fresh_row, const int32_t* src_slot,
+                                      const int32_t* dst_slot, int n, int F, float* store, long n_slots, float* out, void* stream) {
+  UMPR_REQUIRE(n >= 0 && n_fresh >= 0, "feature_fetch_f32: n = %d, n_fresh = %d", n, n_fresh);
+  if (n == 0) return 0;
+  UMPR_REQUIRE(fresh_row != nullptr && src_slot != nullptr && dst_slot != nullptr && out != nullptr,
+               "feature_fetch_f32: null argument");
+  UMPR_REQUIRE(F > 0 && F % 4 == 0 && F <= (1 << 24), "feature_fetch_f32: F = %d is not a positive multiple of 4", F);
+  UMPR_REQUIRE(n_slots >= 0 && n_slots <= 0x7fffffffL, "feature_fetch_f32: n_slots = %ld", n_slots);
+  UMPR_REQUIRE(n_fresh == 0 || fresh != nullptr, "feature_fetch_f32: %d fresh rows but a null `fresh`", n_fresh);
+  UMPR_REQUIRE(((uintptr_t)fresh & 15) == 0 && ((uintptr_t)store & 15) == 0 && ((uintptr_t)out & 15) == 0,
+               "feature_fetch_f32: fresh, store or out not 16-byte aligned");
+  std::vector<int32_t> written;
+  for (int i = 0; i < n; ++i) {
+    const bool hit = src_slot[i] >= 0, computed = fresh_row[i] >= 0;
+    UMPR_REQUIRE(hit != computed, "feature_fetch_f32: photo %d has %s a src_slot and a fresh_row", i, hit ? "both" : "neither");
+    if (hit || dst_slot[i] >= 0) UMPR_REQUIRE(store != nullptr, "feature_fetch_f32: photo %d uses a slot but the store is null", i);
+    if (hit) UMPR_REQUIRE(src_slot[i] < n_slots, "feature_fetch_f32: photo %d: src_slot %d outside the %ld-slot store", i,
+                          src_slot[i], n_slots);
+    if (computed) UMPR_REQUIRE(fresh_row[i] < n_fresh, "feature_fetch_f32: photo %d: fresh_row %d outside the %d fresh rows", i,
+                               fresh_row[i], n_fresh);
+    if (dst_slot[i] >= 0) {
+      UMPR_REQUIRE(dst_slot[i] < n_slots, "feature_fetch_f32: photo %d: dst_slot %d outside the %ld-slot store", i, dst_slot[i],
+                   n_slots);
+      written.push_back(dst_slot[i]);
+    }
+  }
+  std::sort(written.begin(), written.end());
+  for (size_t k = 1; k < written.size(); ++k)
+    UMPR_REQUIRE(written[k] != written[k - 1], "feature_fetch_f32: slot %d is the dst_slot of two photos", written[k]);
+  for (int i = 0; i < n; ++i)
+    UMPR_REQUIRE(src_slot[i] < 0 || !std::binary_search(written.begin(), written.end(), src_slot[i]),
+                 "feature_fetch_f32: photo %d reads slot %d, which this call writes", i, src_slot[i]);
+  const hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nvec = F / 4;
+  for (int first = 0; first < n; first += kPhotoChunk) {
+    const int cnt = min(kPhotoChunk, n - first);
+    FeatChunk chunk = {};
+    for (int i = 0; i < cnt; ++i)
+      chunk.r[i] = {src_slot[first + i] >= 0 ? src_slot[first + i] : -1, src_slot[first + i] >= 0 ? -1 : fresh_row[first + i],
+                    dst_slot[first + i] >= 0 ? dst_slot[first + i] : -1};
+    feature_fetch_f32_kernel<<<dim3(cdiv(nvec, kThreads), cnt), kThreads, 0, s>>>(
+        chunk, nvec, reinterpret_cast<const uint4*>(fresh), reinterpret_cast<uint4*>(store),
+        reinterpret_cast<uint4*>(out + (size_t)first * F));
+    UMPR_LAUNCH_CHECK("feature_fetch_f32");
   }
   return 0;
 }

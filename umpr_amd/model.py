@@ -798,6 +798,8 @@ class VGG16(nn.Module):
                 nn.init.constant_(m.bias, 0)
         self.dropout_masks = None  # optional injected keep-masks uint8 [2][n][4096] (parity tests)
         self._calls = 0
+        self.forward_calls = 0     # every forward, frozen or not (`_calls` seeds the dropout masks and is part of a checkpoint)
+        self.frozen = False        # UMPR(freeze_vgg=True): a fixed feature extractor, see forward
         self.grad_callbacks = []   # called once the classifier gradients have been written in place (GradReducer)
         for p in self.parameters():
             p._umpr_direct = True  # one backward node writes each of these exactly once per step
@@ -813,10 +815,21 @@ class VGG16(nn.Module):
         return ps
 
     def forward(self, images):
-        self._calls += 1
-        seed = (torch.initial_seed() * 1000003 + self._calls) & 0x7FFFFFFFFFFFFFFF
+        self.forward_calls += 1
         ps = self.param_list()
         bf16 = self.compute_dtype == "bf16"
+        if self.frozen:
+            # A fixed feature extractor: the inference path whatever module.training and the grad mode say - the F(4x4,3x3) forward
+            # tile, no dropout and no dropout counter consumed, nothing kept for backward; the output carries no grad.
+            with torch.no_grad():
+                _MODE.infer = True
+                try:
+                    pool5, acts = (_VGGFeaturesBF16 if bf16 else _VGGFeatures).apply(images, *ps[:26])
+                finally:
+                    _MODE.infer = False
+                return _VGGClassifier.apply(pool5, acts, False, None, 0, self, bf16, *ps[26:])
+        self._calls += 1
+        seed = (torch.initial_seed() * 1000003 + self._calls) & 0x7FFFFFFFFFFFFFFF
         _MODE.infer = not torch.is_grad_enabled()
         try:
             pool5, acts = (_VGGFeaturesBF16 if bf16 else _VGGFeatures).apply(images, *ps[:26])
@@ -870,6 +883,13 @@ class UMPR(nn.Module):
             self.visual_net = VisualNet(view_size, vgg_weights=getattr(config, "vgg_weights", None),
                                         dtype=self.compute_dtype)
             self.linear_fusion = nn.Sequential(nn.Linear(config.gru_size * 2 + view_size + view_size, 1), nn.ReLU())
+        # not in the reference: `--freeze_vgg True` makes the VGG16 a fixed feature extractor (the reference trains it at lr 1e-6:
+        # no weight moves by more than 0.05 in the 50 000 steps of a run).  Its parameters keep their state_dict keys and shapes and
+        # take no gradient; pos_v_emb, neg_v_emb and visual_net.linear train as before.  Nothing to freeze in UMPR-R.
+        self.freeze_vgg = bool(getattr(config, "freeze_vgg", False)) and not config.review_net_only
+        if self.freeze_vgg:
+            self.visual_net.vgg16.requires_grad_(False)
+            self.visual_net.vgg16[0].frozen = True
         self.last_loss_terms = None
         # Parameters whose backward node can write the gradient straight into the optimiser's arena (_grad_targets):
         # everything in the review / control nets (GRU weights accumulate in place across their uses) and, set by VGG16
@@ -1013,6 +1033,18 @@ class UMPR(nn.Module):
         m = self._maps(device)
         return _ZeroPad.apply(fw, (1, D + (0 if self.review_net_only else 2 * len(self.views))), None, m.fus)
 
+    def _feature_store(self, photos):
+        """The photos.FeatureStore `photos` was collated against (main.py --feature_store_gb), or None."""
+        key = getattr(photos, "store_key", None)
+        if key is None:
+            return None
+        from .photos import FeatureStore
+        store = FeatureStore.find(key)
+        if store is not None and not self.freeze_vgg:
+            raise _lib_mod.UmprHipError("a batch collated against a feature store reached a model whose VGG trains: the store "
+                                        "holds the output of a frozen VGG only (build the model with freeze_vgg=True)")
+        return store
+
     def forward(self, user_reviews, item_reviews, ui_reviews, u_lengths, i_lengths, ui_lengths, photos, labels):
         _MODE.b16 = self.compute_dtype == "bf16" and _TEXT_BF16
         try:
@@ -1027,8 +1059,11 @@ class UMPR(nn.Module):
         # pinned host batches (DataLoader(pin_memory=True)) upload asynchronously; the kernels follow on the same stream
         user_reviews, item_reviews, ui_reviews = [_c(v.to(device, non_blocking=True))
                                                   for v in (user_reviews, item_reviews, ui_reviews)]
-        photos, labels = [v.to(device, non_blocking=True) for v in (photos, labels)]
-        labels = _c(labels.float())
+        # a batch collated against a photos.FeatureStore (frozen VGG): its photos are never materialised, see below
+        feature_store = self._feature_store(photos) if not self.review_net_only else None
+        if feature_store is None:
+            photos = photos.to(device, non_blocking=True)
+        labels = _c(labels.to(device, non_blocking=True).float())
         emb = self.embedding.weight
         B, S, L = user_reviews.shape
         _, S_ui, L_ui = ui_reviews.shape
@@ -1073,7 +1108,10 @@ class UMPR(nn.Module):
                 t.record_stream(side)
         vn = self.visual_net
         V, Pc = photos.shape[1], photos.shape[2]
-        vgg = vn.vgg16[0](photos.reshape(B * V * Pc, *photos.shape[3:]).float())
+        if feature_store is not None:
+            vgg = feature_store.features(photos, vn.vgg16[0], non_blocking=True)
+        else:
+            vgg = vn.vgg16[0](photos.reshape(B * V * Pc, *photos.shape[3:]).float())
         if side is not None:
             main.wait_stream(side)
             for t in (rr, cu, ci, pp, pn):

@@ -134,6 +134,8 @@ class FusedAdam:
             # at the front of the arena so that one contiguous slice can be all-reduced while the conv backward runs
             order_key = lambda name: 0 if _is_classifier(name) else 1
         named.sort(key=lambda np_: order_key(np_[0]))  # stable: model order inside each class
+        if not named:
+            raise ValueError("FusedAdam: the model has no trainable parameter")
         device = named[0][1].device
         self.groups = [_Group([(n, p) for n, p in named if 'bias' not in n], l2_regularization, device),
                        _Group([(n, p) for n, p in named if 'bias' in n], 0.0, device)]
@@ -159,9 +161,12 @@ class FusedAdam:
         if prev is not None and prev is not self:
             prev.close()
         model._umpr_optimizer = weakref.ref(self)
-        for m in model.modules():
-            if hasattr(m, "grad_callbacks"):
-                add_callback(m, self._on_classifier_grads)
+        # a frozen VGG (UMPR(freeze_vgg=True)) leaves no classifier slice in the arenas: no early update, no callback
+        self._has_classifier = self.early_bucket() is not None
+        if self._has_classifier:
+            for m in model.modules():
+                if hasattr(m, "grad_callbacks"):
+                    add_callback(m, self._on_classifier_grads)
 
     def close(self):
         """Detach from the model: remove this optimiser's callbacks (and its reducer's).  The parameters stay views of the
@@ -224,6 +229,8 @@ class FusedAdam:
         43.49 ms fp32, 16.06 vs 16.51 ms bf16); on a single GPU 0.1-0.3 ms in bf16 (9.56 vs 9.71 ms) and nothing in fp32.  Its stream is one more next to main / text / weight-gradient / RCCL:
         umpr_amd/__init__.py sets GPU_MAX_HW_QUEUES, the number of hardware queues they share."""
         if _EARLY_ADAM == "0" or self.max_grad_norm > 0.0:   # clipping: the coefficient needs every gradient first
+            return
+        if not self._has_classifier:                         # frozen VGG: there is no slice to update early
             return
         self._early = (float(grad_scale),)
         self._early_done = None
@@ -366,7 +373,25 @@ class FusedAdam:
                 st["v"][n] = g.v[off:off + k].detach().cpu().clone()
         return st
 
+    def check_state_dict(self, st):
+        """Raises unless `st` holds Adam moments for exactly the parameters this optimiser trains, in their sizes - a checkpoint
+        written with the VGG frozen resumed with it trainable, or the other way round, does not."""
+        for key in ("m", "v"):
+            have = {n: int(t.numel()) for n, t in st[key].items()}
+            want = {n: g.offsets[n][1] for g in self.groups for n in g.names}
+            if have != want:
+                missing, extra = sorted(set(want) - set(have)), sorted(set(have) - set(want))
+                sized = sorted(n for n in set(want) & set(have) if want[n] != have[n])
+                vgg = [n for n in missing + extra if ".vgg16." in n]
+                hint = (" (the checkpoint was written with the VGG " + ("frozen" if any(n in missing for n in vgg) else "trainable")
+                        + ", this run has it " + ("trainable" if any(n in missing for n in vgg) else "frozen")
+                        + ": pass the same --freeze_vgg)") if vgg else ""
+                raise ValueError(f"optimizer state does not match the trainable parameters{hint}: {len(missing)} parameters "
+                                 f"without moments {missing[:3]}, {len(extra)} moments without a trainable parameter {extra[:3]}, "
+                                 f"{len(sized)} of another size {sized[:3]}")
+
     def load_state_dict(self, st):
+        self.check_state_dict(st)
         self.step_count = int(st["step"])
         self.lr = float(st["lr"])
         self.base_lr = float(st.get("base_lr", self.base_lr))

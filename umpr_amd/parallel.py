@@ -117,7 +117,10 @@ class GradReducer:
     the classifier weights - the first gradients autograd produces - count down; when the last of them has landed the
     all-reduce of that slice is launched asynchronously (RCCL runs on its own stream), so 494 MB of the 554 MB travel
     over xGMI while the convolutional backward is still computing; `finish()` reduces the remainder and waits.
-    Sum only: the 1/world scale is folded into the Adam kernel."""
+    Sum only: the 1/world scale is folded into the Adam kernel.
+
+    With a frozen VGG (UMPR(freeze_vgg=True)) the arenas hold no VGG parameter: there is no early slice (`opt.early_bucket()` is
+    None) and no per-block bucket, no hook or callback is installed, and `finish()` reduces the arenas whole."""
 
     def __init__(self, opt, n_buckets=4):
         self.opt = opt

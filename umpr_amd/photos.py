@@ -10,6 +10,11 @@ the host form.
 ``PhotoStore`` (off unless asked for) keeps the resized uint8 image of every photo it has seen in device memory: a photo is
 decoded once per run, every later use ships no pixels and is a table lookup on the device (umpr_photo_fetch_u8), still
 bit-identical.  No eviction: once the slots are used up, further photos are decoded every time.
+
+``FeatureStore`` (off unless asked for, frozen VGG only) keeps what the VGG makes of a photo instead: 1000 floats, 4 000 B against
+the photo's 150 528 B.  A resident photo is then neither decoded nor resized nor run through the VGG: ``features`` resizes only the
+photos the store lacks, runs the VGG once on those, and one kernel (umpr_feature_fetch_f32) builds the dense feature tensor the
+head takes and fills the new slots.
 """
 from __future__ import annotations
 
@@ -315,3 +320,197 @@ class PhotoStore(PhotoTable):
     def __repr__(self):
         return (f"PhotoStore({self.size[0]}x{self.size[1]}, {self.used}/{self.slots} slots of {self.slot_bytes} B on "
                 f"{self.device}, {len(self.index.ids)} photos registered)")
+
+
+def vgg_fingerprint(vgg):
+    """What a FeatureStore remembers of the VGG parameters its rows were computed from: storage address, version counter, dtype
+    and device of every parameter, and the module's compute dtype.  ``load_state_dict`` / ``load_checkpoint`` (in-place copies:
+    the version counters advance), ``.to()`` and a dtype change (new storage) all change it."""
+    return (str(getattr(vgg, "compute_dtype", "")),) + tuple(
+        (p.data_ptr(), p._version, str(p.dtype), str(p.device)) for p in vgg.parameters())
+
+
+class FeatureTable(PhotoTable):
+    """The host half of a FeatureStore: PhotoTable's ids, id -> slot table and resident bytes, and the plan of which photo of a
+    batch reads a slot, which is computed, and which computed row fills a slot.  Slot `slots` (one past the last) is the reserved
+    row of the all-zero image.  Touches no device."""
+
+    def __init__(self, size=(224, 224), slots=0, max_photos=1 << 22):
+        super().__init__(size, slots, max_photos)
+        self.zero_slot = self.slots
+        self.zero_ready = False
+        self.fingerprint = None
+        self.computed = self.shared = self.missing = self.flushes = self.vgg_calls = 0
+
+    def guard(self, fingerprint):
+        """Empties the table when `fingerprint` is not the one its rows were filled under; returns whether it did."""
+        if fingerprint == self.fingerprint:
+            return False
+        stale = self.fingerprint is not None and (self.used > 0 or self.zero_ready)
+        self.fingerprint = fingerprint
+        if stale:
+            self.invalidate()
+        return stale
+
+    def invalidate(self):
+        """Nothing is resident any more, for the workers too.  A batch collated before this still names its hits: plan() refuses it."""
+        self.index.resident.zero_()
+        self._slot[:] = -1
+        self.used = 0
+        self.zero_ready = False
+        self.flushes += 1
+
+    def plan(self, raw):
+        """(src_slot, dst_slot, fresh_row int32 [n], miss, full) for a RawPhotos collated against this table's index.  Hits read
+        their slot, and so does a photo that became resident after its worker looked.  A 0 x 0 descriptor without a hit is a
+        missing photo and reads the zero-image row.  Every other photo is computed: `miss` lists the photos to run through the
+        VGG, in batch order, and fresh_row[i] is the position in `miss` of the photo whose row photo i takes - its own, or that of
+        the first photo of the call with the same id.  The first computed occurrence of an id gets a free slot while there is
+        one; `full` counts those that found none.  Photos without an id are computed every time."""
+        from ._lib import UmprHipError
+        if raw.size != self.size:
+            raise UmprHipError(f"feature store holds {self.size} photos, the batch is {raw.size}")
+        n = int(np.prod(raw.geometry))
+        if raw.ids is None or raw.hits is None:
+            raise UmprHipError("RawPhotos: not collated against a store's index (no ids)")
+        ids, hits = raw.ids.numpy(), raw.hits.numpy()
+        if len(ids) != n or len(hits) != n:
+            raise UmprHipError(f"RawPhotos: {len(ids)} ids and {len(hits)} hit flags for {n} photos")
+        src = np.full(n, -1, dtype=np.int32)
+        dst = np.full(n, -1, dtype=np.int32)
+        row = np.full(n, -1, dtype=np.int32)
+        hit = np.flatnonzero(hits)
+        if len(hit):
+            if ids[hit].min() < 0 or ids[hit].max() >= self.max_photos or self._slot[ids[hit]].min() < 0:
+                raise UmprHipError("feature store: a photo was left to the store, which does not hold it")
+            src[hit] = self._slot[ids[hit]]
+        rows = raw.descriptors()["rows"]
+        free, full, miss, first = self.used, 0, [], {}
+        for i in np.flatnonzero(hits == 0):
+            k = int(ids[i]) if 0 <= ids[i] < self.max_photos else -1
+            if rows[i] <= 0:
+                src[i] = self.zero_slot
+            elif k >= 0 and self._slot[k] >= 0:
+                src[i] = self._slot[k]
+            elif k >= 0 and k in first:
+                row[i] = first[k]
+            else:
+                row[i] = len(miss)
+                miss.append(int(i))
+                if k >= 0:
+                    first[k] = row[i]
+                    if free < self.slots:
+                        dst[i] = free
+                        free += 1
+                    else:
+                        full += 1
+        return src, dst, row, np.asarray(miss, dtype=np.int64), full
+
+    def commit(self, raw, src, dst, row, full=0):
+        """Books a `features` call that has been enqueued: the filled slots become resident, for the workers too.  Returns the
+        number of slots filled."""
+        ids = raw.ids.numpy()
+        new = np.flatnonzero(dst >= 0)
+        zero = int((src == self.zero_slot).sum())
+        n_miss = int(row.max()) + 1 if len(row) and row.max() >= 0 else 0
+        self.decoded_while_full += full
+        self._slot[ids[new]] = dst[new]
+        self.used += len(new)
+        self.inserts += len(new)
+        self.hits += int((src >= 0).sum()) - zero
+        self.missing += zero
+        self.computed += n_miss
+        self.shared += int((row >= 0).sum()) - n_miss
+        self.index.resident.numpy()[ids[new]] = 1
+        return len(new)
+
+    def stats(self):
+        return dict(super().stats(), computed=self.computed, shared=self.shared, missing=self.missing, flushes=self.flushes,
+                    vgg_calls=self.vgg_calls)
+
+
+class FeatureStore(FeatureTable):
+    """VGG features of photos kept in device memory: `capacity_bytes // 4000` slots of 1000 fp32 plus the reserved row of the
+    all-zero image, allocated once, private to this process and gone with it.  For a FROZEN VGG only (UMPR(freeze_vgg=True)): its
+    output for a photo is then a constant of the run.  `register(paths)` and `index` are PhotoStore's; UMPR.forward hands a
+    RawPhotos collated against the index to `features(raw, vgg)`.  The store remembers which parameters filled it
+    (vgg_fingerprint) and empties itself when they change.  No eviction: when the slots run out, further photos are computed
+    every time."""
+
+    F = 1000
+    _registry = weakref.WeakValueDictionary()
+
+    def __init__(self, device, size=(224, 224), capacity_bytes=1 << 30, max_photos=1 << 22):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("FeatureStore lives on an MI355X (no CPU path)")
+        self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+        self.slot_bytes = 4 * self.F
+        super().__init__(size, int(capacity_bytes) // self.slot_bytes, max_photos)
+        self.buffer = torch.empty((self.slots + 1) * self.F, dtype=torch.float32, device=self.device)
+        self._insert_stream = self._insert_event = None
+        FeatureStore._registry[self.key] = self
+
+    @classmethod
+    def find(cls, key):
+        return cls._registry.get(key)
+
+    def _vgg(self, vgg, images):
+        self.vgg_calls += 1
+        with torch.no_grad():
+            out = vgg(images)
+        if out.requires_grad or out.dtype != torch.float32 or tuple(out.shape) != (images.shape[0], self.F):
+            raise RuntimeError(f"FeatureStore: the VGG returned {tuple(out.shape)} {out.dtype}, not fp32 [n, {self.F}] without grad")
+        return out if out.is_contiguous() else out.contiguous()
+
+    def features(self, raw, vgg, non_blocking=False):
+        """float32 [B*V*P, 1000] on the current stream: what `vgg(raw.to(device).flatten(0, 2))` returns for a frozen `vgg`, with
+        the VGG run only on the photos the store lacks."""
+        from ._lib import UmprHipError, lib
+        if any(p.requires_grad for p in vgg.parameters()):
+            raise UmprHipError("FeatureStore: the VGG has trainable parameters, so its output for a photo is no constant of the "
+                               "run: build the model with freeze_vgg=True")
+        dw, dh = raw.size
+        n = int(np.prod(raw.geometry))
+        if raw.data.dtype != torch.uint8 or raw.data.dim() != 1 or raw.data.numel() < n * DESC.itemsize:
+            raise UmprHipError(f"RawPhotos: buffer of {raw.data.numel()} bytes cannot hold the {n} photo descriptors")
+        if self.guard(vgg_fingerprint(vgg)):
+            logging.getLogger(__name__).info("feature store: the VGG parameters changed; emptied")
+        src, dst, row, miss, full = self.plan(raw)
+        call = lambda *a: lib().call("umpr_feature_fetch_f32", *a)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            if self._insert_event is not None and stream != self._insert_stream:
+                stream.wait_event(self._insert_event)     # slots filled on another stream
+            filled = False
+            if not self.zero_ready and bool((src == self.zero_slot).any()):
+                # the missing photo: the VGG on ONE all-zero image, once per store (and again after it was emptied)
+                fresh = self._vgg(vgg, torch.zeros(1, 3, dh, dw, dtype=torch.float32, device=self.device))
+                one = lambda v: np.asarray([v], dtype=np.int32)
+                r0, s0, d0 = one(0), one(-1), one(self.zero_slot)
+                call(fresh, 1, r0.ctypes.data, s0.ctypes.data, d0.ctypes.data, 1, self.F, self.buffer, self.slots + 1,
+                     torch.empty(self.F, dtype=torch.float32, device=self.device), stream.cuda_stream)
+                self.zero_ready = filled = True
+            fresh = None
+            if len(miss):
+                packed = raw.data.to(self.device, non_blocking=non_blocking)
+                desc = np.ascontiguousarray(raw.descriptors()[miss])      # the misses' records; offsets into the same buffer
+                images = torch.empty(len(miss), 3, dh, dw, dtype=torch.float32, device=self.device)
+                lib().call("umpr_photo_resize_u8", packed, packed.numel(), desc.ctypes.data, len(miss), dh, dw, images,
+                           stream.cuda_stream)
+                fresh = self._vgg(vgg, images)
+            out = torch.empty(n, self.F, dtype=torch.float32, device=self.device)
+            call(fresh, len(miss), row.ctypes.data, src.ctypes.data, dst.ctypes.data, n, self.F, self.buffer, self.slots + 1, out,
+                 stream.cuda_stream)
+            if self.commit(raw, src, dst, row, full) or filled:      # the workers skip these only now that the fill is enqueued
+                self._insert_event = torch.cuda.Event()
+                self._insert_event.record(stream)
+                self._insert_stream = stream
+        return out
+
+    def stats(self):
+        return dict(super().stats(), bytes=(self.slots + 1) * self.slot_bytes)
+
+    def __repr__(self):
+        return (f"FeatureStore({self.used}/{self.slots} slots of {self.slot_bytes} B on {self.device}, "
+                f"{len(self.index.ids)} photos registered)")
