@@ -61,6 +61,14 @@ int umpr_set_conv_pool_follows(int on);
  * (-1: none yet).  Synchronises the device. */
 long umpr_debug_wino_fix_count(void);
 
+/* Test / tooling aid: what the fp32 3x3 convolution dispatch decides for one pass (0 forward, 1 data gradient, 2 weight gradient)
+ * of one layer shape, `inference` as under umpr_set_conv_inference.  Returns the algorithm: 0 generic gather kernels, 1
+ * first-layer kernels, 2 LDS-patch direct kernels, 3 Winograd F(2x2,3x3), 4 Winograd F(4x4,3x3); <0 on bad arguments.
+ * *ws_bytes: scratch the pass reserves (never more than umpr_conv3x3_pack_bytes / umpr_conv3x3_bwd_weight_ws_bytes return);
+ * *v_bytes: size of the transformed input the training forward keeps in the activation arena for the weight gradient (0: none).
+ * Pure host arithmetic: makes no HIP call, runs without a GPU. */
+int umpr_debug_conv3x3_plan(int pass, int N, int Cin, int Cout, int H, int W, int inference, size_t* ws_bytes, size_t* v_bytes);
+
 /* ---- K1-K3: embedding lookup + bidirectional packed GRU + the reference's double un-sort ---------------------
  * Replaces nn.Embedding (model.py:262-264) + ImprovedRnn.forward (model.py:12-21) for one review tensor.
  * ids [N*L] int64; emb [vocab][E]; GRU weights in nn.GRU layout (gate order r,z,n): w_ih [192][E], w_hh [192][64],

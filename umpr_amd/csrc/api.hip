@@ -58,7 +58,7 @@ struct VggLayout {
   int conv_cin[13], conv_cout[13], conv_hw[13], conv_block[13];
   size_t fc_off[2];     // ReLU outputs of fc1, fc2 ([n][4096])
   size_t drop_off[2];   // dropout outputs
-  size_t v_off[13], v_floats[13];   // transformed inputs the forward keeps for the weight gradient (umpr_wino_v_floats; 0: none)
+  size_t v_off[13], v_floats[13];   // transformed inputs the forward keeps for the weight gradient (ConvPlan::v_floats; 0: none)
   size_t total;         // floats
 };
 VggLayout vgg_layout(int n) {
@@ -80,10 +80,7 @@ VggLayout vgg_layout(int n) {
   for (int j = 0; j < 2; ++j) { L.fc_off[j] = off; off += (size_t)n * 4096; }
   for (int j = 0; j < 2; ++j) { L.drop_off[j] = off; off += (size_t)n * 4096; }
   for (int i = 0; i < 13; ++i) {
-    // only layers whose forward takes the Winograd path (56 / 28 maps, conv2_2 at 112; the 14x14 maps' weight gradient is on
-    // the 2x2 tile and umpr_wino_v_floats returns 0 for them)
-    const bool wl = umpr_conv3x3_fwd_is_wino(L.conv_cin[i], L.conv_cout[i], L.conv_hw[i], L.conv_hw[i]);
-    L.v_floats[i] = wl ? umpr_wino_v_floats(n, L.conv_cin[i], L.conv_cout[i], L.conv_hw[i], L.conv_hw[i]) : 0;
+    L.v_floats[i] = umpr_conv3x3_plan(CONV_FWD, n, L.conv_cin[i], L.conv_cout[i], L.conv_hw[i], L.conv_hw[i], false).v_floats;
     L.v_off[i] = off;
     off += L.v_floats[i];
   }
@@ -121,9 +118,20 @@ int umpr_gemm_f32(const float* A, long lda, int transA, const float* B, long ldb
 // its operands to bf16 on the way into LDS and runs on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (what
 // torch.autocast does to the same nn.GRU / nn.Linear / nn.Conv1d layers).  Hosts set it around a call and clear it after.
 int umpr_set_gemm_bf16(int on) { umpr_gemm_set_b16(on != 0); return 0; }
-int umpr_set_conv_inference(int on) { umpr_wino_set_inference(on != 0); return 0; }
-int umpr_set_conv_pool_follows(int on) { umpr_wino_set_pool_follows(on != 0); return 0; }
+// The two conv hints a host sets around its calls, per host thread.  They are read only where a public entry point builds the
+// ConvHints of a call (conv_hints below); the convolution code itself sees arguments.
+static thread_local bool t_conv_inference = false, t_conv_pool_follows = false;
+int umpr_set_conv_inference(int on) { t_conv_inference = on != 0; return 0; }
+int umpr_set_conv_pool_follows(int on) { t_conv_pool_follows = on != 0; return 0; }
+static ConvHints conv_hints() { ConvHints h; h.inference = t_conv_inference; h.pool_follows = t_conv_pool_follows; return h; }
 long umpr_debug_wino_fix_count(void) { return umpr_wino_last_fix_count(); }
+int umpr_debug_conv3x3_plan(int pass, int N, int Cin, int Cout, int H_, int W, int inference, size_t* ws_bytes, size_t* v_bytes) {
+  UMPR_REQUIRE(pass >= CONV_FWD && pass <= CONV_WGRAD && N > 0 && Cin > 0 && Cout > 0 && H_ > 0 && W > 0, "conv3x3_plan: bad arguments");
+  const ConvPlan p = umpr_conv3x3_plan(static_cast<ConvPass>(pass), N, Cin, Cout, H_, W, inference != 0);
+  if (ws_bytes) *ws_bytes = p.ws_floats * sizeof(float);
+  if (v_bytes) *v_bytes = p.v_floats * sizeof(float);
+  return p.algo;
+}
 
 // ------------------------------------------------------------------------------------------------ GRU
 // split-K slabs of the dW_ih product ([384][Ep] each, two slabs per unit): 256 units = up to 128 splits of the [384 x Ep] x N*L
@@ -479,19 +487,19 @@ size_t umpr_conv3x3_pack_bytes(int N, int Cin, int Cout, int H_, int W) {
 int umpr_conv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int H_, int W,
                      int Cout, int relu, float* wpack, size_t wpack_bytes, void* stream) {
   return umpr_conv3x3_run(x, w, 0, bias, nullptr, y, N, Cin, Cout, H_, W, relu, wpack, wpack_bytes / sizeof(float),
-                          S(stream));
+                          conv_hints(), S(stream));
 }
 int umpr_conv3x3_bwd_data(const float* dy, const float* w, const float* mask_src, float* dx, int N, int Cin, int H_,
                           int W, int Cout, float* wt, size_t wt_bytes, void* stream) {
   return umpr_conv3x3_run(dy, w, 1, nullptr, mask_src, dx, N, Cin, Cout, H_, W, 0, wt, wt_bytes / sizeof(float),
-                          S(stream));
+                          conv_hints(), S(stream));
 }
 size_t umpr_conv3x3_bwd_weight_ws_bytes(int N, int Cin, int Cout, int H_, int W) {
   return umpr_conv3x3_wgrad_ws_bytes(N, Cin, Cout, H_, W);
 }
 int umpr_conv3x3_bwd_weight(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int H_, int W,
                             int Cout, float* ws, size_t ws_bytes, void* stream) {
-  return umpr_conv3x3_wgrad(dy, x, dw, db, N, Cin, Cout, H_, W, 0, ws, ws_bytes, S(stream));
+  return umpr_conv3x3_wgrad(dy, x, dw, db, N, Cin, Cout, H_, W, 0, ws, ws_bytes, conv_hints(), S(stream));
 }
 int umpr_maxpool2_fwd(const float* x, float* y, long planes, int H_, int W, void* stream) {
   return umpr_maxpool2_fwd_impl(x, y, planes, H_, W, S(stream));
@@ -514,13 +522,13 @@ int umpr_vgg16_features_fwd(const float* images, const float* const* params, int
     for (int j = 0; j < kConvPerBlock[b]; ++j, ++ci) {
       float* y = acts + L.conv_off[ci];
       const int hw = L.conv_hw[ci];
-      umpr_wino_set_pool_follows(j == kConvPerBlock[b] - 1);   // the block's last convolution feeds the max-pool
-      if (L.v_floats[ci] && !umpr_wino_inference()) umpr_wino_set_v_slot(acts + L.v_off[ci], L.v_floats[ci]);
-      const int rc = umpr_conv3x3_run(x, params[2 * ci], 0, params[2 * ci + 1], nullptr, y, n, L.conv_cin[ci],
-                                      L.conv_cout[ci], hw, hw, 1, ws, ws_bytes / sizeof(float), s);
-      umpr_wino_set_v_slot(nullptr, 0);
-      umpr_wino_set_pool_follows(0);
-      if (rc) return rc;
+      ConvHints hints;
+      hints.inference = t_conv_inference;
+      hints.pool_follows = j == kConvPerBlock[b] - 1;   // the block's last convolution feeds the max-pool
+      if (L.v_floats[ci] && !hints.inference) { hints.v_slot = acts + L.v_off[ci]; hints.v_slot_floats = L.v_floats[ci]; }
+      if (int rc = umpr_conv3x3_run(x, params[2 * ci], 0, params[2 * ci + 1], nullptr, y, n, L.conv_cin[ci], L.conv_cout[ci], hw,
+                                    hw, 1, ws, ws_bytes / sizeof(float), hints, s))
+        return rc;
       x = y;
     }
     const int hw = L.conv_hw[ci - 1];
@@ -762,17 +770,17 @@ int umpr_vgg16_features_bwd(const float* images, const float* const* params, int
       const int cin = L.conv_cin[ci], cout = L.conv_cout[ci];
       const float* xin = ci == 0 ? images : (j == 0 ? acts + L.pool_off[b - 1] : acts + L.conv_off[ci - 1]);
       sched.wgrad_may_start(ci);
-      if (L.v_floats[ci]) umpr_wino_set_v_slot(const_cast<float*>(acts) + L.v_off[ci], L.v_floats[ci]);   // written by the forward
-      const int rcw = umpr_conv3x3_wgrad(g, xin, grads[2 * ci], grads[2 * ci + 1], n, cin, cout, hw, hw, 0, W.scratch,
-                                         W.scratch_bytes, sched.sw);
-      umpr_wino_set_v_slot(nullptr, 0);
-      if (rcw) return rcw;
+      ConvHints hints;   // the slot the training forward of this layer wrote; the call fails unless its plan reads exactly that
+      if (L.v_floats[ci]) { hints.v_slot = const_cast<float*>(acts) + L.v_off[ci]; hints.v_slot_floats = L.v_floats[ci]; }
+      if (int rcw = umpr_conv3x3_wgrad(g, xin, grads[2 * ci], grads[2 * ci + 1], n, cin, cout, hw, hw, 0, W.scratch,
+                                       W.scratch_bytes, hints, sched.sw))
+        return rcw;
       sched.wgrad_enqueued(ci, gslot);
       if (ci == 0) break;
       // input came straight from a conv+ReLU (j > 0): mask by it; from a pool (j == 0): the pool backward masks
       const float* mask = j > 0 ? xin : nullptr;
       cs = sched.claim();
-      if (int rc = umpr_conv3x3_run(g, params[2 * ci], 1, nullptr, mask, W.slot[cs], n, cin, cout, hw, hw, 0, W.wt, W.wt_floats, s))
+      if (int rc = umpr_conv3x3_run(g, params[2 * ci], 1, nullptr, mask, W.slot[cs], n, cin, cout, hw, hw, 0, W.wt, W.wt_floats, ConvHints(), s))
         return rc;
       g = W.slot[cs]; gslot = cs;
     }

@@ -8,9 +8,9 @@
 //  wgrad           : per workgroup a 64(cout) x 64(cin) x 9(tap) tile, K = pixels; the gz tile and the x halo patch
 //                    of a 32-pixel segment are staged once in LDS and serve all nine taps (9 accumulator tiles per
 //                    wave).  Split-K over pixel segments into slabs [split][tap][cout][cin] + deterministic reduce.
-//  dispatch        : umpr_conv3x3_run / umpr_conv3x3_wgrad pick, per layer shape: the first-layer forward kernel
-//                    (Cin <= 3), the Winograd kernels of winograd.hip (56 / 28 / 14 maps with >= 32 channels; backward of conv2_2), the
-//                    LDS-patch implicit GEMM below (VGG map widths), or the generic gather kernel (any other shape).
+//  dispatch        : umpr_conv3x3_plan (below, with the table of layer class x pass x mode) decides once per call between the
+//                    first-layer kernels, the Winograd kernels of winograd.hip, the LDS-patch implicit GEMM and the generic
+//                    gather kernel; umpr_conv3x3_run / umpr_conv3x3_wgrad launch what it names.
 #include "umpr_common.h"
 #include "umpr_internal.h"
 #include "umpr_tiles.h"
@@ -1000,12 +1000,8 @@ __global__ void maxpool2_bwd_relu_kernel(const float* __restrict__ x, const floa
 }  // namespace
 
 // ---- internal host entry points ------------------------------------------------------------------------------
-// UMPR_CONV_WINO=0 keeps the deep layers on the direct kernel (A/B runs)
-static bool conv_no_wino() { static const bool v = !umpr_env_on("UMPR_CONV_WINO"); return v; }
 // UMPR_CONV_BN: 0 auto (128x128 bulk + 128x64 tail), 128 or 64 force one tile shape (A/B runs)
 static int conv_bn() { static const int v = umpr_env_int("UMPR_CONV_BN", 0); return v; }
-// UMPR_CONV_V1=1 selects the generic gather kernel (A/B runs)
-static bool conv_force_v1() { static const bool v = umpr_env_int("UMPR_CONV_V1", 0) == 1; return v; }
 // ---- first layer (Cin <= 3): no LDS, no barriers.  K = 27 is too short for the staged kernels (they pad it to a
 // 144-deep stage and become MFMA-bound on zeros); here every wave keeps its weight fragments in registers for the
 // whole launch and walks over 32-pixel tiles: 14 gathered loads per lane (image planes stay in L2), 14 MFMA k-steps
@@ -1073,59 +1069,172 @@ __global__ __launch_bounds__(256) void conv3x3_fwd_c3_kernel(ConvParams p) {
   }
 }
 
-static bool wino_layer(int H, int W) { return H == W && (W == 56 || W == 28 || W == 14); }
-// 112x112 maps with >= 128 channels on both sides (conv2_2): Winograd in backward only, and only on the F(4x4,3x3) tile -
-// with F(2x2,3x3) the 4x activation-sized transform traffic ate the gain (+1 %); on the larger tile the data gradient and the
-// weight gradient of that layer together save 1.7 ms per step (36.4 -> 34.7 ms).  UMPR_WINO_112 = 0 / 1 overrides.
-static bool wino_112() {
-  static const int v = umpr_env_int("UMPR_WINO_112", -1);
-  return v == 1 || (v < 0 && umpr_wino_f4_mode() >= 1);
+// ---- the plan --------------------------------------------------------------------------------------------------
+// Which kernels a pass of a layer runs (D = LDS-patch direct kernels, C = first-layer kernels, G = generic gather kernels,
+// W2 / W4 = Winograd on the F(2x2,3x3) / F(4x4,3x3) tile), by UMPR_WINO_F4 = 2 (default) | 1 | 0.  "Reduction channels" are
+// Cin in forward, Cout in the data gradient; the weight gradient wants 32 channels on both sides.
+//
+//   layer class                                   forward (training)  forward (inference)  data gradient   weight gradient
+//   Cin <= 3, Cout = 64 (conv1_1)                 C                   C                    D, else G       C (W % 16 == 0)
+//   56 / 28 / 14 maps, >= 32 reduction channels   W4 | W2 | W2        W4 | W4 | W2         W4 | W4 | W2    W4 | W4 | W2 (14: W2)
+//   112 map, >= 128 channels both sides (conv2_2) W4 | D  | D         W4 | W4 | D          W4 | W4 | D     W4 | W4 | D
+//   112 map, Cin >= 64, Cout >= 128 (conv2_1)     D                   W4 | W4 | D          D               W4 | W4 | D
+//   other 224 / 112 / 56 / 28 / 14 maps           D                   D                    D               D
+//   any other shape                               G                   G                    G               G (D: W % 8 or % 14 == 0)
+//
+// Why, row by row.  The 4x4 tile does 4x fewer MFMA FLOPs than the direct kernel (the 2x2 tile 2.25x) and pays where 36 planes
+// over ceil(H/4) x ceil(W/4) tiles are less GEMM work than 16 planes over (H/2) x (W/2) - on 14x14 too, where 3.75 of 16 tiles hang
+// over the border (`edge`).  Its rounding (1-2e-6 of max|y|) is a smooth perturbation in backward, which is linear in its inputs
+// (mode 1); a training forward takes it since the decision fix-up retakes every ReLU / pool decision it could change (mode 2),
+// and an inference forward (ConvHints::inference) has no backward pass reading its decisions.  The weight gradient of the
+// padded 14x14 maps stays on the 2x2 tile: a quarter of the tiles is too short a reduction for the split-K GEMM and the 36-plane
+// finish (0.367 vs 0.353 ms per layer).  At 112x112 only the 4x4 tile pays (with the 2x2 one the 4x activation-sized transform
+// traffic ate the gain), so those rows follow UMPR_WINO_112 (default: on in modes >= 1) and the training forward of conv2_2
+// UMPR_WINO_112_FWD.  conv2_1 has 64 reduction channels in forward: two K stages, bound by V / M traffic, still ahead of the
+// direct kernel (30.9 vs 31.36 ms per step) - but in training its rounding enters the chain one layer earlier and two more ReLU
+// decisions of the golden fixture umpr_full_V1_B2 fall on the other side of float64 (conv1_1 weight gradient 1.5e-2 from the
+// reference, bound 6e-3; tools/count_flips.py --fixture 51,52,2 --chained), so only inference takes it unless
+// UMPR_WINO_C21_FWD = 1 (0: never); its data gradient would write half a GEMM row tile of padding and stays direct.
+// UMPR_CONV_WINO = 0 keeps forward and data gradient off Winograd, UMPR_WGRAD_WINO = 0 the weight gradient, UMPR_CONV_V1 = 1
+// puts every pass on the generic kernels (A/B runs).
+//
+// ws_floats is what a caller reserves for the pass, and what the public size entry points add up.  For a planned Winograd
+// pass it is the Winograd workspace (never smaller than the packed weights); the launcher falls back to plan.direct when the
+// caller brings less and names no V slot.  Two of its terms are only sized for, never reached, and kept because sizes must
+// not move: (1) a forward sizes for the larger of the 2x2 and the 4x4 geometry in modes >= 1; mode 1 reaches both (training,
+// inference), mode 2 only the 4x4 one, so the 2x2 term - the larger, which governs umpr_conv3x3_pack_bytes - is never reached
+// by default; (2) it is taken by map size alone, so a layer with fewer than 32 reduction channels, or any layer under
+// UMPR_CONV_V1 = 1, reserves a Winograd workspace it cannot use.
+//
+// v_floats: the training forward (W4, no edge tiles) computes exactly the transformed input V that the weight gradient of the
+// same layer (W4, same padded channel count) would compute again; both plans then name the size of the slot they share
+// (UMPR_WINO_V_REUSE = 0: never).  Seven of the thirteen VGG16 layers qualify.
+namespace {
+struct ConvSwitches { bool wino, v1, wgrad_wino, w112, w112_fwd, v_reuse; int f4, c21_fwd; };
+ConvSwitches read_conv_switches() {
+  ConvSwitches v;
+  v.wino = umpr_env_on("UMPR_CONV_WINO");
+  v.v1 = umpr_env_int("UMPR_CONV_V1", 0) == 1;
+  v.wgrad_wino = umpr_env_on("UMPR_WGRAD_WINO");
+  v.f4 = umpr_env_int("UMPR_WINO_F4", 2);
+  const int w112 = umpr_env_int("UMPR_WINO_112", -1);
+  v.w112 = w112 == 1 || (w112 < 0 && v.f4 >= 1);
+  v.w112_fwd = umpr_env_int("UMPR_WINO_112_FWD", 1) != 0;
+  v.c21_fwd = umpr_env_int("UMPR_WINO_C21_FWD", -1);
+  v.v_reuse = umpr_env_int("UMPR_WINO_V_REUSE", 1) != 0;
+  return v;
 }
-static bool wino_bwd_layer(int C, int M, int H, int W) {
-  return wino_layer(H, W) || (wino_112() && H == W && W == 112 && C >= 128 && M >= 128);
-}
-// conv2_1 (64 -> 128 @112) in the FORWARD pass: with 64 reduction channels the Winograd GEMM is two K stages and the layer is
-// bound by the V / M traffic, which still undercuts the direct kernel (training step 31.36 -> 30.9 ms, profiles/r03_e_c21_ab.txt).
-// Default: under inference only.  In training its 1-2e-6 rounding enters the chain one layer earlier and every decision
-// downstream sees it: on the golden fixture umpr_full_V1_B2 two more ReLU decisions (features.19 / .21) then fall on the other
-// side of float64 and the conv1_1 weight gradient lands 1.5e-2 from the reference (bound 6e-3) - tools/count_flips.py
-// --fixture 51,52,2 --chained.  UMPR_WINO_C21_FWD = 1 takes it in training too, 0 never.  Its data gradient (64 OUTPUT
-// channels = half a GEMM row tile of padding, written out) stays on the direct kernel.
-static bool wino_fwd_c21(int C, int M, int H, int W, bool inference) {
-  static const int v = umpr_env_int("UMPR_WINO_C21_FWD", -1);
-  return (v == 1 || (v < 0 && inference)) && wino_112() && H == W && W == 112 && C >= 64 && M >= 128;
-}
-static bool wino_fwd_c21_possible(int C, int M, int H, int W) {   // for scratch sizing: does not look at the thread's mode
-  return umpr_env_int("UMPR_WINO_C21_FWD", -1) != 0 && wino_112() && H == W && W == 112 && C >= 64 && M >= 128;
+const ConvSwitches& conv_switches() { static const ConvSwitches v = read_conv_switches(); return v; }
+
+// pixel segment of the direct weight gradient = R rows x CW columns with R*CW <= 32: full MFMA k-utilisation when W is a
+// multiple of 32/16/8
+void wgrad_segment(int W, int* R, int* CW) {
+  // two-row segments keep the halo patch small (72 / 64 positions -> 22 / 16 loads per thread and no register spills;
+  // the one-row 32- and 28-wide variants needed 32 loads and spilled)
+  if (W % 16 == 0) { *R = 2; *CW = 16; }
+  else if (W % 8 == 0) { *R = 4; *CW = 8; }
+  else if (W % 14 == 0) { *R = 2; *CW = 14; }
+  else if (W < 32) { *R = 32 / W; *CW = W; }
+  else { *R = 1; *CW = 32; }
 }
 
-// scratch floats a conv call needs: the packed weights, or (deep layers) the Winograd U / V / M buffers
-size_t umpr_conv3x3_pack_floats(int N, int Cin, int Cout, int H, int W) {
-  const size_t a = (size_t)Cout * ((Cin + V2_CC - 1) / V2_CC) * V2_KC;   // forward pack
-  const size_t b = (size_t)Cin * ((Cout + V2_CC - 1) / V2_CC) * V2_KC;   // transposed pack
-  const size_t c = (size_t)Cin * Cout * 9;                               // plain flip-transpose (generic kernel)
-  size_t m = a > b ? a : b;
-  if (c > m) m = c;
-  if (wino_bwd_layer(Cin, Cout, H, W) && !conv_no_wino()) {
-    const size_t f = umpr_wino_ws_floats(N, Cin, Cout, H, W, 0), t = umpr_wino_ws_floats(N, Cout, Cin, H, W, 1);
-    if (f > m) m = f;
-    if (t > m) m = t;
-  } else if (wino_fwd_c21_possible(Cin, Cout, H, W) && !conv_no_wino()) {
-    const size_t f = umpr_wino_ws_floats(N, Cin, Cout, H, W, 0);
-    if (f > m) m = f;
+struct LayerClass { bool deep, c22, c21, f4_shape; };
+LayerClass layer_class(int Cin, int Cout, int H, int W) {
+  const bool at112 = conv_switches().w112 && H == 112 && W == 112;
+  return {H == W && (W == 56 || W == 28 || W == 14), at112 && Cin >= 128 && Cout >= 128, at112 && Cin >= 64 && Cout >= 128,
+          36L * ((H + 3) / 4) * ((W + 3) / 4) < 16L * (H / 2) * (W / 2)};
+}
+
+// the kernels of a pass that is not on Winograd
+ConvAlgo direct_algo(ConvPass pass, int Cin, int Cout, int H, int W) {
+  if (conv_switches().v1) return CONV_GENERIC;
+  if (pass == CONV_WGRAD) {
+    int R, CW;
+    wgrad_segment(W, &R, &CW);
+    if (R == 2 && CW == 16) return Cin <= 3 ? CONV_C3 : CONV_DIRECT;
+    return (R == 4 && CW == 8) || (R == 2 && CW == 14) ? CONV_DIRECT : CONV_GENERIC;
   }
-  return m;
+  if (pass == CONV_FWD && Cin <= 3 && Cout == 64) return CONV_C3;
+  return H == W && (W == 224 || W == 112 || W == 56 || W == 28 || W == 14) ? CONV_DIRECT : CONV_GENERIC;
 }
 
-// training forward of conv2_2 (128 -> 128 at 112x112): on the 4x4 tile as well since the decision fix-up exists (round 3)
-static bool fwd_wide() {
-  static const int fwd112 = umpr_env_int("UMPR_WINO_112_FWD", 1);
-  return fwd112 && umpr_wino_f4_mode() >= 2;
+ConvAlgo conv_algo(ConvPass pass, int Cin, int Cout, int H, int W, bool inference) {
+  const ConvSwitches& sw = conv_switches();
+  const LayerClass lc = layer_class(Cin, Cout, H, W);
+  bool wino, f4 = sw.f4 >= 1 && lc.f4_shape;
+  if (pass == CONV_FWD) {
+    const bool inf = inference && sw.f4 >= 1;
+    const bool wide = inf || (sw.w112_fwd && sw.f4 >= 2);   // the 112 rows are open to this forward
+    const bool c21 = lc.c21 && (sw.c21_fwd == 1 || (sw.c21_fwd < 0 && inf));
+    wino = sw.wino && Cin >= 32 && (lc.deep || (wide && (lc.c22 || c21)));
+    f4 = f4 && (inf || sw.f4 >= 2);
+  } else if (pass == CONV_DGRAD) {
+    wino = sw.wino && Cout >= 32 && (lc.deep || lc.c22);
+  } else {
+    wino = sw.wgrad_wino && Cin >= 32 && Cout >= 32 && (lc.deep || lc.c22 || lc.c21);
+    f4 = f4 && (H % 4) == 0 && (W % 4) == 0;
+  }
+  if (!wino || sw.v1) return direct_algo(pass, Cin, Cout, H, W);
+  return f4 ? CONV_WINO4 : CONV_WINO2;
 }
-// does a TRAINING forward of this layer take the Winograd path (given the scratch umpr_conv3x3_pack_floats asks for)?  The VGG
-// forward keeps the transformed input of such layers for the weight gradient (umpr_wino_v_floats).
-bool umpr_conv3x3_fwd_is_wino(int Cin, int Cout, int H, int W) {
-  return (fwd_wide() ? wino_bwd_layer(Cin, Cout, H, W) || wino_fwd_c21(Cin, Cout, H, W, false) : wino_layer(H, W)) && !conv_no_wino() && !conv_force_v1() && Cin >= 32;
+
+constexpr int kWgradTargetWgs = 512;  // workgroups per wgrad launch (2 resident per CU): split-K factor = this / tiles
+// Segments and split-K plan of the direct weight gradient; the slabs are [splits][9][Cout][Cin] + [splits][Cout]
+struct WgradGeom { int R, CW, segs_y, segs_x, nsegs, splits, segs_per_split; size_t per_split, bytes; };
+WgradGeom wgrad_geom(int N, int Cin, int Cout, int H, int W) {
+  WgradGeom g;
+  wgrad_segment(W, &g.R, &g.CW);
+  g.segs_y = cdiv(H, g.R); g.segs_x = cdiv(W, g.CW); g.nsegs = N * g.segs_y * g.segs_x;
+  g.splits = cdiv(kWgradTargetWgs, cdiv(Cout, 64) * cdiv(Cin, 64));
+  if (g.splits > g.nsegs) g.splits = g.nsegs;
+  g.segs_per_split = cdiv(g.nsegs, g.splits);
+  g.per_split = ((size_t)9 * Cout * Cin + Cout) * sizeof(float);
+  g.bytes = (size_t)g.splits * g.per_split;
+  return g;
+}
+}  // namespace
+
+ConvPlan umpr_conv3x3_plan(ConvPass pass, int N, int Cin, int Cout, int H, int W, bool inference) {
+  const ConvSwitches& sw = conv_switches();
+  const LayerClass lc = layer_class(Cin, Cout, H, W);
+  ConvPlan p;
+  p.algo = conv_algo(pass, Cin, Cout, H, W, inference);
+  p.direct = direct_algo(pass, Cin, Cout, H, W);
+  p.edge = p.algo == CONV_WINO4 && ((H % 4) != 0 || (W % 4) != 0);
+  p.v_floats = 0;
+  const bool wino = p.algo == CONV_WINO2 || p.algo == CONV_WINO4;
+  if (pass == CONV_WGRAD) {
+    p.ws_floats = wino ? umpr_wino_wgrad_geom(N, Cin, Cout, H, W, p.algo == CONV_WINO4).floats
+                       : wgrad_geom(N, Cin, Cout, H, W).bytes / sizeof(float);
+  } else {
+    const int M = pass == CONV_DGRAD ? Cin : Cout, C = pass == CONV_DGRAD ? Cout : Cin;
+    p.ws_floats = (size_t)M * ((C + V2_CC - 1) / V2_CC) * V2_KC;   // packed weights (>= the generic kernel's flip-transpose)
+    const bool c21_possible = pass == CONV_FWD && lc.c21 && sw.c21_fwd != 0;
+    if (sw.wino && (lc.deep || lc.c22 || c21_possible)) {   // sized by map alone, see (2) above
+      const bool f4 = sw.f4 >= 1 && lc.f4_shape;
+      size_t f = umpr_wino_conv_geom(N, C, M, H, W, f4).floats;
+      if (f4 && pass == CONV_FWD) {                          // both tiles, see (1) above
+        const size_t f2 = umpr_wino_conv_geom(N, C, M, H, W, false).floats;
+        if (f2 > f) f = f2;
+      }
+      if (f > p.ws_floats) p.ws_floats = f;
+    }
+  }
+  // (a weight gradient on the 4x4 tile has no edge tiles, so neither has the forward that shares its V)
+  if (pass != CONV_DGRAD && !(pass == CONV_FWD && inference) && sw.v_reuse &&
+      conv_algo(CONV_FWD, Cin, Cout, H, W, false) == CONV_WINO4 && conv_algo(CONV_WGRAD, Cin, Cout, H, W, false) == CONV_WINO4) {
+    const WinoConvGeom fg = umpr_wino_conv_geom(N, Cin, Cout, H, W, true);
+    const WinoWgradGeom wg = umpr_wino_wgrad_geom(N, Cin, Cout, H, W, true);
+    if (fg.v_floats == (size_t)wg.planes * wg.Cpad * wg.Tpad) p.v_floats = fg.v_floats;   // the two GEMMs pad the channels alike
+  }
+  return p;
+}
+
+// scratch floats the forward and the data gradient of a layer need: the packed weights, or the Winograd U / V / M buffers
+size_t umpr_conv3x3_pack_floats(int N, int Cin, int Cout, int H, int W) {
+  const size_t f = umpr_conv3x3_plan(CONV_FWD, N, Cin, Cout, H, W, false).ws_floats;
+  const size_t t = umpr_conv3x3_plan(CONV_DGRAD, N, Cin, Cout, H, W, false).ws_floats;
+  return f > t ? f : t;
 }
 
 // Forward (transposed = 0):  y[N][Cout] = relu?(conv(x[N][Cin], w) + bias)
@@ -1133,44 +1242,55 @@ bool umpr_conv3x3_fwd_is_wino(int Cin, int Cout, int H, int W) {
 // w is always the parameter [Cout][Cin][3][3]; wpack: scratch of umpr_conv3x3_pack_floats(...) floats.
 int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
                      int N, int Cin, int Cout, int H, int W, int relu, float* wpack, size_t wpack_floats,
-                     hipStream_t s) {
+                     const ConvHints& hints, hipStream_t s) {
   UMPR_REQUIRE(N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0, "conv3x3: bad shape");
+  UMPR_REQUIRE(transposed || !mask, "conv3x3: the forward pass takes no mask");
   const int M = transposed ? Cin : Cout;   // output channels of this launch
   const int C = transposed ? Cout : Cin;   // reduction channels
   const long NP = (long)N * H * W;
-  // in inference the forward pass takes what the backward pass takes (conv2_2 on the 4x4 tile as well)
-  const bool wide = transposed || umpr_wino_inference() || fwd_wide();
-  if ((wide ? wino_bwd_layer(C, M, H, W) || (!transposed && wino_fwd_c21(C, M, H, W, umpr_wino_inference() != 0)) : wino_layer(H, W)) && !conv_no_wino() && !conv_force_v1() && wpack && C >= 32 &&
-      wpack_floats >= umpr_wino_ws_floats(N, C, M, H, W, transposed)) {
-    // Winograd (F(2x2,3x3) forward, F(4x4,3x3) data gradient): 2.25x / 4x fewer MFMA FLOPs; timed under the same family with
-    // the direct conv's FLOP count
-    UmprProfScope prof(transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
-    return umpr_wino_conv3x3(x, w, transposed, bias, mask, y, N, Cin, Cout, H, W, relu, wpack, wpack_floats, s);
-  }
-  if (!transposed && Cin <= 3 && Cout == 64 && !mask && !conv_force_v1()) {
-    ConvParams p{x, w, bias, nullptr, y, N, Cin, H, W, Cout, relu, 0, NP};
-    UmprProfScope prof(UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
-    conv3x3_fwd_c3_kernel<2><<<2048, 256, 0, s>>>(p);
-    UMPR_LAUNCH_CHECK("conv3x3_fwd_c3");
-    return 0;
-  }
-  const bool v2 = H == W && !conv_force_v1() && wpack && (W == 224 || W == 112 || W == 56 || W == 28 || W == 14);
-  if (v2) {
-    const long total = (long)M * ((C + V2_CC - 1) / V2_CC) * V2_KC;
-    UMPR_REQUIRE(wpack_floats >= (size_t)total, "conv3x3: weight scratch too small");
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    pack_weights_kernel<<<blocks, 256, 0, s>>>(w, wpack, M, C, Cin, transposed);
-    UMPR_LAUNCH_CHECK("pack_weights");
-    ConvParams p{x, wpack, bias, mask, y, N, C, H, W, M, relu, 0, NP};
-    UmprProfScope prof(transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
-    if (W == 224) launch_v2<224>(p, conv_bn(), s);
-    else if (W == 112) launch_v2<112>(p, conv_bn(), s);
-    else if (W == 56) launch_v2<56>(p, conv_bn(), s);
-    else if (W == 28) launch_v2<28>(p, conv_bn(), s);
-    else launch_v2<14>(p, conv_bn(), s);
-    UMPR_LAUNCH_CHECK("conv3x3_igemm_v2");
-    return 0;
+  const ConvPlan plan = umpr_conv3x3_plan(transposed ? CONV_DGRAD : CONV_FWD, N, Cin, Cout, H, W, hints.inference);
+  ConvAlgo algo = plan.algo;
+  const bool fits = wpack && wpack_floats >= plan.ws_floats;
+  if (hints.v_slot)   // the weight gradient will read the slot: this call must be the one that writes it
+    UMPR_REQUIRE(algo == CONV_WINO4 && fits && plan.v_floats > 0 && plan.v_floats == hints.v_slot_floats,
+                 "conv3x3: the V slot does not fit this call (%d -> %d at %dx%d, slot %zu floats, plan %zu)", Cin, Cout, H, W,
+                 hints.v_slot_floats, plan.v_floats);
+  else if ((algo == CONV_WINO2 || algo == CONV_WINO4) && !fits) algo = plan.direct;   // scratch of a direct call only
+  if (algo == CONV_DIRECT && !wpack) algo = CONV_GENERIC;                             // a forward without scratch
+  const int family = transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM;   // one family for every algorithm, with the direct
+  const double work = 2.0 * NP * M * C * 9;                                // conv's FLOP count
+  switch (algo) {
+    case CONV_WINO2:
+    case CONV_WINO4: {
+      UmprProfScope prof(family, work, s);
+      return umpr_wino_conv3x3(x, w, transposed, bias, mask, y, N, Cin, Cout, H, W, relu, wpack, wpack_floats,
+                               algo == CONV_WINO4, hints, s);
+    }
+    case CONV_C3: {
+      ConvParams p{x, w, bias, nullptr, y, N, Cin, H, W, Cout, relu, 0, NP};
+      UmprProfScope prof(family, work, s);
+      conv3x3_fwd_c3_kernel<2><<<2048, 256, 0, s>>>(p);
+      UMPR_LAUNCH_CHECK("conv3x3_fwd_c3");
+      return 0;
+    }
+    case CONV_DIRECT: {
+      const long total = (long)M * ((C + V2_CC - 1) / V2_CC) * V2_KC;
+      UMPR_REQUIRE(wpack_floats >= (size_t)total, "conv3x3: weight scratch too small");
+      int blocks = (int)((total + 255) / 256);
+      if (blocks > 4096) blocks = 4096;
+      pack_weights_kernel<<<blocks, 256, 0, s>>>(w, wpack, M, C, Cin, transposed);
+      UMPR_LAUNCH_CHECK("pack_weights");
+      ConvParams p{x, wpack, bias, mask, y, N, C, H, W, M, relu, 0, NP};
+      UmprProfScope prof(family, work, s);
+      if (W == 224) launch_v2<224>(p, conv_bn(), s);
+      else if (W == 112) launch_v2<112>(p, conv_bn(), s);
+      else if (W == 56) launch_v2<56>(p, conv_bn(), s);
+      else if (W == 28) launch_v2<28>(p, conv_bn(), s);
+      else launch_v2<14>(p, conv_bn(), s);
+      UMPR_LAUNCH_CHECK("conv3x3_igemm_v2");
+      return 0;
+    }
+    case CONV_GENERIC: break;
   }
   const float* wm = w;
   if (transposed) {
@@ -1179,7 +1299,7 @@ int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float
     wm = wpack;
   }
   ConvParams p{x, wm, bias, mask, y, N, C, H, W, M, relu, 0, NP};
-  UmprProfScope prof(transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM, 2.0 * NP * M * C * 9, s);
+  UmprProfScope prof(family, work, s);
   if (M <= 64) {
     dim3 grid(cdiv(NP, 128), cdiv(M, 64));
     conv3x3_igemm_kernel<64, 128><<<grid, 256, 0, s>>>(p);
@@ -1200,71 +1320,50 @@ int umpr_conv3x3_flip_transpose(const float* w, float* wt, int Cout, int Cin, hi
   return 0;
 }
 
-constexpr int kWgradTargetWgs = 512;  // workgroups per wgrad launch (2 resident per CU): split-K factor = this / tiles
-
-// pixel segment = R rows x CW columns with R*CW <= 32: full MFMA k-utilisation when W is a multiple of 32/16/8
-static void wgrad_geometry(int W, int* R, int* CW) {
-  // two-row segments keep the halo patch small (72 / 64 positions -> 22 / 16 loads per thread and no register spills;
-  // the one-row 32- and 28-wide variants needed 32 loads and spilled)
-  if (W % 16 == 0) { *R = 2; *CW = 16; }
-  else if (W % 8 == 0) { *R = 4; *CW = 8; }
-  else if (W % 14 == 0) { *R = 2; *CW = 14; }
-  else if (W < 32) { *R = 32 / W; *CW = W; }
-  else { *R = 1; *CW = 32; }
-}
-
-static const bool g_wgrad_wino = umpr_env_on("UMPR_WGRAD_WINO");
-static bool wgrad_wino_layer(int Cin, int Cout, int H, int W) {
-  // conv2_1 (64 -> 128 at 112x112) as well: the weight-gradient GEMM has a 64-wide input-channel tile
-  const bool c21 = wino_112() && H == 112 && W == 112 && Cin >= 64 && Cout >= 128;
-  return g_wgrad_wino && !conv_force_v1() && (wino_bwd_layer(Cin, Cout, H, W) || c21) && Cin >= 32 && Cout >= 32;
-}
-
 size_t umpr_conv3x3_wgrad_ws_bytes(int N, int Cin, int Cout, int H, int W) {
-  if (wgrad_wino_layer(Cin, Cout, H, W)) return umpr_wino_wgrad_ws_floats(N, Cin, Cout, H, W) * sizeof(float);
-  int R, CW;
-  wgrad_geometry(W, &R, &CW);
-  const int nsegs = N * cdiv(H, R) * cdiv(W, CW);
-  const int tiles = cdiv(Cout, 64) * cdiv(Cin, 64);
-  int splits = cdiv(kWgradTargetWgs, tiles);
-  if (splits > nsegs) splits = nsegs;
-  return (size_t)splits * ((size_t)9 * Cout * Cin + Cout) * sizeof(float);
+  return umpr_conv3x3_plan(CONV_WGRAD, N, Cin, Cout, H, W, false).ws_floats * sizeof(float);
 }
 
 int umpr_conv3x3_wgrad(const float* gz, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
-                       int accumulate, float* ws, size_t ws_bytes, hipStream_t s) {
-  if (wgrad_wino_layer(Cin, Cout, H, W) && ws_bytes >= umpr_wino_wgrad_ws_floats(N, Cin, Cout, H, W) * sizeof(float)) {
-    // Winograd F(3x3,2x2) / F(3x3,4x4): 2.25x / 4x fewer MFMA FLOPs; timed under the same family with the direct algorithm's
-    // FLOP count
-    UmprProfScope prof(UMPR_K_CONV_WGRAD, 2.0 * N * H * W * Cout * Cin * 9, s);
-    return umpr_wino_wgrad(gz, x, dw, db, N, Cin, Cout, H, W, accumulate, ws, ws_bytes / sizeof(float), s);
+                       int accumulate, float* ws, size_t ws_bytes, const ConvHints& hints, hipStream_t s) {
+  const ConvPlan plan = umpr_conv3x3_plan(CONV_WGRAD, N, Cin, Cout, H, W, false);
+  ConvAlgo algo = plan.algo;
+  const bool fits = ws_bytes >= plan.ws_floats * sizeof(float);
+  if (hints.v_slot)   // "written by the forward" holds only if that forward ran the plan this call runs
+    UMPR_REQUIRE(algo == CONV_WINO4 && fits && plan.v_floats > 0 && plan.v_floats == hints.v_slot_floats,
+                 "conv3x3 wgrad: the V slot does not match this layer (%d -> %d at %dx%d, slot %zu floats, plan %zu)", Cin, Cout,
+                 H, W, hints.v_slot_floats, plan.v_floats);
+  else if ((algo == CONV_WINO2 || algo == CONV_WINO4) && !fits) algo = plan.direct;   // workspace of a direct call only
+  const double work = 2.0 * N * H * W * Cout * Cin * 9;   // one family for every algorithm, with the direct algorithm's FLOP count
+  if (algo == CONV_WINO2 || algo == CONV_WINO4) {
+    UmprProfScope prof(UMPR_K_CONV_WGRAD, work, s);
+    return umpr_wino_wgrad(gz, x, dw, db, N, Cin, Cout, H, W, accumulate, ws, ws_bytes / sizeof(float), algo == CONV_WINO4, hints, s);
   }
+  const WgradGeom g = wgrad_geom(N, Cin, Cout, H, W);
+  UMPR_REQUIRE(g.R * g.CW <= 32 && (g.R + 2) * (g.CW + 2) <= 102, "wgrad: unsupported width %d", W);
   WgradParams p;
   p.gz = gz; p.x = x; p.N = N; p.Cin = Cin; p.Cout = Cout; p.H = H; p.W = W;
-  wgrad_geometry(W, &p.R, &p.CW);
-  UMPR_REQUIRE(p.R * p.CW <= 32 && (p.R + 2) * (p.CW + 2) <= 102, "wgrad: unsupported width %d", W);
-  p.segs_y = cdiv(H, p.R);
-  p.segs_x = cdiv(W, p.CW);
-  p.nsegs = N * p.segs_y * p.segs_x;
-  const int tiles = cdiv(Cout, 64) * cdiv(Cin, 64);
-  int splits = cdiv(kWgradTargetWgs, tiles);
-  if (splits > p.nsegs) splits = p.nsegs;
-  const size_t per = ((size_t)9 * Cout * Cin + Cout) * sizeof(float);
-  if ((size_t)splits * per > ws_bytes) splits = (int)(ws_bytes / per);
-  UMPR_REQUIRE(splits >= 1, "wgrad: workspace too small (%zu bytes)", ws_bytes);
-  p.segs_per_split = cdiv(p.nsegs, splits);
-  splits = cdiv(p.nsegs, p.segs_per_split);
+  p.R = g.R; p.CW = g.CW; p.segs_y = g.segs_y; p.segs_x = g.segs_x; p.nsegs = g.nsegs; p.segs_per_split = g.segs_per_split;
+  if (g.bytes > ws_bytes) {   // a smaller workspace: fewer, longer splits
+    const int fit = (int)(ws_bytes / g.per_split);
+    UMPR_REQUIRE(fit >= 1, "wgrad: workspace too small (%zu bytes)", ws_bytes);
+    p.segs_per_split = cdiv(g.nsegs, fit);
+  }
+  const int splits = cdiv(p.nsegs, p.segs_per_split);
   p.slab = ws;
   p.bslab = db ? ws + (size_t)splits * 9 * Cout * Cin : nullptr;
   dim3 grid(cdiv(Cin, 64), cdiv(Cout, 64), splits);
   {
-    UmprProfScope prof(UMPR_K_CONV_WGRAD, 2.0 * N * H * W * Cout * Cin * 9, s);
-    if (conv_force_v1()) conv3x3_wgrad_kernel<<<grid, 256, 0, s>>>(p);
-    else if (Cin <= 3 && p.R == 2 && p.CW == 16) conv3x3_wgrad_c3_kernel<2, 16><<<grid, 256, 0, s>>>(p);
-    else if (p.R == 2 && p.CW == 16) conv3x3_wgrad_v2_kernel<2, 16><<<grid, 256, 0, s>>>(p);
-    else if (p.R == 4 && p.CW == 8) conv3x3_wgrad_v2_kernel<4, 8><<<grid, 256, 0, s>>>(p);
-    else if (p.R == 2 && p.CW == 14) conv3x3_wgrad_v2_kernel<2, 14><<<grid, 256, 0, s>>>(p);
-    else conv3x3_wgrad_kernel<<<grid, 256, 0, s>>>(p);
+    UmprProfScope prof(UMPR_K_CONV_WGRAD, work, s);
+    switch (algo) {
+      case CONV_C3: conv3x3_wgrad_c3_kernel<2, 16><<<grid, 256, 0, s>>>(p); break;
+      case CONV_DIRECT:
+        if (g.R == 2 && g.CW == 16) conv3x3_wgrad_v2_kernel<2, 16><<<grid, 256, 0, s>>>(p);
+        else if (g.R == 4) conv3x3_wgrad_v2_kernel<4, 8><<<grid, 256, 0, s>>>(p);
+        else conv3x3_wgrad_v2_kernel<2, 14><<<grid, 256, 0, s>>>(p);
+        break;
+      default: conv3x3_wgrad_kernel<<<grid, 256, 0, s>>>(p);
+    }
   }
   UMPR_LAUNCH_CHECK("conv3x3_wgrad");
   return umpr_wgrad_reduce(p.slab, p.bslab, splits, Cout, Cin, dw, db, accumulate, s);

@@ -82,30 +82,42 @@ struct UmprHead {
 };
 int umpr_head_launch(const UmprHead& p, int backward, hipStream_t s);
 
-// conv3x3.hip
+// conv3x3.hip - the fp32 3x3 convolutions.  umpr_conv3x3_plan is the ONE place that decides which kernels a (pass, shape) runs,
+// on which Winograd tile, and how much scratch it needs; the launchers and every size entry point consume its answer.
+enum ConvPass { CONV_FWD = 0, CONV_DGRAD = 1, CONV_WGRAD = 2 };
+enum ConvAlgo { CONV_GENERIC = 0 /* gather kernel, any shape */, CONV_C3 = 1 /* first-layer kernels */,
+                CONV_DIRECT = 2 /* LDS-patch v2 kernels, VGG map widths */, CONV_WINO2 = 3, CONV_WINO4 = 4 };
+// What only the caller knows about a call.  inference: no backward pass will read this forward's decisions; pool_follows: a 2x2
+// max-pool reads this forward's output; v_slot: where a training forward on the 4x4 tile leaves its transformed input and the
+// weight gradient of the same layer reads it back (v_slot_floats must equal the plan's v_floats).
+struct ConvHints { bool inference = false, pool_follows = false; float* v_slot = nullptr; size_t v_slot_floats = 0; };
+struct ConvPlan {
+  ConvAlgo algo;
+  ConvAlgo direct;    // what runs instead when the caller's scratch is too small for the planned Winograd call
+  bool edge;          // CONV_WINO4 with tiles that hang over the border of the map
+  size_t ws_floats;   // scratch to reserve for this pass (see the comment on umpr_conv3x3_plan)
+  size_t v_floats;    // size of the V slot the training forward and the weight gradient of this layer share (0: none)
+};
+ConvPlan umpr_conv3x3_plan(ConvPass pass, int N, int Cin, int Cout, int H, int W, bool inference);
 size_t umpr_conv3x3_pack_floats(int N, int Cin, int Cout, int H, int W);
 int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
                      int N, int Cin, int Cout, int H, int W, int relu, float* wpack, size_t wpack_floats,
-                     hipStream_t s);
-// winograd.hip
-size_t umpr_wino_ws_floats(int N, int C, int M, int H, int W, int transposed);
-void umpr_wino_set_inference(int on);   // per host thread, see umpr_set_conv_inference
-void umpr_wino_set_pool_follows(int on);   // per host thread, see umpr_set_conv_pool_follows
+                     const ConvHints& hints, hipStream_t s);
+// winograd.hip - geometry and workspace (offsets in floats) of one Winograd call on the tile the plan names, and the launchers
+struct WinoConvGeom { int planes, MT, S; long T, Tpad; bool edge; size_t v_floats, U, V, M, count, tie, floats; };
+WinoConvGeom umpr_wino_conv_geom(int N, int C, int M, int H, int W, bool f4);
+struct WinoWgradGeom { long T, Tpad; int MT, CT, Mpad, Cpad, stages, splits, stages_per_split, planes, bnc; size_t Gy, V, P, BP, floats; };
+WinoWgradGeom umpr_wino_wgrad_geom(int N, int Cin, int Cout, int H, int W, bool f4);
 long umpr_wino_last_fix_count();            // see umpr_debug_wino_fix_count
-void umpr_wino_set_v_slot(float* p, size_t floats);   // per host thread: where a training forward keeps V for the weight gradient
-size_t umpr_wino_v_floats(int N, int Cin, int Cout, int H, int W);   // 0: the layer's V is not shared
-bool umpr_conv3x3_fwd_is_wino(int Cin, int Cout, int H, int W);     // the training forward of this layer runs Winograd
-int umpr_wino_inference();
-int umpr_wino_f4_mode();   // UMPR_WINO_F4: 0 = F(2x2,3x3) only, 1 = F(4x4,3x3) in the backward pass, 2 = forward as well
-size_t umpr_wino_wgrad_ws_floats(int N, int Cin, int Cout, int H, int W);
 int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
-                    int accumulate, float* ws, size_t ws_floats, hipStream_t s);
+                    int accumulate, float* ws, size_t ws_floats, bool f4, const ConvHints& hints, hipStream_t s);
 int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
-                      int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, hipStream_t s);
+                      int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, bool f4,
+                      const ConvHints& hints, hipStream_t s);
 int umpr_conv3x3_flip_transpose(const float* w, float* wt, int Cout, int Cin, hipStream_t s);
 size_t umpr_conv3x3_wgrad_ws_bytes(int N, int Cin, int Cout, int H, int W);
 int umpr_conv3x3_wgrad(const float* gz, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
-                       int accumulate, float* ws, size_t ws_bytes, hipStream_t s);
+                       int accumulate, float* ws, size_t ws_bytes, const ConvHints& hints, hipStream_t s);
 int umpr_maxpool2_fwd_impl(const float* x, float* y, long planes, int H, int W, hipStream_t s);
 int umpr_maxpool2_bwd_relu_impl(const float* x, const float* gy, float* gx, long planes, int H, int W, hipStream_t s);
 

@@ -1,20 +1,17 @@
-// Winograd path for the deep VGG16 layers (56x56, 28x28, 14x14 maps; in backward also conv2_2 at 112x112), fp32.
+// Winograd kernels of the fp32 3x3 convolutions.  Which layer and pass runs them, and on which tile, is decided by
+// umpr_conv3x3_plan (conv3x3.hip: the table above it); this file launches what the plan names.
 //
-// Forward, F(2x2,3x3):   Y = A^T [ (G g G^T) .* (B^T d B) ] A   per 2x2 output tile / 4x4 input tile
+// Forward / data gradient, F(2x2,3x3):   Y = A^T [ (G g G^T) .* (B^T d B) ] A   per 2x2 output tile / 4x4 input tile
 //   16 independent GEMMs  M[xi][m][t] = sum_c U[xi][m][c] * V[xi][c][t]  (t = tile index over the batch) replace the
 //   9-tap implicit GEMM: 2.25x fewer MFMA FLOPs.  Kernels per layer call:
 //     wino_weights_kernel      : U = G g G^T (for dgrad on the flipped, channel-transposed kernel), LDS image order
 //     wino_input[_pair]_kernel : x -> V   (HBM bound: reads |x|, writes 4|x|; zero-pads channels / tiles to the GEMM tile)
 //     wino_gemm_dma_kernel     : batched GEMM on v_mfma_f32_32x32x2_f32, operands copied global -> LDS by LDS-DMA
 //     wino_output[_pair]_kernel: M -> y   with the fused epilogue (+bias, ReLU) or (dgrad) * [mask > 0]
-// Data gradient, F(4x4,3x3) where the map is a multiple of 4 (wino4_* kernels, the same GEMM over 36 planes and a quarter of
-//   the tiles: 4x fewer FLOPs, V / M 2.25x instead of 4x the activation), else F(2x2,3x3) as in forward.  The forward pass
-//   keeps the 2x2 tile: the larger tile's rounding (5e-6 of max|y| instead of 3e-7) flips ReLU / pool decisions and moves
-//   the early layers' gradients outside the parity bound; in backward it is a smooth perturbation (UMPR_WINO_F4, below).
+// F(4x4,3x3) (wino4_* kernels): the same GEMM over 36 planes and a quarter of the tiles: 4x fewer FLOPs, V / M 2.25x instead
+//   of 4x the activation.  Its rounding (1-2e-6 of max|y| instead of 3e-7) is a smooth perturbation in backward; a training
+//   forward on it retakes every ReLU / pool decision the rounding could change at the direct kernel's accuracy (WinoFix).
 // Weight gradient, F(3x3,2x2) / F(3x3,4x4): see the second half of this file (wino[4]_dy / wino_wgrad_gemm / finish).
-// The 224x224 layers, conv2_1 and the forward pass of conv2_2 stay on the direct kernels of conv3x3.hip: with 64 channels
-// on one side the batched GEMM is HBM-bound on V / M, and in forward the 4x transform traffic of the 2x2 tile costs more
-// than the MFMA time it saves.
 #include <type_traits>
 
 #include "umpr_common.h"
@@ -845,41 +842,6 @@ inline int nblk(long n, int cap) {
 
 }  // namespace
 
-// UMPR_WINO_F4: 0 = F(2x2,3x3) everywhere; 1 = F(4x4,3x3) for the data gradient only (the round-2 default);
-// 2 (default since round 3) = the training forward as well.  The backward pass is linear in its inputs (the ReLU / pool
-// decisions were taken in forward), so the larger tile's rounding stays a ~1e-6 perturbation of the gradient.  In FORWARD the
-// same rounding would flip several times more ReLU / max-pool decisions than the direct kernel's 1.7e-7 does (round 2, textbook
-// points: the first layers' gradients of golden umpr_full_V1_B2_randnM moved to 5e-3 relative L2 from the float64 run where the
-// reference's own fp32 is at 1.5e-3).  Round 3 removes the cause twice over: better-conditioned interpolation points (half the
-// rounding) and the decision fix-up of wino4_output_kernel / wino_fixup_kernel, which retakes every decision the tile's rounding
-// could change at the direct kernel's accuracy (the same fixture: 8e-4; tools/count_flips.py counts the decisions).
-int umpr_wino_f4_mode() {
-  static const int mode = umpr_env_int("UMPR_WINO_F4", 2);   // function-local: also read by conv3x3.hip's initialisers
-  return mode;
-}
-// Inference (umpr_set_conv_inference, per host thread): no backward pass will read this forward's ReLU / pool decisions,
-// so the forward pass may take the larger tile as well - predictions move by 3e-6 (bound 1e-4).
-static thread_local int t_wino_infer = 0;
-void umpr_wino_set_inference(int on) { t_wino_infer = on; }
-int umpr_wino_inference() { return t_wino_infer && umpr_wino_f4_mode() >= 1; }
-// The 4x4 tile pays where 36 planes over ceil(H/4) x ceil(W/4) tiles are less GEMM work than 16 planes over (H/2) x (W/2):
-// always on maps that are a multiple of 4, and on 14x14 (16 tiles of which 3.75 hang over the border: 576 vs 784 plane-tiles).
-static inline bool wino_f4_shape(int H, int W) {
-  return 36L * ((H + 3) / 4) * ((W + 3) / 4) < 16L * (H / 2) * (W / 2);
-}
-// A 2x2 max-pool follows this forward convolution (set by the VGG16 forward around conv3_3 / conv4_3 / conv5_3; thread-local
-// like the inference hint): the decision fix-up then also covers the pool windows' argmax (see WinoFix).
-static thread_local int t_wino_pool_follows = 0;
-void umpr_wino_set_pool_follows(int on) { t_wino_pool_follows = on; }
-// V slot (round 3): the transformed input V = B^T d B of a training forward on the 4x4 tile is exactly what the weight gradient
-// of the same layer transforms again in backward (same input, same tile, same padded layout).  When the caller names a buffer
-// that outlives the forward (umpr_vgg16_features_fwd: a region of the activation arena), the forward GEMM reads its B operand
-// from there and the weight gradient skips its own input transform (seven of the ten Winograd layers qualify; ~0.9 ms of pure
-// HBM traffic per step for 2.7 GB of arena at batch 64).  Per host thread, like the other hints.
-static thread_local float* t_v_slot = nullptr;
-static thread_local size_t t_v_slot_floats = 0;
-void umpr_wino_set_v_slot(float* p, size_t floats) { t_v_slot = p; t_v_slot_floats = floats; }
-
 // test / tooling aid: the list counter of this host thread's most recent fix-up pass (device memory inside that call's workspace)
 static thread_local const unsigned int* t_last_fix_count = nullptr;
 long umpr_wino_last_fix_count() {
@@ -888,18 +850,13 @@ long umpr_wino_last_fix_count() {
   if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(&v, t_last_fix_count, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -2;
   return (long)v;
 }
-static inline bool wino_f4_map(int H, int W, int transposed) {
-  const int need = transposed || t_wino_infer ? 1 : 2;
-  return umpr_wino_f4_mode() >= need && wino_f4_shape(H, W);
-}
 
-// Geometry and workspace of one Winograd convolution: 16 planes over 2x2 tiles, or 36 planes over 4x4 tiles where the map
-// allows F(4x4,3x3).  Offsets in floats:  U [planes][MT*128][S*32] | V [planes][S*32][Tpad] | M [planes][MT*128][Tpad] |
+// Geometry and workspace of one Winograd convolution: 16 planes over 2x2 tiles, or (f4: the tile umpr_conv3x3_plan chose) 36
+// planes over 4x4 tiles.  Offsets in floats:  U [planes][MT*128][S*32] | V [planes][S*32][Tpad] | M [planes][MT*128][Tpad] |
 // 64 words for the fix-up counter | on the 4x4 tile, one word of tie bits per tile (the word in front of them, inside the 64:
 // the input's largest magnitude).  The fix-up LIST aliases the V region on purpose: it is free once the GEMM has read it, or at
 // once when V itself lives in the caller's slot.
-struct WinoConvGeom { int planes, MT, S; long T, Tpad; bool edge; size_t v_floats, U, V, M, count, tie, floats; };
-static WinoConvGeom wino_conv_geom(int N, int C, int M, int H, int W, bool f4) {
+WinoConvGeom umpr_wino_conv_geom(int N, int C, int M, int H, int W, bool f4) {
   WinoConvGeom g;
   g.planes = f4 ? 36 : 16; g.edge = f4 && ((H % 4) != 0 || (W % 4) != 0);
   g.T = f4 ? (long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long)N * (H / 2) * (W / 2);
@@ -910,46 +867,24 @@ static WinoConvGeom wino_conv_geom(int N, int C, int M, int H, int W, bool f4) {
   g.floats = g.count + 64 + (f4 ? g.Tpad : 0);
   return g;
 }
-size_t umpr_wino_ws_floats(int N, int C, int M, int H, int W, int transposed) {
-  const bool map4 = wino_f4_shape(H, W);
-  const int mode = umpr_wino_f4_mode();
-  if (!map4 || mode == 0) return wino_conv_geom(N, C, M, H, W, false).floats;
-  if (transposed) return wino_conv_geom(N, C, M, H, W, true).floats;
-  // forward: the 2x2 tile (mode 1 training; in mode 2 the layers a max-pool follows) or the 4x4 one (mode 2; inference)
-  const size_t a = wino_conv_geom(N, C, M, H, W, false).floats, b = wino_conv_geom(N, C, M, H, W, true).floats;
-  return a > b ? a : b;
-}
 
-// floats of the forward V of a layer whose weight gradient can read it back (0: the layer does not qualify): training forward
-// and weight gradient both on the 4x4 tile over the same tile grid, and the two GEMMs' channel paddings agree
-size_t umpr_wino_v_floats(int N, int Cin, int Cout, int H, int W) {
-  if (umpr_wino_f4_mode() < 2 || !wino_f4_shape(H, W) || (H % 4) != 0 || (W % 4) != 0) return 0;
-  static const int on = umpr_env_int("UMPR_WINO_V_REUSE", 1);
-  if (!on) return 0;
-  const long S = (Cin + WK - 1) / WK;
-  const long bnc = Cin <= 64 ? 64 : WBN;
-  if (S * WK != (Cin + bnc - 1) / bnc * bnc) return 0;
-  const long T = (long)N * (H / 4) * (W / 4);
-  return (size_t)36 * S * WK * wino_tpad(T);
-}
 
 // forward (transposed = 0) or data gradient (transposed = 1), same contract as umpr_conv3x3_run
 int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
-                      int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, hipStream_t s) {
+                      int N, int Cin, int Cout, int H, int W, int relu, float* ws, size_t ws_floats, bool f4,
+                      const ConvHints& hints, hipStream_t s) {
   const int M = transposed ? Cin : Cout;
   const int C = transposed ? Cout : Cin;
-  UMPR_REQUIRE(ws_floats >= umpr_wino_ws_floats(N, C, M, H, W, transposed), "winograd: workspace too small");
+  const WinoConvGeom G = umpr_wino_conv_geom(N, C, M, H, W, f4);
+  UMPR_REQUIRE(ws_floats >= G.floats, "winograd: workspace too small");
   UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd: odd map %dx%d", H, W);
-  const bool f4 = wino_f4_map(H, W, transposed);
-  const WinoConvGeom G = wino_conv_geom(N, C, M, H, W, f4);
   const int planes = G.planes, MT = G.MT, S = G.S;
   const long T = G.T, Tpad = G.Tpad; const bool edge = G.edge;
   float *U = ws + G.U, *V = ws + G.V, *Mx = ws + G.M, *list_region = ws + G.V;
-  if (t_v_slot && !transposed) {
-    const size_t vfl = umpr_wino_v_floats(N, Cin, Cout, H, W);
-    UMPR_REQUIRE(f4 && !t_wino_infer && vfl > 0 && vfl == G.v_floats && t_v_slot_floats >= vfl,
+  if (hints.v_slot) {   // umpr_conv3x3_run has checked the slot against the plan; this is the layout it must match
+    UMPR_REQUIRE(f4 && !edge && !transposed && hints.v_slot_floats == G.v_floats,
                  "winograd: the V slot does not fit this forward (%d -> %d at %dx%d)", Cin, Cout, H, W);
-    V = t_v_slot;
+    V = hints.v_slot;
   }
   if (f4) wino4_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed, wino4_consts());
   else wino_weights_kernel<<<nblk((long)MT * WBM * S * WK, 2048), 256, 0, s>>>(w, U, M, C, Cin, transposed);
@@ -961,7 +896,7 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
   // proportion - 6e-6 of the outputs on the golden fixtures' images, 3e-3 on the benchmark's i.i.d.-noise images, whose deep
   // feature maps are nearly flat (neighbouring outputs differ by ~3e-3 of their magnitude), at kappa = 8.
   static const int kappa = umpr_env_int("UMPR_WINO_FIX_KAPPA", 8);   // 0 disables
-  const bool fix = f4 && !transposed && !t_wino_infer && kappa > 0 && mask == nullptr;
+  const bool fix = f4 && !transposed && !hints.inference && kappa > 0 && mask == nullptr;
   WinoFix fx{nullptr, nullptr, 0u, 0.f, nullptr};
   unsigned int* tie_bits = nullptr;
   if (fix) {
@@ -970,7 +905,7 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
     fx.cap = (unsigned)(G.v_floats < (size_t)0x7fffffff ? G.v_floats : (size_t)0x7fffffff);
     fx.kappa_eps = (float)kappa * 5.9604644775390625e-08f;
     UMPR_REQUIRE((long)N * M * H * W < 0xffffffffL, "winograd fix-up: output tensor too large for 32-bit element indices");
-    if (t_wino_pool_follows) {
+    if (hints.pool_follows) {
       tie_bits = reinterpret_cast<unsigned int*>(ws + G.tie);   // tie_bits[-1]: the input's largest magnitude
       if (hipMemsetAsync(tie_bits - 1, 0, (size_t)(T + 1) * sizeof(unsigned int), s) != hipSuccess) { umpr_set_error("winograd fix-up: memset"); return -2; }
       UMPR_REQUIRE(((long)N * C * H * W) % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0, "winograd fix-up: unaligned input");
@@ -1508,15 +1443,13 @@ __global__ void wino_wgrad_finish_kernel(const float* __restrict__ P, int splits
 
 constexpr int kWinoWgradTargetWgs = 1024;
 static const int g_wino_wgrad_rounds = umpr_env_int("UMPR_WINO_WGRAD_ROUNDS", 1);   // 0: the plain 1024-workgroup target
+}  // namespace
 
-// workspace (offsets in floats): Gy [planes][Mpad][Tpad] | V [planes][Cpad][Tpad] | P [splits][planes][Mpad][Cpad] | BP, the bias
+// Geometry of one Winograd weight gradient on the tile umpr_conv3x3_plan chose (f4: F(3x3,4x4), else F(3x3,2x2)).  Workspace
+// (offsets in floats): Gy [planes][Mpad][Tpad] | V [planes][Cpad][Tpad] | P [splits][planes][Mpad][Cpad] | BP, the bias
 // partials [Mpad][Tpad / 64] (+ 64)
-struct WinoWgradGeom { long T, Tpad; int MT, CT, Mpad, Cpad, stages, splits, stages_per_split, planes, bnc; size_t Gy, V, P, BP, floats; };
-WinoWgradGeom wino_wgrad_geom(int N, int Cin, int Cout, int H, int W) {
+WinoWgradGeom umpr_wino_wgrad_geom(int N, int Cin, int Cout, int H, int W, bool f4) {
   WinoWgradGeom g;
-  // padded 14x14 maps stay on F(3x3,2x2): a quarter of the tiles is too short a reduction for the split-K GEMM and the 36-plane
-  // finish (measured 0.367 vs 0.353 ms per layer), while the data gradient gains (0.312 vs 0.351 ms)
-  const bool f4 = wino_f4_map(H, W, 1) && (H % 4) == 0 && (W % 4) == 0;
   g.planes = f4 ? 36 : 16;
   g.T = f4 ? (long)N * ((H + 3) / 4) * ((W + 3) / 4) : (long)N * (H / 2) * (W / 2);
   g.Tpad = wino_tpad(g.T);
@@ -1556,17 +1489,12 @@ WinoWgradGeom wino_wgrad_geom(int N, int Cin, int Cout, int H, int W) {
   return g;
 }
 
-}  // namespace
-
-size_t umpr_wino_wgrad_ws_floats(int N, int Cin, int Cout, int H, int W) { return wino_wgrad_geom(N, Cin, Cout, H, W).floats; }
-
 int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N, int Cin, int Cout, int H, int W,
-                    int accumulate, float* ws, size_t ws_floats, hipStream_t s) {
-  const WinoWgradGeom g = wino_wgrad_geom(N, Cin, Cout, H, W);
+                    int accumulate, float* ws, size_t ws_floats, bool f4, const ConvHints& hints, hipStream_t s) {
+  const WinoWgradGeom g = umpr_wino_wgrad_geom(N, Cin, Cout, H, W, f4);
   UMPR_REQUIRE(ws_floats >= g.floats, "winograd wgrad: workspace too small");
   UMPR_REQUIRE((H % 2) == 0 && (W % 2) == 0, "winograd wgrad: odd map %dx%d", H, W);
   float *Gy = ws + g.Gy, *V = ws + g.V, *P = ws + g.P, *BP = ws + g.BP;   // BP: per-wave bias partial sums of the dy transform
-  const bool f4 = g.planes == 36;
   // rows m >= Cout of Gy are never written: every P element is a dot product of ONE Gy row with ONE V row, so garbage
   // stays in rows of P that the finish kernel does not read.
   const bool edge = f4 && ((H % 4) != 0 || (W % 4) != 0);
@@ -1582,11 +1510,11 @@ int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N
   else
     wino_dy_kernel<<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad);
   UMPR_LAUNCH_CHECK("wino_dy");
-  if (t_v_slot) {   // the forward pass left this layer's transformed input in the caller's slot
-    const size_t vfl = umpr_wino_v_floats(N, Cin, Cout, H, W);
-    UMPR_REQUIRE(f4 && !edge && vfl == (size_t)g.planes * g.Cpad * g.Tpad && t_v_slot_floats >= vfl,
+  if (hints.v_slot) {   // the forward pass left this layer's transformed input in the caller's slot (checked against the plan
+                        // by umpr_conv3x3_wgrad; this is the layout it must match)
+    UMPR_REQUIRE(f4 && !edge && hints.v_slot_floats == (size_t)g.planes * g.Cpad * g.Tpad,
                  "winograd wgrad: the V slot does not match this layer (%d -> %d at %dx%d)", Cin, Cout, H, W);
-    V = t_v_slot;
+    V = hints.v_slot;
   } else if (f4 && edge)
     wino4_input_kernel<true, false><<<nblk((long)g.Cpad * g.Tpad, 16384), 256, 0, s>>>(x, V, N, Cin, g.Cpad, H, W, g.Tpad, g.Tpad, wino4_consts(), nullptr, nullptr);
   else if (f4)
