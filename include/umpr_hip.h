@@ -88,8 +88,9 @@ int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
                              const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
                              const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
                              float* out, float* saved, float* ws, size_t ws_bytes, void* stream);
-/* dout [N][L][128]; d* receive the parameter gradients (overwritten).  The embedding table is frozen
- * (nn.Embedding.from_pretrained, model.py:237) so no gradient is produced for it. */
+/* dout [N][L][128]; d* receive the parameter gradients (overwritten).  No gradient is produced for the embedding table (the
+ * reference's default: nn.Embedding.from_pretrained, model.py:237); umpr_embed_gru_bidir_bwd_dx below hands out the token
+ * gradient a trainable table needs. */
 int umpr_embed_gru_bidir_bwd(const int64_t* ids, const float* emb, int E,
                              const float* w_hh_f, const float* w_hh_r,
                              const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
@@ -108,6 +109,42 @@ int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E,
                                  float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
                                  float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
                                  int accumulate, float* ws, size_t ws_bytes, void* stream);
+
+/* The same, and the gradient of the embedded tokens for a TRAINABLE table (nn.Embedding.from_pretrained(..., freeze=False)):
+ * dx [N*L][E] = dgx[:, 0:192] W_ih_f + dgx[:, 192:384] W_ih_r, overwritten (dx_accumulate = 0) or added onto (!= 0).  Two products
+ * on the generic GEMM, in fp32 whatever umpr_set_gemm_bf16 says.  Positions past a sequence's length receive exact zeros (their
+ * dgx is zero).  dx = NULL: w_ih_* are not read and the call is umpr_embed_gru_bidir_bwd_acc launch for launch; the eight
+ * parameter gradients are bit-identical either way.  Same workspace (umpr_embed_gru_bidir_ws_bytes). */
+int umpr_embed_gru_bidir_bwd_dx(const int64_t* ids, const float* emb, int E,
+                                const float* w_hh_f, const float* w_hh_r,
+                                const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                                const float* dout, const float* out, const float* saved,
+                                float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
+                                float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
+                                int accumulate, const float* w_ih_f, const float* w_ih_r, float* dx, int dx_accumulate,
+                                float* ws, size_t ws_bytes, void* stream);
+
+/* ---- gradient of the embedding table: d_emb [vocab][E] = scatter-add of token gradients, deterministic, no atomics ----------
+ * Up to 4 sources k of T_k tokens each: ids[k] int64 [T_k], dx[k] fp32 [T_k][E] (what umpr_embed_gru_bidir_bwd_dx and the two
+ * *_net_bwd_dx calls hand out).  ids / dx / counts are HOST arrays of n_src device pointers / token counts, read during the
+ * call.  sorted_pos: device int32 [T], T = sum of T_k - the positions 0..T-1 of the concatenated sources, STABLE-sorted by id
+ * (torch.sort(cat(ids), stable=True).indices as int32).
+ * d_emb is OVERWRITTEN WHOLE: every row is written exactly once, a row no token names becomes +0.0 (no zeroing pass is needed
+ * before the call).  Row v = the sum of dx over the positions whose id is v, chained in fp32 from +0.0 in ascending position
+ * order; the sorted order is cut at every multiple of umpr_embed_grad_chunk() positions, a run of one id that crosses such a cut
+ * is summed piece by piece and the pieces are then added in order.  Where the cuts fall is a function of the sorted ids alone -
+ * not of the grid, the scheduling or the device - so the result is bit-reproducible (the rule of umpr_grad_norm), and the same
+ * tokens give the same bits however they are split into sources.
+ * Ids live in device memory, so none is known to the host and none is refused: an id outside [0, vocab) contributes to NO row
+ * and nothing is written for it.  A sorted_pos entry outside [0, T) is skipped likewise; with a sorted_pos that is not the
+ * stable sort the values are unspecified, but no access leaves the buffers.  T = 0 (or n_src = 0) gives an all-zero table and
+ * needs no workspace.  Any E >= 1 and vocab >= 1; row offsets are 64-bit; T < 2^31 - 512.
+ * ws: umpr_embed_grad_ws_bytes(T, E) bytes, 8-byte aligned (pure host arithmetic: the ids behind the sorted positions, two
+ * piece sums per umpr_embed_grad_chunk() positions).  No allocation, no copy, no host synchronisation: capture-safe. */
+int umpr_embed_grad_chunk(void);
+size_t umpr_embed_grad_ws_bytes(long T, int E);
+int umpr_embed_grad(const int64_t* const* ids, const float* const* dx, const long* counts, int n_src, int E, long vocab,
+                    const int32_t* sorted_pos, float* d_emb, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K4-K5: R-Net co-attention (model.py:50-55) --------------------------------------------------------------
  * Gu, Gi [B][SL][128]; M [128][128].  Outputs soft_u/soft_i [B][SL], atte_u/atte_i rows of 128 written at
@@ -202,6 +239,11 @@ int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const 
 int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
                         float* const* grads, float* ws, size_t ws_bytes, void* stream);
+/* umpr_review_net_bwd that also hands out the token gradient of the user+item pair, dx_pair [2N*L][E] (overwritten; see
+ * umpr_embed_gru_bidir_bwd_dx).  dx_pair = NULL is umpr_review_net_bwd.  Same workspace. */
+int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
+                           const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
+                           float* const* grads, float* dx_pair, float* ws, size_t ws_bytes, void* stream);
 size_t umpr_control_net_arena_bytes(int B, int S_ui, int L_ui, int S, int L, int KC, int V);
 size_t umpr_control_net_ws_bytes(int B, int S_ui, int L_ui, int S, int L, int E, int KC, int KS, int V);
 /* params (16): the C-Net GRU's eight, Wc [KC][128][KS], bc, Wl [V][KC], bl, Ms, Ws, ssW [128], ssb [1];
@@ -215,6 +257,13 @@ int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
                          int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
                          const float* d_ci, const float* d_pp, const float* d_pn, float* const* grads, float* ws, size_t ws_bytes,
                          void* stream);
+/* umpr_control_net_bwd that also hands out the token gradients of the C-Net GRU's two calls: dx_pair [2N*L][E] and
+ * dx_ui [B*S_ui*L_ui][E] (each overwritten; both NULL is umpr_control_net_bwd, one NULL is refused).  Same workspace. */
+int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* params,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
+                            int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
+                            const float* d_ci, const float* d_pp, const float* d_pn, float* const* grads, float* dx_pair,
+                            float* dx_ui, float* ws, size_t ws_bytes, void* stream);
 
 /* ---- K10: VGG16-D feature extractor (torchvision.models.vgg16, call site model.py:204-207,217) ---------------
  * images [n][3][224][224]; params: 32 pointers = 13 x (conv weight [Cout][Cin][3][3], bias) then 3 x (fc weight

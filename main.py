@@ -5,6 +5,7 @@
     python main.py --data_dir synthetic --learning_rate 1e-3 --grad_clip 5.0  # clip the gradient to a global 2-norm of 5
     python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
                                                                                   # for every photo kept in 1 GB of HBM
+    python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
 
 The model / optimiser / train / evaluate drivers are the MI355X-native ones (umpr_amd).  With a data_dir that holds
@@ -180,13 +181,15 @@ def main():
 # options the reference does not have
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
-                 "freeze_vgg": False, "feature_store_gb": 0.0}
+                 "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False}
 
 
 def check_flags(config):
     """Refuses, at start-up, combinations of options that cannot work."""
     if not isinstance(config.freeze_vgg, bool):
         sys.exit(f"--freeze_vgg takes True or False, got {config.freeze_vgg!r}")
+    if not isinstance(config.train_embedding, bool):
+        sys.exit(f"--train_embedding takes True or False, got {config.train_embedding!r}")
     if config.feature_store_gb < 0:
         sys.exit(f"--feature_store_gb must be >= 0, got {config.feature_store_gb}")
     if config.feature_store_gb > 0 and not config.freeze_vgg:

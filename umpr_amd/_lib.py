@@ -27,6 +27,10 @@ SIGNATURES = {
     "umpr_embed_gru_bidir_fwd": ("ppipppppppppppiipppzp", "i"),
     "umpr_embed_gru_bidir_bwd": ("ppipppppiippppppppppppzp", "i"),
     "umpr_embed_gru_bidir_bwd_acc": ("ppipppppiipppppppppppipzp", "i"),
+    "umpr_embed_gru_bidir_bwd_dx": ("ppipppppiipppppppppppipppipzp", "i"),
+    "umpr_embed_grad_chunk": ("", "i"),
+    "umpr_embed_grad_ws_bytes": ("li", "z"),
+    "umpr_embed_grad": ("pppiilpppzp", "i"),
     "umpr_coattention_fwd_ws_bytes": ("ii", "z"),
     "umpr_coattention_fwd": ("pppiipppplplpppppzp", "i"),
     "umpr_coattention_fwd_bf16": ("pppiipppplplpppppzp", "i"),
@@ -90,10 +94,12 @@ SIGNATURES = {
     "umpr_review_net_ws_bytes": ("iiii", "z"),
     "umpr_review_net_fwd": ("ppipppiiiiiipppzp", "i"),
     "umpr_review_net_bwd": ("ppipppiiiippppzp", "i"),
+    "umpr_review_net_bwd_dx": ("ppipppiiiipppppzp", "i"),
     "umpr_control_net_arena_bytes": ("iiiiiii", "z"),
     "umpr_control_net_ws_bytes": ("iiiiiiiii", "z"),
     "umpr_control_net_fwd": ("pppipppppiiiiiiiifiippppppzp", "i"),
     "umpr_control_net_bwd": ("pppipppppiiiiiiiiipppppppzp", "i"),
+    "umpr_control_net_bwd_dx": ("pppipppppiiiiiiiiipppppppppzp", "i"),
     "umpr_head_fwd": ("pppppppppppppfiiipppppppp", "i"),
     "umpr_head_bwd": ("pppppppppppfiiippppppppppppppppppppp", "i"),
     "umpr_photo_resize_u8": ("pzpiiipp", "i"),

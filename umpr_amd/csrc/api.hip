@@ -252,12 +252,14 @@ int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
   return umpr_gru_recurrent_fwd(gx, w_hh_f, b_hh_f, w_hh_r, b_hh_r, lengths, order, dst_row, out, saved, N, L, S(stream));
 }
 
-int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
-                                 const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
-                                 const float* dout, const float* out, const float* saved,
-                                 float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
-                                 float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
-                                 int accumulate, float* ws, size_t ws_bytes, void* stream) {
+int umpr_embed_gru_bidir_bwd_dx(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
+                                const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                                const float* dout, const float* out, const float* saved,
+                                float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
+                                float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
+                                int accumulate, const float* w_ih_f, const float* w_ih_r, float* dx, int dx_accumulate,
+                                float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(dx == nullptr || (w_ih_f != nullptr && w_ih_r != nullptr), "embed_gru_bwd: dx needs w_ih_f and w_ih_r");
   UMPR_REQUIRE(dout != nullptr && out != nullptr && saved != nullptr, "embed_gru_bwd: dout / out / saved must not be NULL");
   UMPR_REQUIRE(ws_bytes >= umpr_embed_gru_bidir_ws_bytes(N, L, E), "embed_gru_bwd: workspace too small");
   const int tiles = umpr_gru_tiles(N), Ep = emb_pitch(E);
@@ -297,7 +299,28 @@ int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E, co
     unstack_dwih_kernel<<<cdiv(2 * G3 * E, 256), 256, 0, S(stream)>>>(stacked, E, Ep, dwih[0], dwih[1], accumulate);
     UMPR_LAUNCH_CHECK("unstack_dwih");
   }
+  if (dx) {  // token gradient for a trainable table: dx = dgx[:, 0:192] W_ih_f + dgx[:, 192:384] W_ih_r, fp32 in both precisions
+    UmprF32Scope f32;
+    const float* wih[2] = {w_ih_f, w_ih_r};
+    for (int d = 0; d < 2; ++d) {
+      UmprGemm g;
+      g.A = dgx + d * G3; g.lda = 384; g.B = wih[d]; g.ldb = E;
+      g.C = dx; g.ldc = E; g.M = N * L; g.N = E; g.K = G3; g.accumulate = d == 1 || dx_accumulate != 0;
+      if (int rc = umpr_gemm(g, S(stream))) return rc;
+    }
+  }
   return 0;
+}
+
+int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
+                                 const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                                 const float* dout, const float* out, const float* saved,
+                                 float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
+                                 float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
+                                 int accumulate, float* ws, size_t ws_bytes, void* stream) {
+  return umpr_embed_gru_bidir_bwd_dx(ids, emb, E, w_hh_f, w_hh_r, lengths, order, dst_row, N, L, dout, out, saved, dw_ih_f,
+                                     dw_hh_f, db_ih_f, db_hh_f, dw_ih_r, dw_hh_r, db_ih_r, db_hh_r, accumulate, nullptr, nullptr,
+                                     nullptr, 0, ws, ws_bytes, stream);
 }
 
 int umpr_embed_gru_bidir_bwd(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,

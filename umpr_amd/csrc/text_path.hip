@@ -176,10 +176,10 @@ int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const 
   return 0;
 }
 
-// grads: 15 pointers in the order of params, each overwritten
-int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
-                        const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
-                        float* const* G, float* ws, size_t ws_bytes, void* stream) {
+// grads: 15 pointers in the order of params, each overwritten; dx_pair (or NULL): the token gradient for a trainable table
+int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                           const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
+                           float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(ids_pair && emb && P && G && lengths && order && arena && d_out, "review_net_bwd: bad arguments");
   const ReviewWs W = review_ws(ws, B, S, L, E);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "review_net_bwd: workspace too small");
@@ -205,8 +205,13 @@ int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const 
   if (int rc = umpr_coattention_bwd(gru_u, gru_i, P[8], A.T, A.soft_u, A.soft_i, A.colmax, A.argcol, A.rowmax, A.argrow, d_repr_u,
                                     2 * D, d_repr_i, 2 * D, ds_u, ds_i, B, (int)SL, dGu, dGi, G[8], 1, sws, swsb, stream)) return rc;
   debug_sync(4);
-  return umpr_embed_gru_bidir_bwd_acc(ids_pair, emb, E, P[1], P[5], lengths, order, order, (int)(2 * N), L, dG, A.gru_out, A.gru_saved,
-                                      G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, sws, swsb, stream);
+  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], lengths, order, order, (int)(2 * N), L, dG, A.gru_out, A.gru_saved,
+                                     G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_pair, 0, sws, swsb, stream);
+}
+int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                        const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
+                        float* const* G, float* ws, size_t ws_bytes, void* stream) {
+  return umpr_review_net_bwd_dx(ids_pair, emb, E, P, lengths, order, B, S, L, b16_gemm, arena, d_out, G, nullptr, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------------------------------------------------------ ControlNet
@@ -253,11 +258,13 @@ int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
 }
 
 // d_cu, d_ci, d_pp, d_pn [B][V]; grads: 16 pointers in the order of params, each overwritten
-int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
-                         const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
-                         int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
-                         const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* ws, size_t ws_bytes,
-                         void* stream) {
+// dx_pair / dx_ui (both or neither): the token gradients of the C-Net GRU's two calls for a trainable table
+int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
+                            int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
+                            const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* dx_pair, float* dx_ui,
+                            float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE((dx_pair == nullptr) == (dx_ui == nullptr), "control_net_bwd: dx_pair and dx_ui go together");
   UMPR_REQUIRE(ids_ui && ids_pair && emb && P && G && arena && d_cu && d_ci && d_pp && d_pn, "control_net_bwd: bad arguments");
   const ControlWs W = control_ws(ws, B, S_ui, L_ui, S, L, E, KC, KS, V);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "control_net_bwd: workspace too small");
@@ -281,10 +288,19 @@ int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
   for (int q = 0; q < 3; ++q)   // the ui head adds onto the S-Net's dX and writes the weight gradients; the other two add onto those
     if (int rc = umpr_cnet_head_bwd(X[q], P[8], P[10], A.h[q].cmax, A.h[q].argl, A.h[q].sp, A.h[q].vp, dfin[q], dvp[q], B, ss[q], ll[q],
                                     KC, KS, V, dX[q], q == 0 ? 1 : 0, q == 0 ? 0 : 1, G[8], G[9], G[10], G[11], sws, swsb, stream)) return rc;
-  if (int rc = umpr_embed_gru_bidir_bwd_acc(ids_ui, emb, E, P[1], P[5], len_ui, ord_ui, ord_ui, (int)Nui, L_ui, dX_ui, A.gru_ui, A.saved_ui,
-                                            G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, sws, swsb, stream)) return rc;
-  return umpr_embed_gru_bidir_bwd_acc(ids_pair, emb, E, P[1], P[5], len_pair, ord_pair, ord_pair, (int)(2 * N), L, dX_pair, A.gru_pair,
-                                      A.saved_pair, G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 1, sws, swsb, stream);
+  if (int rc = umpr_embed_gru_bidir_bwd_dx(ids_ui, emb, E, P[1], P[5], len_ui, ord_ui, ord_ui, (int)Nui, L_ui, dX_ui, A.gru_ui, A.saved_ui,
+                                           G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_ui, 0, sws, swsb, stream)) return rc;
+  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], len_pair, ord_pair, ord_pair, (int)(2 * N), L, dX_pair, A.gru_pair,
+                                     A.saved_pair, G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 1, P[0], P[4], dx_pair, 0, sws, swsb,
+                                     stream);
+}
+int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                         const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
+                         int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
+                         const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* ws, size_t ws_bytes,
+                         void* stream) {
+  return umpr_control_net_bwd_dx(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, len_pair, ord_pair, B, S_ui, L_ui, S, L, KC, KS, V, b16_gemm,
+                                 arena, d_cu, d_ci, d_pp, d_pn, G, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -30,6 +30,13 @@ struct UmprB16Scope {
   ~UmprB16Scope() { umpr_gemm_set_b16(prev); }
 };
 
+// ... and in fp32 while alive, whatever the host thread's setting (the embedding-gradient products)
+struct UmprF32Scope {
+  int prev;
+  UmprF32Scope() : prev(umpr_gemm_b16()) { umpr_gemm_set_b16(0); }
+  ~UmprF32Scope() { umpr_gemm_set_b16(prev); }
+};
+
 constexpr int D = 128, H = 64, G3 = 192, AT = 64;   // text path: token feature 2 * gru_size, gru_size, its 3 gates, self_atte_size
 bool umpr_merge_small();   // UMPR_MERGE_SMALL=0: the review merge on the fc kernels / the generic GEMM (api.hip)
 

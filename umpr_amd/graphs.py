@@ -14,7 +14,7 @@ What changes from step to step lives in ONE device buffer the graph reads:
 
 Results are bit-identical to the eager step (tests/test_gpu_e2e.py::test_graphed_umpr_r_step_equals_eager).
 
-Not for the full model: its VGG backward forks onto the library's weight-gradient stream and its early Adam step onto another,
+Not with a trainable embedding table (config.train_embedding): the constructor refuses it.  Not for the full model: its VGG backward forks onto the library's weight-gradient stream and its early Adam step onto another,
 and it is GPU-bound anyway (31 ms of kernels behind 4 ms of host issue)."""
 from __future__ import annotations
 
@@ -33,6 +33,9 @@ def _align(n, a=256):
 class GraphedTrainStep:
     def __init__(self, model: UMPR, opt, example_batch):
         assert model.review_net_only, "GraphedTrainStep captures the UMPR-R step (see the module docstring)"
+        if model.embedding.weight.requires_grad:
+            raise NotImplementedError("GraphedTrainStep does not capture a step with a trainable embedding table (train_embedding): "
+                                      "its per-step sort of the token ids is not part of the captured graph; use train_step")
         dev = model.embedding.weight.device
         u, i, ui, ul, il, uil, photos, labels = example_batch
         self.model, self.opt, self.dev = model, opt, dev

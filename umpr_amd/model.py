@@ -368,12 +368,75 @@ class _PadMaps:
 # --------------------------------------------------------------------------------------------- fused text path
 # UMPR.forward issues the text path through these two Functions: ONE C call per direction each (csrc/text_path.hip), one arena
 # tensor saved for backward.  The stage-level Functions above remain the unit the parity tests pin kernel by kernel.
+class _EmbedStep:
+    """What one forward of a model with a TRAINABLE embedding table (config.train_embedding) leaves for its backward: the token
+    ids of every use of the table, in the fixed source order R-Net pair, C-Net pair, C-Net ui (the first only in UMPR-R), their
+    positions stable-sorted by id, and - filled in by the two text nodes' backward - the token gradients dx."""
+    R_PAIR, C_PAIR, C_UI = 0, 1, 2
+
+    def __init__(self, ids):
+        self.ids = [i.reshape(-1) for i in ids]
+        # the sort is plumbing, like the sentence permutation: equal ids keep their position order, so each table row's run is
+        # a function of the ids alone
+        flat = self.ids[0] if len(self.ids) == 1 else torch.cat(self.ids)
+        self.sorted_pos = torch.sort(flat, stable=True).indices.to(torch.int32)
+        self.dx = [None] * len(self.ids)
+        self.ready = []       # one event per text node, recorded behind its dx: the scatter's stream waits for them
+
+    def produced(self, slot, dx):
+        self.dx[slot] = dx
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dx.device))
+        self.ready.append(ev)
+
+
+class _EmbedTable(torch.autograd.Function):
+    """The trainable embedding table as ONE upstream node of the step: its output is a one-element token both text nodes take as an
+    input, so autograd runs this backward once per step, after both of them - and that backward is the scatter of their token
+    gradients into d_emb (umpr_embed_grad: every row of the table written exactly once, no atomics, no zeroing pass)."""
+
+    @staticmethod
+    def forward(ctx, weight, step):
+        ctx.step = step
+        ctx.weight_obj = weight
+        ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
+        ctx.set_materialize_grads(False)
+        return torch.empty(1, device=weight.device, dtype=torch.float32)
+
+    @staticmethod
+    def backward(ctx, _):
+        step, weight = ctx.step, ctx.weight_obj
+        vocab, E = weight.shape
+        dev = weight.device
+        # the join: autograd runs this node on the stream its forward ran on - the text side stream, like both text nodes - and
+        # whichever stream a text node's backward did run on, this one waits for the event recorded behind its dx
+        cur = torch.cuda.current_stream(dev)
+        for ev in step.ready:
+            cur.wait_event(ev)
+        step.ready = []
+        # a text node whose backward did not run (its outputs reached no loss) contributed nothing: zeros for its tokens
+        dx = [d if d is not None else torch.zeros(i.numel(), E, device=dev) for d, i in zip(step.dx, step.ids)]
+        tg, direct = _grad_targets((weight,))
+        n = len(dx)
+        T = sum(i.numel() for i in step.ids)
+        keep_i, iarr = _ptr_array(step.ids)
+        keep_d, darr = _ptr_array(dx)
+        counts = (ctypes.c_long * n)(*[i.numel() for i in step.ids])
+        ws, wsb = _ws(lib().size("umpr_embed_grad_ws_bytes", T, E), dev)
+        lib().call("umpr_embed_grad", iarr, darr, ctypes.cast(counts, ctypes.c_void_p), n, E, vocab, step.sorted_pos, tg[0], ws, wsb,
+                   stream_ptr())
+        step.dx = [None] * n
+        if ctx.on_side and direct[0]:
+            note_gradients_written(dev)     # in place, from the side stream both text nodes ran on: umpr_amd/streams.py
+        return _grad_returns((weight,), tg, direct)[0], None
+
+
 class _ReviewNetF(torch.autograd.Function):
     """The whole ReviewNet (src/model.py:157-169) on the user+item pair: params = the R-Net GRU's eight, M, Ms_u, Ws_u, Ms_i,
     Ws_i, W_u, W_i."""
 
     @staticmethod
-    def forward(ctx, ids_pair, lens, order, emb, dims, b16_gemm, b16_scores, *params):
+    def forward(ctx, ids_pair, lens, order, emb, dims, b16_gemm, b16_scores, tok, step, *params):
         B, S, L = dims
         E = emb.shape[1]
         dev = ids_pair.device
@@ -388,6 +451,7 @@ class _ReviewNetF(torch.autograd.Function):
         ctx.param_objs = params
         ctx.meta = (B, S, L, int(b16_gemm))
         ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
+        ctx.step = step if tok is not None else None     # a trainable table: the backward also hands out the token gradient
         if need:
             ctx.save_for_backward(ids_pair, lens, order, emb, arena, *cp)
         return out
@@ -401,11 +465,17 @@ class _ReviewNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_review_net_ws_bytes", B, S, L, E), ids_pair.device)
         keep_p, parr = _ptr_array(cp)
         keep_g, garr = _ptr_array(tg)
-        lib().call("umpr_review_net_bwd", ids_pair, emb, E, parr, lens, order, B, S, L, b16, arena, _c(d_out), garr, ws, wsb,
-                   stream_ptr())
+        if ctx.step is None:
+            lib().call("umpr_review_net_bwd", ids_pair, emb, E, parr, lens, order, B, S, L, b16, arena, _c(d_out), garr, ws, wsb,
+                       stream_ptr())
+        else:
+            dx = torch.empty(ids_pair.numel(), E, device=ids_pair.device, dtype=torch.float32)
+            lib().call("umpr_review_net_bwd_dx", ids_pair, emb, E, parr, lens, order, B, S, L, b16, arena, _c(d_out), garr, dx, ws,
+                       wsb, stream_ptr())
+            ctx.step.produced(_EmbedStep.R_PAIR, dx)
         if ctx.on_side and any(direct):
             note_gradients_written(ids_pair.device)     # in-place gradients from the side stream: umpr_amd/streams.py
-        return (None, None, None, None, None, None, None, *_grad_returns(ctx.param_objs, tg, direct))
+        return (None,) * 9 + tuple(_grad_returns(ctx.param_objs, tg, direct))
 
 
 class _ControlNetF(torch.autograd.Function):
@@ -413,7 +483,7 @@ class _ControlNetF(torch.autograd.Function):
     control S-Net Ms / Ws, SS-Net weight / bias.  Returns (c_u, c_i, prefer_pos, prefer_neg)."""
 
     @staticmethod
-    def forward(ctx, ids_ui, ids_pair, lens_ui, ord_ui, lens, order, emb, dims, thr, b16_gemm, *params):
+    def forward(ctx, ids_ui, ids_pair, lens_ui, ord_ui, lens, order, emb, dims, thr, b16_gemm, tok, step, *params):
         B, S_ui, L_ui, S, L = dims
         E = emb.shape[1]
         KC, _, KS = params[8].shape
@@ -431,6 +501,7 @@ class _ControlNetF(torch.autograd.Function):
         ctx.param_objs = params
         ctx.meta = (B, S_ui, L_ui, S, L, KC, KS, V, int(b16_gemm))
         ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
+        ctx.step = step if tok is not None else None
         ctx.set_materialize_grads(False)
         if need:
             ctx.save_for_backward(ids_ui, ids_pair, lens_ui, ord_ui, lens, order, emb, arena, *cp)
@@ -447,11 +518,19 @@ class _ControlNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_control_net_ws_bytes", B, S_ui, L_ui, S, L, E, KC, KS, V), dev)
         keep_p, parr = _ptr_array(cp)
         keep_g, garr = _ptr_array(tg)
-        lib().call("umpr_control_net_bwd", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L, KC, KS,
-                   V, b16, arena, d[0], d[1], d[2], d[3], garr, ws, wsb, stream_ptr())
+        if ctx.step is None:
+            lib().call("umpr_control_net_bwd", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L, KC,
+                       KS, V, b16, arena, d[0], d[1], d[2], d[3], garr, ws, wsb, stream_ptr())
+        else:
+            dx_pair = torch.empty(ids_pair.numel(), E, device=dev, dtype=torch.float32)
+            dx_ui = torch.empty(ids_ui.numel(), E, device=dev, dtype=torch.float32)
+            lib().call("umpr_control_net_bwd_dx", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L,
+                       KC, KS, V, b16, arena, d[0], d[1], d[2], d[3], garr, dx_pair, dx_ui, ws, wsb, stream_ptr())
+            ctx.step.dx[_EmbedStep.C_UI] = dx_ui
+            ctx.step.produced(_EmbedStep.C_PAIR, dx_pair)
         if ctx.on_side and any(direct):
             note_gradients_written(dev)
-        return (None,) * 10 + tuple(_grad_returns(ctx.param_objs, tg, direct))
+        return (None,) * 12 + tuple(_grad_returns(ctx.param_objs, tg, direct))
 
 
 # --------------------------------------------------------------------------------------------- K10
@@ -871,7 +950,13 @@ class UMPR(nn.Module):
         self._pad_maps = None
         self._static_index = None
         self.views = list(getattr(config, "views", []))
-        self.embedding = nn.Embedding.from_pretrained(torch.Tensor(word_emb))
+        # not in the reference's configuration, but a one-word change there (from_pretrained(..., freeze=False)): `--train_embedding
+        # True` fine-tunes the word vectors.  The table's gradient is produced once per step by _EmbedTable, in fp32 in both
+        # precisions; it is written whole, straight into the optimiser's arena.
+        self.train_embedding = bool(getattr(config, "train_embedding", False))
+        self.embedding = nn.Embedding.from_pretrained(torch.Tensor(word_emb), freeze=not self.train_embedding)
+        if self.train_embedding:
+            self.embedding.weight._umpr_direct = True
         E = self.embedding.embedding_dim
         self.review_net = ReviewNet(E, config.gru_size, config.self_atte_size)
         if config.review_net_only:
@@ -1091,10 +1176,17 @@ class UMPR(nn.Module):
             else:
                 ids_pair = torch.empty(2 * N, L, device=device, dtype=torch.int64)
                 lib().call("umpr_concat_ids", user_reviews, item_reviews, N * L, ids_pair, stream_ptr())
-            rr = _ReviewNetF.apply(ids_pair, lens, order, emb, (B, S, L), b16_gemm, b16_scores, *self._review_params(device))
+            tok = step = None
+            if emb.requires_grad and torch.is_grad_enabled():
+                # a trainable table: one upstream node both text nodes depend on; its backward scatters their token gradients
+                step = _EmbedStep((ids_pair, ids_pair, ui_reviews) if full else (ids_pair,))
+                tok = _EmbedTable.apply(emb, step)
+                emb = emb.detach()
+            rr = _ReviewNetF.apply(ids_pair, lens, order, emb, (B, S, L), b16_gemm, b16_scores, tok, step,
+                                   *self._review_params(device))
             if full:
                 cu, ci, pp, pn = _ControlNetF.apply(ui_reviews.view(B * S_ui, L_ui), ids_pair, lens_ui, ord_ui, lens, order, emb,
-                                                    (B, S_ui, L_ui, S, L), self.control_net.c_net.threshold, b16_gemm,
+                                                    (B, S_ui, L_ui, S, L), self.control_net.c_net.threshold, b16_gemm, tok, step,
                                                     *self._control_params(device))
         _TEXT_TLS.on_side = False
         fus_w = self._fusion_weight(device)

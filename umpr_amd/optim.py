@@ -375,7 +375,8 @@ class FusedAdam:
 
     def check_state_dict(self, st):
         """Raises unless `st` holds Adam moments for exactly the parameters this optimiser trains, in their sizes - a checkpoint
-        written with the VGG frozen resumed with it trainable, or the other way round, does not."""
+        written with the VGG frozen resumed with it trainable, or the other way round, does not; nor does one written under the other
+        --train_embedding setting."""
         for key in ("m", "v"):
             have = {n: int(t.numel()) for n, t in st[key].items()}
             want = {n: g.offsets[n][1] for g in self.groups for n in g.names}
@@ -386,6 +387,11 @@ class FusedAdam:
                 hint = (" (the checkpoint was written with the VGG " + ("frozen" if any(n in missing for n in vgg) else "trainable")
                         + ", this run has it " + ("trainable" if any(n in missing for n in vgg) else "frozen")
                         + ": pass the same --freeze_vgg)") if vgg else ""
+                table = [n for n in missing + extra if n == "embedding.weight" or n.endswith(".embedding.weight")]
+                if table:
+                    hint += (" (the checkpoint was written with the embedding table "
+                             + ("frozen" if any(n in missing for n in table) else "trainable") + ", this run has it "
+                             + ("trainable" if any(n in missing for n in table) else "frozen") + ": pass the same --train_embedding)")
                 raise ValueError(f"optimizer state does not match the trainable parameters{hint}: {len(missing)} parameters "
                                  f"without moments {missing[:3]}, {len(extra)} moments without a trainable parameter {extra[:3]}, "
                                  f"{len(sized)} of another size {sized[:3]}")

@@ -67,7 +67,7 @@ class _PretrainHead(torch.autograd.Function):
 class PretrainRNet(nn.Module):
     def __init__(self, word2vec, gru_hidden):
         super().__init__()
-        self.embedding = nn.Embedding.from_pretrained(torch.Tensor(word2vec.embedding))
+        self.embedding = nn.Embedding.from_pretrained(torch.Tensor(word2vec.embedding))   # frozen here, whatever --train_embedding says
         self.r_net = RNet(word2vec.word_dim, gru_hidden)
         self.linear = nn.Sequential(nn.Linear(gru_hidden * 4, 1), nn.Sigmoid())
 
