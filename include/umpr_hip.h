@@ -146,6 +146,31 @@ size_t umpr_embed_grad_ws_bytes(long T, int E);
 int umpr_embed_grad(const int64_t* const* ids, const float* const* dx, const long* counts, int n_src, int E, long vocab,
                     const int32_t* sorted_pos, float* d_emb, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- the same gradient kept SPARSE, and row-wise Adam on the rows it names (torch.optim.SparseAdam on nn.Embedding(sparse=True))
+ * umpr_embed_grad_rows: sources, sorted_pos, E and vocab as for umpr_embed_grad.  Outputs over the T SORTED positions: row_id
+ * int64 [T], row_grad fp32 [T][E].  Every position j is written exactly once: if j begins a run (of equal ids) whose id lies in
+ * [0, vocab), row_id[j] is that id and row_grad[j] the run's sum - BIT-EQUAL to the row umpr_embed_grad writes for the same
+ * inputs (the same cuts, the same order inside a piece and over the pieces); otherwise row_id[j] = -1 and row_grad[j] is +0.0 in
+ * every column, so the whole of row_grad can be one more arena of umpr_grad_norm.  Nothing of size vocab is read or written; no
+ * atomics.  T = 0 is a successful no-op (row_id / row_grad / ws may be NULL).  Refused before any launch: a null source table or
+ * source, a null sorted_pos / row_id / row_grad with T > 0, E < 1, vocab < 1, a workspace below
+ * umpr_embed_grad_rows_ws_bytes(T, E) bytes or not 8-byte aligned.  No allocation, no copy, no host synchronisation.
+ *
+ * umpr_sparse_adam_rows: for every j in [0, T) with 0 <= row_id[j] < vocab, and g = row_grad[j] * grad_scale,
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p -= lr sqrt(1 - beta2^step) / (1 - beta1^step) * m / (sqrt(v) + eps)
+ * on row row_id[j] of p, m, v [vocab][E] - SparseAdam's form: eps is added to sqrt(v) itself, there is no weight decay, and a row
+ * no j names keeps every byte of p, m and v.  The row ids must be distinct (umpr_embed_grad_rows makes them so): each row is then
+ * read and written by one wave alone.  clip_state: NULL, or the 8-float state of umpr_grad_norm - the scale is then the one float
+ * product grad_scale * state[COEF] (COEF == 1: bit-identical to NULL) and state[FINITE] == 0 writes nothing.  p, m, v: any
+ * float-aligned base.  Refused before the launch: E < 1, vocab < 1, step < 1, T < 0, a null pointer with T > 0; T = 0 is a
+ * successful no-op.  No allocation, no copy: capture-safe. */
+size_t umpr_embed_grad_rows_ws_bytes(long T, int E);
+int umpr_embed_grad_rows(const int64_t* const* ids, const float* const* dx, const long* counts, int n_src, int E, long vocab,
+                         const int32_t* sorted_pos, int64_t* row_id, float* row_grad, void* ws, size_t ws_bytes, void* stream);
+int umpr_sparse_adam_rows(float* p, float* m, float* v, long vocab, int E, const int64_t* row_id, const float* row_grad, long T,
+                          double lr, double beta1, double beta2, double eps, long step, double grad_scale,
+                          const float* clip_state /*or NULL*/, void* stream);
+
 /* ---- K4-K5: R-Net co-attention (model.py:50-55) --------------------------------------------------------------
  * Gu, Gi [B][SL][128]; M [128][128].  Outputs soft_u/soft_i [B][SL], atte_u/atte_i rows of 128 written at
  * atte_x + b*ld_x (lets the caller place them inside the [B][256] concat of model.py:166-167).

@@ -6,6 +6,7 @@
     python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
                                                                                   # for every photo kept in 1 GB of HBM
     python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
+    python main.py --data_dir data/music --train_embedding True --sparse_embedding True   # ... updating only the rows a step names
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
 
 The model / optimiser / train / evaluate drivers are the MI355X-native ones (umpr_amd).  With a data_dir that holds
@@ -181,7 +182,7 @@ def main():
 # options the reference does not have
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
-                 "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False}
+                 "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False}
 
 
 def check_flags(config):
@@ -190,6 +191,11 @@ def check_flags(config):
         sys.exit(f"--freeze_vgg takes True or False, got {config.freeze_vgg!r}")
     if not isinstance(config.train_embedding, bool):
         sys.exit(f"--train_embedding takes True or False, got {config.train_embedding!r}")
+    if not isinstance(config.sparse_embedding, bool):
+        sys.exit(f"--sparse_embedding takes True or False, got {config.sparse_embedding!r}")
+    if config.sparse_embedding and not config.train_embedding:
+        sys.exit("--sparse_embedding needs --train_embedding True: it chooses how a trainable table is updated (the rows a step "
+                 "names only, as torch.optim.SparseAdam would)")
     if config.feature_store_gb < 0:
         sys.exit(f"--feature_store_gb must be >= 0, got {config.feature_store_gb}")
     if config.feature_store_gb > 0 and not config.freeze_vgg:

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """What does a trainable embedding table (UMPR(train_embedding=True), `--train_embedding True`) cost per training step?
 
-For every workload two model / optimiser pairs live in ONE process, table frozen and trainable, and take turns in blocks of
---steps steps (host clock around a block that ends in a device synchronise), so that both see the same machine; the median block
-of --rounds rounds is reported per side, and the spread (min .. max) next to it.  What the option adds to a step: two fp32 GEMMs
-per GRU backward (the token gradient dx), one id sort, umpr_embed_grad, and vocab * E more elements in the Adam step.  Before the
-steps umpr_embed_grad is timed alone with device events on the first workload's token ids (random dx): it reads T * E floats and
-writes vocab * E.
+For every workload three model / optimiser pairs live in ONE process - table frozen ("off"), trainable with the dense update
+("on"), trainable with the sparse update (`--sparse_embedding True`, "sparse") - and take turns in blocks of --steps steps (host
+clock around a block that ends in a device synchronise), in an order that rotates from round to round, so that all see the same
+machine; the median block of --rounds rounds is reported per side, and the spread (min .. max) next to it.  What the dense option
+adds to a step: two fp32 GEMMs per GRU backward (the token gradient dx), one id sort, umpr_embed_grad, and vocab * E more elements
+in the Adam step.  The sparse one replaces the last two by umpr_embed_grad_rows and umpr_sparse_adam_rows, which touch T * E
+elements, and allocates no gradient arena for the table (vocab * E * 4 bytes).  Before the steps umpr_embed_grad,
+umpr_embed_grad_rows and umpr_sparse_adam_rows are timed alone with device events on the workload's token ids (random dx).
 
     python tools/bench_embed_grad.py [--workloads umpr_r,full_f32,full_bf16_e300] [--rounds 7] [--steps 10] [--warmup 3]
 
@@ -38,14 +40,15 @@ WORKLOADS = {
 VOCAB = 400003
 
 
-def build(w, dev, train_embedding):
+def build(w, dev, train_embedding, sparse_embedding=False):
     torch.manual_seed(0)
-    Config.extend({"dtype": "fp32", "train_embedding": False})
+    Config.extend({"dtype": "fp32", "train_embedding": False, "sparse_embedding": False})
     cfg = Config(argv=[])
     cfg.review_net_only = w["review_net_only"]
     cfg.views = ["v0"]
     cfg.dtype = w["dtype"]
     cfg.train_embedding = train_embedding
+    cfg.sparse_embedding = sparse_embedding
     P = make_param_state(0, w["emb"], VOCAB, 1, w["review_net_only"])
     model = UMPR(cfg, P["embedding.weight"].numpy())
     model.load_state_dict(P)
@@ -58,7 +61,8 @@ def build(w, dev, train_embedding):
 
 
 def time_scatter(batch, w, dev, reps=20):
-    """Device-event time of umpr_embed_grad (its three launches) on the workload's token sources, and of the id sort."""
+    """Device-event time of umpr_embed_grad (its three launches), of umpr_embed_grad_rows and umpr_sparse_adam_rows on the
+    workload's token sources, and of the id sort."""
     L = lib()
     E = w["emb"]
     pair = torch.cat([batch[0].reshape(-1), batch[1].reshape(-1)])
@@ -80,8 +84,21 @@ def time_scatter(batch, w, dev, reps=20):
         L.call("umpr_embed_grad", ctypes.addressof(iarr), ctypes.addressof(darr), ctypes.addressof(counts), len(ids), E, VOCAB,
                box["pos"], d_emb, ws, wsb, stream_ptr())
 
+    row_id = torch.empty(T, dtype=torch.int64, device=dev)
+    row_grad = torch.empty(T, E, device=dev)
+    p, m, v = (torch.zeros(VOCAB, E, device=dev) for _ in range(3))
+    n_rows = int(torch.unique(torch.cat(ids)).numel())
+
+    def rows():
+        L.call("umpr_embed_grad_rows", ctypes.addressof(iarr), ctypes.addressof(darr), ctypes.addressof(counts), len(ids), E, VOCAB,
+               box["pos"], row_id, row_grad, ws, wsb, stream_ptr())
+
+    def adam_rows():
+        L.call("umpr_sparse_adam_rows", p, m, v, VOCAB, E, row_id, row_grad, T, 1e-6, 0.9, 0.999, 1e-8, 1, 1.0, None, stream_ptr())
+
     out = []
-    for name, fn, nbytes in (("id_sort", sort, 0), ("embed_grad", scatter, 4 * E * (T + VOCAB))):
+    for name, fn, nbytes in (("id_sort", sort, 0), ("embed_grad", scatter, 4 * E * (T + VOCAB)),
+                             ("embed_grad_rows", rows, 4 * E * 2 * T), ("sparse_adam_rows", adam_rows, 4 * E * (T + 6 * n_rows))):
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
@@ -95,7 +112,7 @@ def time_scatter(batch, w, dev, reps=20):
             b.synchronize()
             ms.append(a.elapsed_time(b) / reps)
         t = statistics.median(ms)
-        row = {"kernel": name, "tokens": T, "unique_ids": int(torch.unique(torch.cat(ids)).numel()), "E": E, "vocab": VOCAB,
+        row = {"kernel": name, "tokens": T, "unique_ids": n_rows, "E": E, "vocab": VOCAB,
                "ms": round(t, 5), "ms_min_max": [round(min(ms), 5), round(max(ms), 5)]}
         if nbytes:
             row.update(bytes=nbytes, TB_per_s=round(nbytes / (t * 1e-3) / 1e12, 3))
@@ -119,28 +136,33 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     for name in names:
         w = WORKLOADS[name]
-        sides = {"off": build(w, dev, False), "on": build(w, dev, True)}
+        sides = {"off": build(w, dev, False), "on": build(w, dev, True), "sparse": build(w, dev, True, True)}
         for line in time_scatter(sides["on"][0], w, dev):
             print(json.dumps({"sources_of": name, **line}), flush=True)
         for _, step in sides.values():
             for _ in range(a.warmup):
                 step()
         torch.cuda.synchronize()
-        ms = {"off": [], "on": []}
+        ms = {"off": [], "on": [], "sparse": []}
+        order = list(ms)
         for r in range(a.rounds):
-            for side in (("off", "on") if r % 2 == 0 else ("on", "off")):
+            for side in order[r % 3:] + order[:r % 3]:
                 step = sides[side][1]
                 t0 = time.perf_counter()
                 for _ in range(a.steps):
                     step()
                 torch.cuda.synchronize()
                 ms[side].append(1e3 * (time.perf_counter() - t0) / a.steps)
-        off, on = statistics.median(ms["off"]), statistics.median(ms["on"])
+        off, on, sp = (statistics.median(ms[k]) for k in order)
         print(json.dumps({"workload": name, **w, "steps_per_block": a.steps, "rounds": a.rounds,
-                          "ms_per_step_off": round(off, 4), "ms_per_step_on": round(on, 4), "diff_ms": round(on - off, 4),
+                          "ms_per_step_off": round(off, 4), "ms_per_step_on": round(on, 4), "ms_per_step_sparse": round(sp, 4),
+                          "diff_ms": round(on - off, 4), "diff_ms_sparse": round(sp - off, 4),
                           "samples_per_s_off": round(1e3 * w["batch"] / off, 1), "samples_per_s_on": round(1e3 * w["batch"] / on, 1),
+                          "samples_per_s_sparse": round(1e3 * w["batch"] / sp, 1),
                           "off_min_max": [round(min(ms["off"]), 4), round(max(ms["off"]), 4)],
-                          "on_min_max": [round(min(ms["on"]), 4), round(max(ms["on"]), 4)]}), flush=True)
+                          "on_min_max": [round(min(ms["on"]), 4), round(max(ms["on"]), 4)],
+                          "sparse_min_max": [round(min(ms["sparse"]), 4), round(max(ms["sparse"]), 4)],
+                          "table_grad_arena_bytes_not_allocated": 4 * VOCAB * w["emb"]}), flush=True)
         del sides
         torch.cuda.empty_cache()
     return 0

@@ -31,6 +31,9 @@ SIGNATURES = {
     "umpr_embed_grad_chunk": ("", "i"),
     "umpr_embed_grad_ws_bytes": ("li", "z"),
     "umpr_embed_grad": ("pppiilpppzp", "i"),
+    "umpr_embed_grad_rows_ws_bytes": ("li", "z"),
+    "umpr_embed_grad_rows": ("pppiilppppzp", "i"),
+    "umpr_sparse_adam_rows": ("ppplippl" "dddd" "ld" "pp", "i"),
     "umpr_coattention_fwd_ws_bytes": ("ii", "z"),
     "umpr_coattention_fwd": ("pppiipppplplpppppzp", "i"),
     "umpr_coattention_fwd_bf16": ("pppiipppplplpppppzp", "i"),

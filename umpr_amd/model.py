@@ -20,7 +20,7 @@ from torch import nn
 
 from . import _lib as _lib_mod
 from ._lib import Workspace, lib, stream_ptr
-from .streams import note_gradients_written
+from .streams import note_gradients_written, wait_for_gradients
 
 TEXT_STREAM = os.environ.get("UMPR_TEXT_STREAM", "1") != "0"   # text path on side streams beside the VGG stack
 # (UMPR_TEXT_STREAMS=2 - ReviewNet and ControlNet on streams of their own - measured slower in round 2 and went away with the fused
@@ -393,12 +393,15 @@ class _EmbedStep:
 class _EmbedTable(torch.autograd.Function):
     """The trainable embedding table as ONE upstream node of the step: its output is a one-element token both text nodes take as an
     input, so autograd runs this backward once per step, after both of them - and that backward is the scatter of their token
-    gradients into d_emb (umpr_embed_grad: every row of the table written exactly once, no atomics, no zeroing pass)."""
+    gradients into d_emb (umpr_embed_grad: every row of the table written exactly once, no atomics, no zeroing pass).  With `rows`
+    (UMPR.sparse_embedding) the same sums stay sparse - umpr_embed_grad_rows into the model's _SparseRows, one row per id the step
+    names - and the weight gets no gradient: FusedAdam.step updates those rows alone."""
 
     @staticmethod
-    def forward(ctx, weight, step):
+    def forward(ctx, weight, step, rows=None):
         ctx.step = step
         ctx.weight_obj = weight
+        ctx.rows = rows             # a _SparseRows (UMPR.sparse_embedding): the gradient stays sparse, the weight gets none
         ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
         ctx.set_materialize_grads(False)
         return torch.empty(1, device=weight.device, dtype=torch.float32)
@@ -416,19 +419,46 @@ class _EmbedTable(torch.autograd.Function):
         step.ready = []
         # a text node whose backward did not run (its outputs reached no loss) contributed nothing: zeros for its tokens
         dx = [d if d is not None else torch.zeros(i.numel(), E, device=dev) for d, i in zip(step.dx, step.ids)]
-        tg, direct = _grad_targets((weight,))
         n = len(dx)
         T = sum(i.numel() for i in step.ids)
         keep_i, iarr = _ptr_array(step.ids)
         keep_d, darr = _ptr_array(dx)
         counts = (ctypes.c_long * n)(*[i.numel() for i in step.ids])
+        if ctx.rows is not None:
+            row_id, row_grad = ctx.rows.reserve(T, E, dev)
+            ws, wsb = _ws(lib().size("umpr_embed_grad_rows_ws_bytes", T, E), dev)
+            lib().call("umpr_embed_grad_rows", iarr, darr, ctypes.cast(counts, ctypes.c_void_p), n, E, vocab, step.sorted_pos, row_id,
+                       row_grad, ws, wsb, stream_ptr())
+            ctx.rows.T = T
+            step.dx = [None] * n
+            if ctx.on_side:
+                note_gradients_written(dev)     # read by FusedAdam.step on the caller's stream
+            return None, None, None
+        tg, direct = _grad_targets((weight,))
         ws, wsb = _ws(lib().size("umpr_embed_grad_ws_bytes", T, E), dev)
         lib().call("umpr_embed_grad", iarr, darr, ctypes.cast(counts, ctypes.c_void_p), n, E, vocab, step.sorted_pos, tg[0], ws, wsb,
                    stream_ptr())
         step.dx = [None] * n
         if ctx.on_side and direct[0]:
             note_gradients_written(dev)     # in place, from the side stream both text nodes ran on: umpr_amd/streams.py
-        return _grad_returns((weight,), tg, direct)[0], None
+        return _grad_returns((weight,), tg, direct)[0], None, None
+
+
+class _SparseRows:
+    """The table's gradient of one step in sparse form (UMPR.sparse_embedding), as umpr_embed_grad_rows leaves it: over the T
+    sorted positions, row_id [T] (the table row whose run begins there, or -1) and row_grad [T][E] (its sum, or +0.0).  The two
+    buffers grow to the largest T seen and are otherwise kept; FusedAdam reads their addresses anew in every step, so a buffer
+    that grew (and moved) is followed.  T is None while no backward has reached the table since the last zero_grad."""
+
+    def __init__(self):
+        self.row_id = self.row_grad = None
+        self.T = None
+
+    def reserve(self, T, E, device):
+        if self.row_id is None or self.row_id.numel() < T or self.row_grad.shape[1] != E or self.row_id.device != device:
+            self.row_id = torch.empty(max(T, 1), dtype=torch.int64, device=device)
+            self.row_grad = torch.empty(max(T, 1), E, dtype=torch.float32, device=device)
+        return self.row_id, self.row_grad
 
 
 class _ReviewNetF(torch.autograd.Function):
@@ -955,7 +985,12 @@ class UMPR(nn.Module):
         # precisions; it is written whole, straight into the optimiser's arena.
         self.train_embedding = bool(getattr(config, "train_embedding", False))
         self.embedding = nn.Embedding.from_pretrained(torch.Tensor(word_emb), freeze=not self.train_embedding)
-        if self.train_embedding:
+        # `--sparse_embedding True` (needs a trainable table): the gradient stays sparse - one row per id the step names, in
+        # self._sparse_rows - and FusedAdam updates those rows alone, as torch.optim.SparseAdam would; embedding.weight.grad stays
+        # None and the table has no gradient arena.
+        self.sparse_embedding = self.train_embedding and bool(getattr(config, "sparse_embedding", False))
+        self._sparse_rows = _SparseRows() if self.sparse_embedding else None
+        if self.train_embedding and not self.sparse_embedding:
             self.embedding.weight._umpr_direct = True
         E = self.embedding.embedding_dim
         self.review_net = ReviewNet(E, config.gru_size, config.self_atte_size)
@@ -1130,8 +1165,25 @@ class UMPR(nn.Module):
                                         "holds the output of a frozen VGG only (build the model with freeze_vgg=True)")
         return store
 
+    def sparse_table_grad(self):
+        """The table's gradient of the last backward as a coalesced torch.sparse_coo_tensor [vocab][E] - one index per id the step
+        named, PAD included, in ascending order - or None (the option is off, or no backward has reached the table since the last
+        zero_grad).  Synchronises with the stream that wrote it."""
+        rows = self._sparse_rows
+        if rows is None or rows.T is None:
+            return None
+        wait_for_gradients(rows.row_id.device)
+        row_id, row_grad = rows.row_id[:rows.T], rows.row_grad[:rows.T]
+        named = row_id >= 0
+        return torch.sparse_coo_tensor(row_id[named].unsqueeze(0), row_grad[named], tuple(self.embedding.weight.shape)).coalesce()
+
+    def drop_sparse_grad(self):
+        """zero_grad for the sparse table gradient: the next optimiser step updates no row unless a backward runs first."""
+        if self._sparse_rows is not None:
+            self._sparse_rows.T = None
+
     def forward(self, user_reviews, item_reviews, ui_reviews, u_lengths, i_lengths, ui_lengths, photos, labels):
-        _MODE.b16 = self.compute_dtype == "bf16" and _TEXT_BF16
+        _MODE.b16 =self.compute_dtype == "bf16" and _TEXT_BF16
         try:
             return self._forward(user_reviews, item_reviews, ui_reviews, u_lengths, i_lengths, ui_lengths, photos, labels)
         finally:
@@ -1180,7 +1232,7 @@ class UMPR(nn.Module):
             if emb.requires_grad and torch.is_grad_enabled():
                 # a trainable table: one upstream node both text nodes depend on; its backward scatters their token gradients
                 step = _EmbedStep((ids_pair, ids_pair, ui_reviews) if full else (ids_pair,))
-                tok = _EmbedTable.apply(emb, step)
+                tok = _EmbedTable.apply(emb, step, self._sparse_rows)
                 emb = emb.detach()
             rr = _ReviewNetF.apply(ids_pair, lens, order, emb, (B, S, L), b16_gemm, b16_scores, tok, step,
                                    *self._review_params(device))

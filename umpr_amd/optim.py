@@ -119,7 +119,14 @@ class FusedAdam:
     (an inf or NaN anywhere in the gradient) is SKIPPED: parameters and moments stay as they are.  ``step_count`` still advances
     on a skipped step - the bias corrections are computed on the host, which does not wait for the flag.  While clipping is on the
     early update of the classifier slice is off (``arm_early``): the coefficient is not known before every gradient exists.
-    0 (the default) is off: the step launches exactly what it launches without this argument."""
+    0 (the default) is off: the step launches exactly what it launches without this argument.
+
+    A model with ``sparse_embedding`` (``--sparse_embedding True``) keeps its word table OUT of both groups: the table is not
+    re-pointed into an arena and has no gradient arena.  This optimiser owns dense moments [vocab][E] for it, and ``step()``
+    launches ``umpr_sparse_adam_rows`` behind the dense groups: the rows the step's batch named - ``model._sparse_rows``, written
+    by the backward - are updated as ``torch.optim.SparseAdam(lr, betas, eps)`` updates them (no L2, eps added to sqrt(v)), every
+    other row keeps each byte of its value and moments.  With clipping the row gradients are one more arena of the norm, and
+    the row kernel reads the same coefficient."""
 
     def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None,
                  max_grad_norm=0.0):
@@ -129,6 +136,12 @@ class FusedAdam:
         self.max_grad_norm = max_grad_norm
         self._clip = None           # device state of the clipping path, made by the first clipped step
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        self.sparse = None          # (name, parameter, m, v) of a table updated row-wise
+        if getattr(model, "sparse_embedding", False):
+            table = model.embedding.weight
+            (name,) = [n for n, p in named if p is table]
+            named = [(n, p) for n, p in named if p is not table]
+            self.sparse = (name, table, torch.zeros_like(table), torch.zeros_like(table))
         if order_key is None:
             # the VGG classifier's gradients are produced first in backward and are 89 % of all gradient bytes: put them
             # at the front of the arena so that one contiguous slice can be all-reduced while the conv backward runs
@@ -222,6 +235,8 @@ class FusedAdam:
                 g.g[lo:hi].zero_()
             for p in g.direct:
                 p._umpr_fresh = True
+        if self.sparse is not None:
+            self.model.drop_sparse_grad()
 
     def arm_early(self, grad_scale=1.0):
         """train_step: the coming backward belongs to exactly one optimiser step with this gradient scale.
@@ -280,12 +295,14 @@ class FusedAdam:
     # ---- clipping by global norm (max_grad_norm > 0) -------------------------------------------------------------------------
     def _clip_buffers(self):
         """(state, workspace, arena pointers, arena counts, number of arenas) of the clipping path; the arenas never move, so the
-        two host tables umpr_grad_norm reads are built once."""
+        two host tables umpr_grad_norm reads are built once.  (A sparse table's row gradients take one more slot behind them,
+        which _sparse_arena refreshes per step.)"""
         if self._clip is None:
             dev = self.groups[0].p.device
             arenas = self.grad_arenas()
-            ptrs = (ctypes.c_void_p * max(len(arenas), 1))(*[a.data_ptr() for a in arenas])
-            counts = (ctypes.c_long * max(len(arenas), 1))(*[a.numel() for a in arenas])
+            slots = max(len(arenas) + (self.sparse is not None), 1)
+            ptrs = (ctypes.c_void_p * slots)(*[a.data_ptr() for a in arenas])
+            counts = (ctypes.c_long * slots)(*[a.numel() for a in arenas])
             state = torch.zeros(8, dtype=torch.float32, device=dev)
             ws_bytes = lib().size("umpr_grad_norm_ws_bytes")
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
@@ -310,6 +327,7 @@ class FusedAdam:
 
     def _step_clipped(self, grad_scale):
         state, ws, ws_bytes, ptrs, counts, n_arenas = self._clip_buffers()
+        n_arenas = self._sparse_arena(ptrs, counts, n_arenas)
         hyper = getattr(self, "_hyper", None)
         for g in self.groups:                          # the norm reads every arena: all stale slices are zeroed first
             for p in g.direct:
@@ -328,6 +346,32 @@ class FusedAdam:
             else:
                 lib().call("umpr_adam_step_clip", g.p, g.g, g.m, g.v, g.numel, self.lr, self.betas[0], self.betas[1], self.eps,
                            g.weight_decay, self.step_count, grad_scale, state, stream_ptr())
+        self._step_sparse(grad_scale, state)
+
+    # ---- the row-wise update of a sparse table ---------------------------------------------------------------------------------
+    def _sparse_rows(self):
+        """(row_id, row_grad, T) of the step's sparse table gradient, or None: no sparse table, or no backward reached it"""
+        rows = self.model._sparse_rows if self.sparse is not None else None
+        return None if rows is None or not rows.T else (rows.row_id, rows.row_grad, rows.T)
+
+    def _sparse_arena(self, ptrs, counts, n_arenas):
+        """the row gradients as one more arena of umpr_grad_norm: the first T rows of the buffer - the pointer is refreshed here,
+        so a buffer that grew (and moved) is followed - or nothing in a step whose backward did not reach the table"""
+        rows = self._sparse_rows()
+        if rows is None:
+            return n_arenas
+        ptrs[n_arenas] = rows[1].data_ptr()
+        counts[n_arenas] = rows[2] * rows[1].shape[1]
+        return n_arenas + 1
+
+    def _step_sparse(self, grad_scale, clip_state):
+        rows = self._sparse_rows()
+        if rows is None:
+            return
+        row_id, row_grad, T = rows
+        _, p, m, v = self.sparse
+        lib().call("umpr_sparse_adam_rows", p, m, v, p.shape[0], p.shape[1], row_id, row_grad, T, self.lr, self.betas[0],
+                   self.betas[1], self.eps, self.step_count, float(grad_scale), clip_state, stream_ptr())
 
     def step(self, grad_scale=1.0):
         if self.groups[0].p.device.type != "cuda":
@@ -358,6 +402,7 @@ class FusedAdam:
                     lib().call("umpr_adam_step", g.p[lo:hi], g.g[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.lr,
                                self.betas[0], self.betas[1], self.eps, g.weight_decay, self.step_count, grad_scale,
                                stream_ptr())
+        self._step_sparse(grad_scale, None)
 
     def epoch_end(self):
         """ExponentialLR.step() (main.py:54)."""
@@ -371,15 +416,31 @@ class FusedAdam:
                 off, k = g.offsets[n]
                 st["m"][n] = g.m[off:off + k].detach().cpu().clone()
                 st["v"][n] = g.v[off:off + k].detach().cpu().clone()
+        if self.sparse is not None:
+            name, _, m, v = self.sparse
+            st["m"][name], st["v"][name] = m.detach().cpu().reshape(-1).clone(), v.detach().cpu().reshape(-1).clone()
+            st["sparse_embedding"] = True
         return st
+
+    def _moment_sizes(self):
+        want = {n: g.offsets[n][1] for g in self.groups for n in g.names}
+        sparse = getattr(self, "sparse", None)
+        if sparse is not None:
+            want[sparse[0]] = sparse[1].numel()
+        return want
 
     def check_state_dict(self, st):
         """Raises unless `st` holds Adam moments for exactly the parameters this optimiser trains, in their sizes - a checkpoint
         written with the VGG frozen resumed with it trainable, or the other way round, does not; nor does one written under the other
-        --train_embedding setting."""
+        --train_embedding setting.  Nor does one written under the other --sparse_embedding setting: the table's moments have the
+        same names and sizes there, but not the same meaning (lazily kept per row, no L2 in them)."""
+        was, now = bool(st.get("sparse_embedding", False)), getattr(self, "sparse", None) is not None
+        if was != now:
+            raise ValueError("optimizer state does not match this run: the checkpoint was written with --sparse_embedding "
+                             f"{was}, this run has --sparse_embedding {now}: pass the same --sparse_embedding")
         for key in ("m", "v"):
             have = {n: int(t.numel()) for n, t in st[key].items()}
-            want = {n: g.offsets[n][1] for g in self.groups for n in g.names}
+            want = self._moment_sizes()
             if have != want:
                 missing, extra = sorted(set(want) - set(have)), sorted(set(have) - set(want))
                 sized = sorted(n for n in set(want) & set(have) if want[n] != have[n])
@@ -406,6 +467,10 @@ class FusedAdam:
                 off, k = g.offsets[n]
                 g.m[off:off + k].copy_(st["m"][n])
                 g.v[off:off + k].copy_(st["v"][n])
+        if self.sparse is not None:
+            name, _, m, v = self.sparse
+            m.copy_(st["m"][name].view_as(m))
+            v.copy_(st["v"][name].view_as(v))
 
     def reattach(self):
         """No-op hook: ``model.load_state_dict`` copies INTO the arena views, so parameters stay attached."""

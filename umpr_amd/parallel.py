@@ -123,6 +123,9 @@ class GradReducer:
     None) and no per-block bucket, no hook or callback is installed, and `finish()` reduces the arenas whole."""
 
     def __init__(self, opt, n_buckets=4):
+        if getattr(opt, "sparse", None) is not None:
+            raise NotImplementedError("GradReducer: --sparse_embedding runs on one rank only: the table's sparse gradient has no "
+                                      "arena to all-reduce (train with --sparse_embedding False on more than one)")
         self.opt = opt
         self.n_buckets = n_buckets
         self.handles = []

@@ -47,6 +47,9 @@ def train_step(model, opt: FusedAdam, batch, world=1, reducer=None):
     """model.train(); pred, loss = model(*batch); loss.mean(); zero_grad; backward; step  (main.py:32-37).
     With world > 1 the gradients are summed over ranks (RCCL) - by `reducer` overlapped with backward if given."""
     model.train()
+    if (world > 1 or reducer is not None) and getattr(opt, "sparse", None) is not None:
+        raise NotImplementedError("train_step: --sparse_embedding runs on one rank only: the table's sparse gradient has no arena "
+                                  "to all-reduce (train with --sparse_embedding False on more than one)")
     n_active = getattr(batch, "n_active", world)     # ranks with a non-empty chunk of this batch (parallel.Shard)
     if batch[0].shape[0] == 0:
         # Fewer samples than ranks in a short last batch: DataParallel would run fewer replicas (main.py:82).  This rank
