@@ -300,7 +300,10 @@ int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, cons
  * gives the same bytes.  Injected masks are read only.  A call writes every byte it uses: the classifier forward all of out,
  * the fc1 / fc2 regions of the arena and - when dropout runs - the two dropout regions and, when it generates them, the masks
  * (in eval mode the dropout regions and the masks are not touched); the backward all six classifier gradients and d_pool5;
- * neither reads workspace bytes it has not written itself.  n_img < 1 and a workspace below the queried size are refused
+ * neither reads workspace bytes it has not written itself.  The three classifier backwards (umpr_vgg16_classifier_bwd,
+ * _bwd_compact, _bwd_compact_bf16) take d_pool5 == NULL for a caller whose convolutional stage does not train: the six
+ * gradients are written exactly as with a d_pool5, fc1's data-gradient product (a second pass over its 411 MB matrix) is
+ * not launched and nothing of size n x 25088 is written; the workspace size is the same.  n_img < 1 and a workspace below the queried size are refused
  * before anything is launched.  Above 128 images the classifier's products run on the generic GEMM above (in its bf16 mode
  * under the _bf16 entry points). */
 size_t umpr_vgg16_act_bytes(int n_img);

@@ -5,6 +5,8 @@
     python main.py --data_dir synthetic --learning_rate 1e-3 --grad_clip 5.0  # clip the gradient to a global 2-norm of 5
     python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
                                                                                   # for every photo kept in 1 GB of HBM
+    python main.py --data_dir data/music --freeze_conv True --pool5_store_gb 8    # freeze the conv base, train the classifier on
+                                                                                  # each photo's pool5 row kept in 8 GB of HBM
     python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
     python main.py --data_dir data/music --train_embedding True --sparse_embedding True   # ... updating only the rows a step names
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
@@ -73,8 +75,8 @@ class _Collate:
     def __init__(self, ignore_photos, rank=0, world=1, store=None):
         self.ignore_photos = ignore_photos
         self.shard = (rank, world) if world > 1 else None
-        self.store = store          # a PhotoStore's or FeatureStore's index (--photo_store_gb, --feature_store_gb): photos the
-                                    # store holds are not decoded
+        self.store = store          # a PhotoStore's, FeatureStore's or Pool5Store's index (--photo_store_gb, --feature_store_gb,
+                                    # --pool5_store_gb): photos the store holds are not decoded
 
     def __call__(self, samples):
         from umpr_amd.data import batch_loader
@@ -111,8 +113,17 @@ def run_real(config, rank, world, log):
     # eviction) and decodes it once per run instead of once per epoch and validation pass (umpr_amd/photos.py::PhotoStore)
     # --freeze_vgg True --feature_store_gb X: the store keeps what the frozen VGG makes of a photo instead (4 000 B per photo): a
     # resident photo is neither decoded nor resized nor run through the VGG (umpr_amd/photos.py::FeatureStore)
+    # --freeze_conv True --pool5_store_gb X: the store keeps the frozen conv base's pool5 row of a photo (100 352 B): a resident
+    # photo is neither decoded nor resized nor run through the 13 conv layers, and the classifier trains on the stored row
+    # (umpr_amd/photos.py::Pool5Store)
     store = None
-    if config.feature_store_gb > 0 and not config.review_net_only:
+    if config.pool5_store_gb > 0 and not config.review_net_only:
+        from umpr_amd.photos import Pool5Store
+        store = Pool5Store(config.device, capacity_bytes=int(config.pool5_store_gb * 1e9))
+        log(f'Pool5 store: {store.slots} slots of {store.slot_bytes} B ({store.slots * store.slot_bytes / 1e9:.2f} GB) on '
+            f'{config.device}' + ('; it replaces the photo store (--photo_store_gb): a photo whose pool5 row is resident is '
+                                  'never resized' if config.photo_store_gb > 0 else ''))
+    elif config.feature_store_gb > 0 and not config.review_net_only:
         from umpr_amd.photos import FeatureStore
         store = FeatureStore(config.device, capacity_bytes=int(config.feature_store_gb * 1e9))
         log(f'Feature store: {store.slots} slots of {store.slot_bytes} B ({store.slots * store.slot_bytes / 1e9:.2f} GB) on '
@@ -123,7 +134,7 @@ def run_real(config, rank, world, log):
         store = PhotoStore(config.device, capacity_bytes=int(config.photo_store_gb * 1e9))
         log(f'Photo store: {store.slots} slots of {store.slot_bytes} B ({store.slots * store.slot_bytes / 1e9:.2f} GB) on '
             f'{config.device}')
-    store_name = 'Feature store' if config.feature_store_gb > 0 else 'Photo store'
+    store_name = 'Pool5 store' if config.pool5_store_gb > 0 else 'Feature store' if config.feature_store_gb > 0 else 'Photo store'
     known = lambda data: store and store.register(data.photo_paths())
     collate = _Collate(config.review_net_only, rank, world, store.index if store else None)
     workers = max(0, int(getattr(config, "loader_workers", 0)))
@@ -182,7 +193,8 @@ def main():
 # options the reference does not have
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
-                 "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False}
+                 "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
+                 "freeze_conv": False, "pool5_store_gb": 0.0}
 
 
 def check_flags(config):
@@ -196,11 +208,24 @@ def check_flags(config):
     if config.sparse_embedding and not config.train_embedding:
         sys.exit("--sparse_embedding needs --train_embedding True: it chooses how a trainable table is updated (the rows a step "
                  "names only, as torch.optim.SparseAdam would)")
+    if config.pool5_store_gb > 0 and config.feature_store_gb > 0:
+        sys.exit("--pool5_store_gb and --feature_store_gb exclude each other: --feature_store_gb belongs to --freeze_vgg True, "
+                 "--pool5_store_gb to --freeze_conv True")
     if config.feature_store_gb < 0:
         sys.exit(f"--feature_store_gb must be >= 0, got {config.feature_store_gb}")
     if config.feature_store_gb > 0 and not config.freeze_vgg:
         sys.exit("--feature_store_gb needs --freeze_vgg True: the store keeps the VGG's output for every photo, which is a constant "
                  "of the run only while the VGG does not train")
+    if not isinstance(config.freeze_conv, bool):
+        sys.exit(f"--freeze_conv takes True or False, got {config.freeze_conv!r}")
+    if config.freeze_conv and config.freeze_vgg:
+        sys.exit("--freeze_conv True and --freeze_vgg True exclude each other: --freeze_vgg freezes the whole VGG, --freeze_conv its "
+                 "conv base only (the classifier trains)")
+    if config.pool5_store_gb < 0:
+        sys.exit(f"--pool5_store_gb must be >= 0, got {config.pool5_store_gb}")
+    if config.pool5_store_gb > 0 and not config.freeze_conv:
+        sys.exit("--pool5_store_gb needs --freeze_conv True: the store keeps the conv base's pool5 for every photo, which is a "
+                 "constant of the run only while the conv base does not train")
 
 
 def _main():

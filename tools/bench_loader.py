@@ -18,6 +18,12 @@ With `--freeze_vgg True` it measures the frozen VGG and the feature store (umpr_
 store warm), frozen without a store, frozen with the photo store warm, frozen with the feature store cold, and frozen with it warm.
 
     python tools/bench_loader.py --items 2000 --freeze_vgg True --workers 0,4
+
+With `--freeze_conv True` it measures the frozen conv base and the pool5 store (umpr_amd/photos.py::Pool5Store, capacity
+`--pool5_store_gb`, default 1): the same five legs with the classifier training - trainable with the photo store warm, conv base
+frozen without a store, with the photo store warm, with the pool5 store cold, and with it warm.
+
+    python tools/bench_loader.py --items 2000 --freeze_conv True --workers 0,4
 """
 import argparse
 import functools
@@ -74,13 +80,21 @@ def main():
     ap.add_argument("--freeze_vgg", type=lambda t: t == "True", default=False, help="True: measure the frozen VGG")
     ap.add_argument("--feature_store_gb", type=float, default=0.0, help="capacity of the feature store (with --freeze_vgg True; "
                     "default 1)")
+    ap.add_argument("--freeze_conv", type=lambda t: t == "True", default=False, help="True: measure the frozen conv base")
+    ap.add_argument("--pool5_store_gb", type=float, default=0.0, help="capacity of the pool5 store (with --freeze_conv True; "
+                    "default 1)")
+    ap.add_argument("--dtypes", default="fp32,bf16", help="arithmetic modes of the --freeze_vgg / --freeze_conv legs")
     a = ap.parse_args()
     if a.feature_store_gb > 0 and not a.freeze_vgg:
         sys.exit("--feature_store_gb needs --freeze_vgg True")
-    stores = a.photo_store_gb > 0 or a.freeze_vgg
+    if a.pool5_store_gb > 0 and not a.freeze_conv:
+        sys.exit("--pool5_store_gb needs --freeze_conv True")
+    if a.freeze_conv and a.freeze_vgg:
+        sys.exit("--freeze_conv True and --freeze_vgg True exclude each other")
+    stores = a.photo_store_gb > 0 or a.freeze_vgg or a.freeze_conv
     a.workers = a.workers or ("0,4,8" if stores else "0,4,8,12")
     a.users = a.users or (max(200, a.items // 2) if stores else 200)
-    resident = resident_rates(a.batch) if a.photo_store_gb > 0 and not a.freeze_vgg else None
+    resident = resident_rates(a.batch) if a.photo_store_gb > 0 and not (a.freeze_vgg or a.freeze_conv) else None
     from torch.utils.data import DataLoader
     from main import _Collate
     from umpr_amd.config import Config
@@ -95,7 +109,7 @@ def main():
         print(f"corpus: {n} reviews -> {len(ds)} samples, Dataset built in {time.perf_counter() - t0:.2f} s", flush=True)
         photo = ds[0][3][0][0]
         per_photo(photo)
-        if a.freeze_vgg:
+        if a.freeze_vgg or a.freeze_conv:
             return frozen_vgg(a, ds, cfg, w2v)
         if a.photo_store_gb > 0:
             return photo_store(a, ds, cfg, w2v, resident)
@@ -186,23 +200,25 @@ def frozen_vgg(a, ds, cfg, w2v):
     photo store warm (the same loader work as the trainable leg: the difference is the VGG alone), frozen with the feature store
     cold (the epoch that fills it) and warm.  Every leg runs one warm-up epoch first (allocator, workspaces, first-use setup, the
     worker pool's start) - except the cold epoch, which can only happen once: its model has run epochs before, and its worker
-    pool has served one loader-only epoch, which makes nothing resident."""
+    pool has served one loader-only epoch, which makes nothing resident.
+    With --freeze_conv True the same legs for the frozen conv base (the classifier trains) and the pool5 store."""
     from umpr_amd.model import UMPR
     from umpr_amd.optim import FusedAdam
-    from umpr_amd.photos import FeatureStore, PhotoStore
+    from umpr_amd.photos import FeatureStore, PhotoStore, Pool5Store
     from umpr_amd.train import train_step
     if not torch.cuda.is_available():
-        sys.exit("--freeze_vgg needs an MI355X")
+        sys.exit("--freeze_vgg / --freeze_conv need an MI355X")
+    flag, frozen, kept = ("freeze_conv", "conv frozen", "pool5 store") if a.freeze_conv else ("freeze_vgg", "frozen", "feature store")
     dev = torch.device("cuda:0")
     paths = list(ds.photo_paths())
     print(f"an epoch: {len(ds) // a.batch} batches of {a.batch}, {len(set(paths) - {'unknown'})} distinct photos", flush=True)
-    for dtype in ("fp32", "bf16"):
+    for dtype in a.dtypes.split(","):
         cfg.dtype = dtype
         for w in [int(x) for x in a.workers.split(",")]:
             rates = {}
 
             def leg(freeze):
-                cfg.freeze_vgg = freeze
+                setattr(cfg, flag, freeze)
                 torch.manual_seed(0)
                 model = UMPR(cfg, w2v.embedding).to(dev)
                 opt = FusedAdam(model, cfg.learning_rate, cfg.l2_regularization, cfg.lr_decay)
@@ -217,23 +233,26 @@ def frozen_vgg(a, ds, cfg, w2v):
             model, opt, step = leg(True)
             dl = _loader(a, ds, w, None)
             _epoch(a, dl, step)
-            rates["frozen, no store"] = _epoch(a, dl, step)
+            rates[f"{frozen}, no store"] = _epoch(a, dl, step)
             del dl
             store = PhotoStore(dev, capacity_bytes=int((a.photo_store_gb or 1.0) * 1e9)).register(paths)
             dl = _loader(a, ds, w, store)
             _epoch(a, dl, step)
-            rates["frozen, photo store warm"] = _epoch(a, dl, step)
+            rates[f"{frozen}, photo store warm"] = _epoch(a, dl, step)
             del dl, store
-            store = FeatureStore(dev, capacity_bytes=int((a.feature_store_gb or 1.0) * 1e9)).register(paths)
+            if a.freeze_conv:
+                store = Pool5Store(dev, capacity_bytes=int((a.pool5_store_gb or 1.0) * 1e9)).register(paths)
+            else:
+                store = FeatureStore(dev, capacity_bytes=int((a.feature_store_gb or 1.0) * 1e9)).register(paths)
             dl = _loader(a, ds, w, store)
             _epoch(a, dl)
-            rates["frozen, feature store cold"] = _epoch(a, dl, step)
-            rates["frozen, feature store warm"] = _epoch(a, dl, step)
+            rates[f"{frozen}, {kept} cold"] = _epoch(a, dl, step)
+            rates[f"{frozen}, {kept} warm"] = _epoch(a, dl, step)
             print(f"end to end, {dtype}, {w:2d} workers: " + ", ".join(f"{k} {v:.1f} samples/s" for k, v in rates.items()),
                   flush=True)
-            print(f"    feature store: {store.stats()}", flush=True)
+            print(f"    {kept}: {store.stats()}", flush=True)
             del model, opt, step, dl, store
-    cfg.freeze_vgg = False
+    setattr(cfg, flag, False)
 
 
 def photo_store(a, ds, cfg, w2v, resident):

@@ -636,8 +636,9 @@ int umpr_vgg16_fwd(const float* images, const float* const* params, int n, int t
 
 size_t umpr_vgg16_classifier_bwd_ws_bytes(int n_img) { return vgg_cls_bwd_ws(nullptr, n_img).bytes; }
 
-// d_pool5 [n][25088] receives the gradient w.r.t. the pooled feature map; grads: the 32-pointer array (only the six
-// classifier entries 26..31 are written).
+// d_pool5 [n][25088] receives the gradient w.r.t. the pooled feature map, or is NULL when nothing upstream of the classifier
+// trains: the six parameter gradients are the same and fc1's data-gradient product is left out.  grads: the 32-pointer array
+// (only the six classifier entries 26..31 are written).
 namespace {
 int classifier_bwd_impl(const float* const* params, int n, int train, const ClsActs& A, const uint8_t* masks,
                         const float* d_out, float* const* grads, float* d_pool5, float* ws, size_t ws_bytes, hipStream_t s,
@@ -666,6 +667,7 @@ int classifier_bwd_impl(const float* const* params, int n, int train, const ClsA
     }
     if (int rc = umpr_colsum_rows(g, n, fout, fout, grads[27 + 2 * j], 0, s)) return rc;
     float* dxo = j == 0 ? d_pool5 : cur;
+    if (!dxo) break;   // fc1 with d_pool5 == NULL: nobody reads the data gradient, so the second pass over fc1's matrix is not launched
     if (small) {  // dx[n][fin] = g W
       if (int rc = umpr_fc_small_dx(g, params[26 + 2 * j], dxo, n, fout, fin, W.scratch, W.scratch_bytes, s, bf16)) return rc;
     } else {
@@ -683,7 +685,7 @@ int classifier_bwd_impl(const float* const* params, int n, int train, const ClsA
 int umpr_vgg16_classifier_bwd(const float* const* params, int n, int train, const float* acts, const uint8_t* masks,
                               const float* d_out, float* const* grads, float* d_pool5, float* ws, size_t ws_bytes,
                               void* stream) {
-  UMPR_REQUIRE(n > 0 && params && acts && grads && d_out && d_pool5, "vgg16_classifier_bwd: bad arguments");
+  UMPR_REQUIRE(n > 0 && params && acts && grads && d_out, "vgg16_classifier_bwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_full(const_cast<float*>(acts), n), masks, d_out, grads, d_pool5,
                              ws, ws_bytes, S(stream));
@@ -692,7 +694,7 @@ int umpr_vgg16_classifier_bwd(const float* const* params, int n, int train, cons
 int umpr_vgg16_classifier_bwd_compact(const float* const* params, int n, int train, const float* cls_arena,
                                       const uint8_t* masks, const float* d_out, float* const* grads, float* d_pool5,
                                       float* ws, size_t ws_bytes, void* stream) {
-  UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out && d_pool5, "vgg16_classifier_bwd_compact: bad arguments");
+  UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out, "vgg16_classifier_bwd_compact: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd_compact: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_compact(const_cast<float*>(cls_arena), n), masks, d_out, grads,
                              d_pool5, ws, ws_bytes, S(stream));
@@ -711,7 +713,7 @@ int umpr_vgg16_classifier_fwd_compact_bf16(const float* const* params, int n, in
 int umpr_vgg16_classifier_bwd_compact_bf16(const float* const* params, int n, int train, const float* cls_arena,
                                            const uint8_t* masks, const float* d_out, float* const* grads, float* d_pool5,
                                            float* ws, size_t ws_bytes, void* stream) {
-  UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out && d_pool5, "vgg16_classifier_bwd_compact_bf16: bad arguments");
+  UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out, "vgg16_classifier_bwd_compact_bf16: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd_compact_bf16: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_compact(const_cast<float*>(cls_arena), n), masks, d_out, grads,
                              d_pool5, ws, ws_bytes, S(stream), 1);

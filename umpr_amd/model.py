@@ -705,13 +705,14 @@ class _VGGClassifier(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pool5, acts, train, masks_in, seed, owner, compact, *params):
-        """`acts`: the fp32 activation arena of _VGGFeatures, or (compact) the classifier arena of _VGGFeaturesBF16."""
+        """`acts`: the fp32 activation arena of _VGGFeatures, or (compact) the classifier arena of _VGGFeaturesBF16.
+        compact == "fp32": that compact arena under an fp32 model (VGG16.classify with a frozen conv base)."""
         n = pool5.shape[0]
         dev = pool5.device
         ctx.param_objs = params
         ctx.owner = owner
         # compact = the bf16 path: its classifier products run on the bf16 matrix pipe too (UMPR_CLS_BF16=0: fp32 MFMA)
-        ctx.suffix = ("_compact_bf16" if _CLS_BF16 else "_compact") if compact else ""
+        ctx.suffix = ("_compact_bf16" if _CLS_BF16 and compact != "fp32" else "_compact") if compact else ""
         params = [_c(p) for p in params]
         use_masks = masks_in is not None
         masks = _c(masks_in) if use_masks else torch.empty(2, n, 4096, device=dev, dtype=torch.uint8)
@@ -730,7 +731,9 @@ class _VGGClassifier(torch.autograd.Function):
         n = d_out.shape[0]
         dev = d_out.device
         grads, direct = _grad_targets(ctx.param_objs)
-        d_pool5 = torch.empty(n, 25088, device=dev, dtype=torch.float32)
+        # nothing upstream of pool5 trains (frozen conv base, frozen VGG): no [n, 25088] tensor, and the library leaves out fc1's
+        # data-gradient product (d_pool5 = NULL)
+        d_pool5 = torch.empty(n, 25088, device=dev, dtype=torch.float32) if ctx.needs_input_grad[0] else None
         ws, wsb = _ws(lib().size("umpr_vgg16_classifier_bwd_ws_bytes", n), dev)
         keep_p, parr = _ptr_array([params[0]] * 26 + params)
         keep_g, garr = _ptr_array([grads[0]] * 26 + grads)
@@ -909,6 +912,7 @@ class VGG16(nn.Module):
         self._calls = 0
         self.forward_calls = 0     # every forward, frozen or not (`_calls` seeds the dropout masks and is part of a checkpoint)
         self.frozen = False        # UMPR(freeze_vgg=True): a fixed feature extractor, see forward
+        self.frozen_conv = False   # UMPR(freeze_conv=True): the conv stage is one, the classifier trains, see forward
         self.grad_callbacks = []   # called once the classifier gradients have been written in place (GradReducer)
         for p in self.parameters():
             p._umpr_direct = True  # one backward node writes each of these exactly once per step
@@ -923,10 +927,47 @@ class VGG16(nn.Module):
                 ps += [m.weight, m.bias]
         return ps
 
+    def _conv_stage(self, images):
+        """(pool5, arena) of the conv stage as a fixed feature extractor: under no_grad on the inference path (the F(4x4,3x3)
+        forward tile, nothing kept for backward).  `arena` is what pool5 is a view of: the fp32 activation arena, or in bf16 the
+        compact classifier arena with pool5 at its head."""
+        bf16 = self.compute_dtype == "bf16"
+        with torch.no_grad():
+            _MODE.infer = True
+            try:
+                return (_VGGFeaturesBF16 if bf16 else _VGGFeatures).apply(images, *self.param_list()[:26])
+            finally:
+                _MODE.infer = False
+
+    def conv_base(self, images):
+        """pool5 [n, 25088] fp32 without grad: what the conv stage makes of `images` [n, 3, 224, 224] when it is a fixed feature
+        extractor (photos.Pool5Store keeps these rows)."""
+        return self._conv_stage(images)[0]
+
+    def classify(self, arena, n):
+        """The classifier on a compact arena (umpr_vgg16_cls_arena_bytes(n) as flat fp32) whose first n x 25088 floats hold pool5
+        rows that carry no grad: [n, 1000].  Dropout, the injected masks and the seed counter as in the trainable model."""
+        ps = self.param_list()
+        self._calls += 1
+        seed = (torch.initial_seed() * 1000003 + self._calls) & 0x7FFFFFFFFFFFFFFF
+        pool5 = arena[:n * 25088].view(n, 25088)
+        return _VGGClassifier.apply(pool5, arena, self.training, self.dropout_masks, seed, self,
+                                    True if self.compute_dtype == "bf16" else "fp32", *ps[26:])
+
     def forward(self, images):
         self.forward_calls += 1
         ps = self.param_list()
         bf16 = self.compute_dtype == "bf16"
+        if self.frozen_conv:
+            # The conv stage is a fixed feature extractor, the classifier trains on its pool5: the rows move into a compact
+            # classifier arena, so the conv activation arena is released here and not held for a backward that never reads it.
+            n = images.shape[0]
+            pool5, arena = self._conv_stage(images)
+            if not bf16:
+                arena = torch.empty(lib().size("umpr_vgg16_cls_arena_bytes", n) // 4, device=images.device, dtype=torch.float32)
+                arena[:n * 25088].copy_(pool5.reshape(-1))
+            del pool5
+            return self.classify(arena, n)
         if self.frozen:
             # A fixed feature extractor: the inference path whatever module.training and the grad mode say - the F(4x4,3x3) forward
             # tile, no dropout and no dropout counter consumed, nothing kept for backward; the output carries no grad.
@@ -1010,6 +1051,16 @@ class UMPR(nn.Module):
         if self.freeze_vgg:
             self.visual_net.vgg16.requires_grad_(False)
             self.visual_net.vgg16[0].frozen = True
+        # not in the reference: `--freeze_conv True`, the usual fine-tuning regime - the 13 conv layers (99 % of the model's FLOPs)
+        # are a fixed feature extractor and take no gradient, the classifier (123.6 M of the VGG's 138.4 M parameters) trains on
+        # their pool5.  Keys and shapes of the state_dict stay.  Nothing to freeze in UMPR-R.
+        self.freeze_conv = bool(getattr(config, "freeze_conv", False)) and not config.review_net_only
+        if self.freeze_conv:
+            if self.freeze_vgg:
+                raise ValueError("freeze_vgg and freeze_conv are both set: freeze_vgg freezes the whole VGG, freeze_conv its conv "
+                                 "base only (the classifier trains) - choose one")
+            self.visual_net.vgg16[0].features.requires_grad_(False)
+            self.visual_net.vgg16[0].frozen_conv = True
         self.last_loss_terms = None
         # Parameters whose backward node can write the gradient straight into the optimiser's arena (_grad_targets):
         # everything in the review / control nets (GRU weights accumulate in place across their uses) and, set by VGG16
@@ -1154,11 +1205,18 @@ class UMPR(nn.Module):
         return _ZeroPad.apply(fw, (1, D + (0 if self.review_net_only else 2 * len(self.views))), None, m.fus)
 
     def _feature_store(self, photos):
-        """The photos.FeatureStore `photos` was collated against (main.py --feature_store_gb), or None."""
+        """The photos.FeatureStore or Pool5Store `photos` was collated against (main.py --feature_store_gb, --pool5_store_gb), or
+        None."""
         key = getattr(photos, "store_key", None)
         if key is None:
             return None
-        from .photos import FeatureStore
+        from .photos import FeatureStore, Pool5Store
+        store = Pool5Store.find(key)
+        if store is not None:
+            if not self.freeze_conv:
+                raise _lib_mod.UmprHipError("a batch collated against a pool5 store reached a model without freeze_conv: the store "
+                                            "holds the output of a frozen conv base only (build the model with freeze_conv=True)")
+            return store
         store = FeatureStore.find(key)
         if store is not None and not self.freeze_vgg:
             raise _lib_mod.UmprHipError("a batch collated against a feature store reached a model whose VGG trains: the store "
@@ -1252,7 +1310,9 @@ class UMPR(nn.Module):
                 t.record_stream(side)
         vn = self.visual_net
         V, Pc = photos.shape[1], photos.shape[2]
-        if feature_store is not None:
+        if feature_store is not None and self.freeze_conv:     # a Pool5Store: the classifier runs (and trains) on the stored rows
+            vgg = vn.vgg16[0].classify(feature_store.features(photos, vn.vgg16[0], non_blocking=True), B * V * Pc)
+        elif feature_store is not None:
             vgg = feature_store.features(photos, vn.vgg16[0], non_blocking=True)
         else:
             vgg = vn.vgg16[0](photos.reshape(B * V * Pc, *photos.shape[3:]).float())

@@ -431,7 +431,7 @@ class FusedAdam:
 
     def check_state_dict(self, st):
         """Raises unless `st` holds Adam moments for exactly the parameters this optimiser trains, in their sizes - a checkpoint
-        written with the VGG frozen resumed with it trainable, or the other way round, does not; nor does one written under the other
+        written with the VGG (or its conv base, --freeze_conv) frozen resumed with it trainable, or the other way round, does not; nor does one written under the other
         --train_embedding setting.  Nor does one written under the other --sparse_embedding setting: the table's moments have the
         same names and sizes there, but not the same meaning (lazily kept per row, no L2 in them)."""
         was, now = bool(st.get("sparse_embedding", False)), getattr(self, "sparse", None) is not None
@@ -448,6 +448,12 @@ class FusedAdam:
                 hint = (" (the checkpoint was written with the VGG " + ("frozen" if any(n in missing for n in vgg) else "trainable")
                         + ", this run has it " + ("trainable" if any(n in missing for n in vgg) else "frozen")
                         + ": pass the same --freeze_vgg)") if vgg else ""
+                # only conv moments differ and the classifier's are on both sides: the other --freeze_conv setting
+                if vgg and all(".features." in n for n in vgg) and any(".vgg16." in n and ".classifier." in n
+                                                                       for n in set(want) & set(have)):
+                    hint = (" (the checkpoint was written with the VGG conv base "
+                            + ("frozen" if any(n in missing for n in vgg) else "trainable") + ", this run has it "
+                            + ("trainable" if any(n in missing for n in vgg) else "frozen") + ": pass the same --freeze_conv)")
                 table = [n for n in missing + extra if n == "embedding.weight" or n.endswith(".embedding.weight")]
                 if table:
                     hint += (" (the checkpoint was written with the embedding table "

@@ -15,6 +15,10 @@ bit-identical.  No eviction: once the slots are used up, further photos are deco
 the photo's 150 528 B.  A resident photo is then neither decoded nor resized nor run through the VGG: ``features`` resizes only the
 photos the store lacks, runs the VGG once on those, and one kernel (umpr_feature_fetch_f32) builds the dense feature tensor the
 head takes and fills the new slots.
+
+``Pool5Store`` (off unless asked for, frozen conv base only: UMPR(freeze_conv=True)) keeps the conv stage's pool5 row instead:
+25088 floats, 100 352 B, still less than the uint8 photo.  The classifier trains on the stored rows: ``features`` returns the
+compact classifier arena with the rows fetched into its head, and an Adam step on the classifier leaves the store as it is.
 """
 from __future__ import annotations
 
@@ -330,6 +334,13 @@ def vgg_fingerprint(vgg):
         (p.data_ptr(), p._version, str(p.dtype), str(p.device)) for p in vgg.parameters())
 
 
+def conv_fingerprint(vgg):
+    """vgg_fingerprint over the conv stage (``features.*``) only - what a Pool5Store's rows were computed from.  A step on the
+    classifier leaves it as it is; any write to a conv parameter changes it."""
+    return (str(getattr(vgg, "compute_dtype", "")),) + tuple(
+        (p.data_ptr(), p._version, str(p.dtype), str(p.device)) for p in vgg.features.parameters())
+
+
 class FeatureTable(PhotoTable):
     """The host half of a FeatureStore: PhotoTable's ids, id -> slot table and resident bytes, and the plan of which photo of a
     batch reads a slot, which is computed, and which computed row fills a slot.  Slot `slots` (one past the last) is the reserved
@@ -443,13 +454,13 @@ class FeatureStore(FeatureTable):
     def __init__(self, device, size=(224, 224), capacity_bytes=1 << 30, max_photos=1 << 22):
         device = torch.device(device)
         if device.type != "cuda":
-            raise RuntimeError("FeatureStore lives on an MI355X (no CPU path)")
+            raise RuntimeError(f"{type(self).__name__} lives on an MI355X (no CPU path)")
         self.device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
         self.slot_bytes = 4 * self.F
         super().__init__(size, int(capacity_bytes) // self.slot_bytes, max_photos)
         self.buffer = torch.empty((self.slots + 1) * self.F, dtype=torch.float32, device=self.device)
         self._insert_stream = self._insert_event = None
-        FeatureStore._registry[self.key] = self
+        type(self)._registry[self.key] = self      # each store class has a key space of its own
 
     @classmethod
     def find(cls, key):
@@ -463,19 +474,30 @@ class FeatureStore(FeatureTable):
             raise RuntimeError(f"FeatureStore: the VGG returned {tuple(out.shape)} {out.dtype}, not fp32 [n, {self.F}] without grad")
         return out if out.is_contiguous() else out.contiguous()
 
+    def _refuse_trainable(self, vgg):
+        from ._lib import UmprHipError
+        if any(p.requires_grad for p in vgg.parameters()):
+            raise UmprHipError("FeatureStore: the VGG has trainable parameters, so its output for a photo is no constant of the "
+                               "run: build the model with freeze_vgg=True")
+
+    _fingerprint = staticmethod(vgg_fingerprint)
+    _emptied = "feature store: the VGG parameters changed; emptied"
+
+    def _out(self, n):
+        """What `features` returns; the fetch writes the n rows at its base."""
+        return torch.empty(n, self.F, dtype=torch.float32, device=self.device)
+
     def features(self, raw, vgg, non_blocking=False):
         """float32 [B*V*P, 1000] on the current stream: what `vgg(raw.to(device).flatten(0, 2))` returns for a frozen `vgg`, with
         the VGG run only on the photos the store lacks."""
         from ._lib import UmprHipError, lib
-        if any(p.requires_grad for p in vgg.parameters()):
-            raise UmprHipError("FeatureStore: the VGG has trainable parameters, so its output for a photo is no constant of the "
-                               "run: build the model with freeze_vgg=True")
+        self._refuse_trainable(vgg)
         dw, dh = raw.size
         n = int(np.prod(raw.geometry))
         if raw.data.dtype != torch.uint8 or raw.data.dim() != 1 or raw.data.numel() < n * DESC.itemsize:
             raise UmprHipError(f"RawPhotos: buffer of {raw.data.numel()} bytes cannot hold the {n} photo descriptors")
-        if self.guard(vgg_fingerprint(vgg)):
-            logging.getLogger(__name__).info("feature store: the VGG parameters changed; emptied")
+        if self.guard(self._fingerprint(vgg)):
+            logging.getLogger(__name__).info(self._emptied)
         src, dst, row, miss, full = self.plan(raw)
         call = lambda *a: lib().call("umpr_feature_fetch_f32", *a)
         with torch.cuda.device(self.device):
@@ -499,7 +521,7 @@ class FeatureStore(FeatureTable):
                 lib().call("umpr_photo_resize_u8", packed, packed.numel(), desc.ctypes.data, len(miss), dh, dw, images,
                            stream.cuda_stream)
                 fresh = self._vgg(vgg, images)
-            out = torch.empty(n, self.F, dtype=torch.float32, device=self.device)
+            out = self._out(n)
             call(fresh, len(miss), row.ctypes.data, src.ctypes.data, dst.ctypes.data, n, self.F, self.buffer, self.slots + 1, out,
                  stream.cuda_stream)
             if self.commit(raw, src, dst, row, full) or filled:      # the workers skip these only now that the fill is enqueued
@@ -513,4 +535,45 @@ class FeatureStore(FeatureTable):
 
     def __repr__(self):
         return (f"FeatureStore({self.used}/{self.slots} slots of {self.slot_bytes} B on {self.device}, "
+                f"{len(self.index.ids)} photos registered)")
+
+
+class Pool5Store(FeatureStore):
+    """pool5 rows of photos kept in device memory: `capacity_bytes // 100352` slots of 25088 fp32 plus the reserved row of the
+    all-zero image.  For a FROZEN CONV BASE only (UMPR(freeze_conv=True)): the conv stage's output for a photo is then a constant
+    of the run while the classifier trains on it.  Plan, zero row, ids and `find` are FeatureStore's, in a key space of its own.
+    The store remembers the conv parameters that filled it (conv_fingerprint): an optimiser step on the classifier leaves it as it
+    is, a write to any conv parameter empties it.  Rows stay fp32 in both precisions; no eviction; gone with the process."""
+
+    F = 25088
+    _registry = weakref.WeakValueDictionary()
+
+    def _vgg(self, vgg, images):
+        self.vgg_calls += 1
+        out = vgg.conv_base(images)
+        if out.requires_grad or out.dtype != torch.float32 or tuple(out.shape) != (images.shape[0], self.F):
+            raise RuntimeError(f"Pool5Store: the conv base returned {tuple(out.shape)} {out.dtype}, not fp32 [n, {self.F}] without grad")
+        return out if out.is_contiguous() else out.contiguous()
+
+    def _refuse_trainable(self, vgg):
+        from ._lib import UmprHipError
+        if any(p.requires_grad for p in vgg.features.parameters()):
+            raise UmprHipError("Pool5Store: the conv base has trainable parameters, so its pool5 for a photo is no constant of the "
+                               "run: build the model with freeze_conv=True")
+
+    _fingerprint = staticmethod(conv_fingerprint)
+    _emptied = "pool5 store: the conv parameters changed; emptied"
+
+    def _out(self, n):
+        from ._lib import lib
+        return torch.empty(lib().size("umpr_vgg16_cls_arena_bytes", n) // 4, dtype=torch.float32, device=self.device)
+
+    def features(self, raw, vgg, non_blocking=False):
+        """The compact classifier arena of the batch (umpr_vgg16_cls_arena_bytes(B*V*P) as flat fp32) on the current stream, its
+        first B*V*P x 25088 floats filled with the photos' pool5 rows by the one fetch: ready for `vgg.classify(arena, B*V*P)`.
+        The conv base runs only on the photos the store lacks."""
+        return super().features(raw, vgg, non_blocking)
+
+    def __repr__(self):
+        return (f"Pool5Store({self.used}/{self.slots} slots of {self.slot_bytes} B on {self.device}, "
                 f"{len(self.index.ids)} photos registered)")
