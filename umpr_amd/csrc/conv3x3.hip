@@ -15,6 +15,7 @@
 #include "umpr_internal.h"
 #include "umpr_tiles.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -28,6 +29,92 @@ struct ConvParams {
   long p0_base;  // first flat pixel of this launch (a layer may be covered by a main launch + a finer-tiled tail)
   long p_end;    // one past the last flat pixel of this launch
 };
+
+// Epilogue of the implicit-GEMM kernels: y = [mask > 0] relu?(tot + bias) for the TM x TN accumulator tiles of one wave.
+// The first version tested p.bias / p.relu / p.mask and co < Cout per element, so each of a lane's 64 outputs was a chain of
+// its own - branch, load bias[co], wait, add, 64-bit co * HW, branch, load mask[o], wait, select, store - and every load
+// latency was exposed, 64 times in a row (gfx950 listing of <64,256,224>: 2800 instructions after the loop, 128 loads that each
+// met an immediate s_waitcnt vmcnt(0)).  Here
+//  * the pointer tests and "does this wave's tile end inside Cout" (TAIL) pick one instantiation, once per wave;
+//  * the bias comes in once per accumulator row - 16 * TM loads in one batch - not once per column tile;
+//  * the mask comes in batches of 16 * TM loads, one per column tile, and the batch of tile j + 1 is issued before the stores
+//    of tile j, so one load latency is exposed per wave, not one per element;
+//  * an element's offset is the per-lane base plus a compile-time multiple of HW;
+//  * without TAIL the stores of a column tile sit under ONE exec mask (the lane has a pixel); with TAIL each is predicated.
+// rowu = first output channel of the wave's tile (wave-uniform), half = lane >> 5, row0 = rowu + 4 * half = the lane's first
+// channel; obase[j] = n * Cout * HW + yx of the lane's
+// pixel in column tile j, or of ANY pixel of the launch when the lane has none (pv[j] false).
+// Nothing outside the tensors is touched: a lane without a pixel loads the mask of the pixel obase names and stores nothing;
+// rows co >= Cout load bias[Cout - 1] and the mask word of row Cout - 1 of that pixel and store nothing.
+template <int TM, int TN, bool BIAS, bool MASK, bool TAIL>
+__device__ __forceinline__ void igemm_epilogue_as(const f32x16 (&tot)[TM][TN], const ConvParams& p, int HW, int row0,
+                                                  const long (&obase)[TN], const bool (&pv)[TN]) {
+  const int Cout = p.Cout;
+  const bool relu = p.relu != 0;
+  float bv[TM][16];
+  if constexpr (BIAS) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int co = row0 + i * 32 + mfma_row(r, 0);
+        bv[i][r] = p.bias[TAIL ? min(co, Cout - 1) : co];
+      }
+  }
+  float mv[2][TM][16];
+  auto load_mask = [&](int j) {
+    const float* mp = p.mask + obase[j] + (long)row0 * HW;
+    const float* mlast = p.mask + obase[j] + (long)(Cout - 1) * HW;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int ro = i * 32 + mfma_row(r, 0);
+        mv[j & 1][i][r] = *(!TAIL || row0 + ro < Cout ? mp + (long)ro * HW : mlast);
+      }
+  };
+  if constexpr (MASK) load_mask(0);
+#pragma unroll
+  for (int j = 0; j < TN; ++j) {
+    if constexpr (MASK) {
+      if (j + 1 < TN) load_mask(j + 1);
+    }
+    if (pv[j]) {
+      float* yp = p.y + obase[j] + (long)row0 * HW;
+#pragma unroll
+      for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int ro = i * 32 + mfma_row(r, 0);
+          float v = tot[i][j][r];
+          if constexpr (BIAS) v += bv[i][r];
+          const float vr = fmaxf(v, 0.f);
+          v = relu ? vr : v;
+          if constexpr (MASK) v = mv[j & 1][i][r] > 0.f ? v : 0.f;
+          if (!TAIL || row0 + ro < Cout) yp[(long)ro * HW] = v;
+        }
+    }
+  }
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void igemm_epilogue(const f32x16 (&tot)[TM][TN], const ConvParams& p, int HW, int rowu, int half,
+                                               const long (&obase)[TN], const bool (&pv)[TN]) {
+  const int row0 = rowu + 4 * half;
+  auto run = [&](auto bias, auto mask) {
+    if (rowu + TM * 32 <= p.Cout) igemm_epilogue_as<TM, TN, decltype(bias)::value, decltype(mask)::value, false>(tot, p, HW, row0, obase, pv);
+    else igemm_epilogue_as<TM, TN, decltype(bias)::value, decltype(mask)::value, true>(tot, p, HW, row0, obase, pv);
+  };
+  using T = std::true_type;
+  using F = std::false_type;
+  if (p.mask) {
+    if (p.bias) run(T{}, T{});
+    else run(F{}, T{});
+  } else {
+    if (p.bias) run(T{}, F{});
+    else run(F{}, F{});
+  }
+}
 
 template <int BM, int BN>
 __global__ __launch_bounds__(256) void conv3x3_igemm_kernel(ConvParams p) {
@@ -156,28 +243,16 @@ __global__ __launch_bounds__(256) void conv3x3_igemm_kernel(ConvParams p) {
       for (int j = 0; j < TN; ++j) tot[i][j] += acc[i][j];
   }
 
+  long obase[TN];
+  bool pv[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
     const long pq = p0 + wn * WTN + j * 32 + l31;
-    if (pq >= NP) continue;
-    const int n = (int)(pq / HW), yx = (int)(pq % HW);
-    const long obase = (long)n * p.Cout * HW + yx;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = m0 + wm * WTM + i * 32 + mfma_row(r, lane);
-        if (co < p.Cout) {
-          float v = tot[i][j][r];
-          if (p.bias) v += p.bias[co];
-          if (p.relu) v = fmaxf(v, 0.f);
-          const long o = obase + (long)co * HW;
-          if (p.mask) v = p.mask[o] > 0.f ? v : 0.f;
-          p.y[o] = v;
-        }
-      }
-    }
+    pv[j] = pq < NP;
+    const long pc = pv[j] ? pq : p0;      // p0 < NP: the grid covers no tile past the end
+    obase[j] = (pc / HW) * p.Cout * HW + pc % HW;
   }
+  igemm_epilogue<TM, TN>(tot, p, HW, m0 + __builtin_amdgcn_readfirstlane(wm) * WTM, kh, obase, pv);
 }
 
 // ------------------------------------------------------------------------------------------------------------
@@ -231,7 +306,9 @@ __global__ __launch_bounds__(256, (BN == 64 && !(BM == 128 && W == 224) ? 3 : 2)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, half = lane >> 5;
-  const int H = p.H, HW = H * W, HP = H + 2;
+  // square maps only (umpr_conv3x3_run requires H == W == the template W): the geometry is compile-time, so every split of a
+  // flat pixel into image / row / column below is a multiply-shift, not a division sequence
+  constexpr int H = W, HW = H * W, HP = H + 2;
   // XCD-aware tile order: workgroups b, b+8, b+16, ... share an XCD (and its L2).  The Cout/BM workgroups that read
   // the SAME pixel tile get consecutive slots on one XCD, so the input patch is fetched into that L2 once instead of
   // once per output-channel tile (FETCH_SIZE showed 2.6x the compulsory bytes with the pixel-major order).
@@ -245,28 +322,36 @@ __global__ __launch_bounds__(256, (BN == 64 && !(BM == 128 && W == 224) ? 3 : 2)
   const int ns = (p.C + CC - 1) / CC;
   const int Kp = ns * KC;
   const int n0 = (int)(p0 / HW);
-  const int y0 = (int)(p0 % HW) / W;
-  const long v_first = (long)n0 * HP + y0 + 1;
+  const int yx0 = (int)(p0 - (long)n0 * HW);  // the tile's first pixel inside image n0: pixel d of the tile is pixel yx0 + d
+  const int y0 = yx0 / W;                     // counted from the start of image n0, so the per-lane arithmetic below is 32-bit
 
+  // virtual row v_first - 1 + tid = n0 * HP + (y0 + tid): image n0 + t / HP, row t % HP - 1 with t = y0 + tid
   if (tid < PR) {
-    const long v = v_first - 1 + tid;
-    const int nr = (int)(v / HP);
-    const int yy = (int)(v - (long)nr * HP) - 1;
-    rowsrc[tid] = (v >= 0 && nr < p.N && yy >= 0 && yy < H) ? ((long)nr * p.C * H + yy) * W : -1;
+    const int t = y0 + tid;
+    const int nr = n0 + t / HP;
+    const int yy = t % HP - 1;
+    rowsrc[tid] = (nr < p.N && yy >= 0 && yy < H) ? ((long)nr * p.C * H + yy) * W : -1;
   }
-  for (int e = tid; e < 2 * CC * PLANE; e += 256) (&Ps[0][0])[e] = 0.f;  // halo columns stay zero for good
+  // The staging writes columns 0 .. W-1 of all PR rows of all CC planes of a buffer in every stage (zeros where rowsrc is -1 or
+  // the channel is past C), and both buffers are staged before their first fragment read.  What it never writes is the halo: the
+  // four leading zeros of a plane and the slots W .. W+3 of each row, i.e. floats slot * RW .. slot * RW + 3 of a plane for slot
+  // = 0 .. PR.  Only those are zeroed here, for good (the first version cleared both buffers whole: up to 36 stores per thread).
+  constexpr int HALO = (PR + 1) * 4;
+  for (int e = tid; e < 2 * CC * HALO; e += 256) {
+    const int pl = e / HALO, h = e - pl * HALO;
+    (&Ps[0][0])[pl * PLANE + (h >> 2) * RW + (h & 3)] = 0.f;
+  }
   __syncthreads();
 
   // per-lane B base offsets (floats) for the TN column tiles
+  const int dlast = NP - p0 < BN ? (int)(NP - p0) - 1 : BN - 1;  // pixels past the end of the launch read the last pixel's patch slot
   int boff[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
-    long pq = p0 + wn * WTN + j * 32 + l31;
-    if (pq >= NP) pq = NP - 1;
-    const int n = (int)(pq / HW), yx = (int)(pq % HW);
+    const int loc = yx0 + min(wn * WTN + j * 32 + l31, dlast);
+    const int dn = loc / HW, yx = loc - dn * HW;
     const int y = yx / W, x = yx - y * W;
-    const long v = (long)n * HP + y + 1;
-    boff[j] = 3 + (int)(v - v_first) * RW + x + half * 2 * PLANE;
+    boff[j] = 3 + (dn * HP + y - y0) * RW + x + half * 2 * PLANE;
   }
   // per-thread staging geometry (stage independent)
   const float* asrc[AV];
@@ -398,28 +483,17 @@ __global__ __launch_bounds__(256, (BN == 64 && !(BM == 128 && W == 224) ? 3 : 2)
       for (int j = 0; j < TN; ++j) tot[i][j] += acc[i][j];
   }
 
+  long obase[TN];
+  bool pv[TN];
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
-    const long pq = p0 + wn * WTN + j * 32 + l31;
-    if (pq >= NP) continue;
-    const int n = (int)(pq / HW), yx = (int)(pq % HW);
-    const long obase = (long)n * p.Cout * HW + yx;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int co = m0 + wm * WTM + i * 32 + mfma_row(r, lane);
-        if (co < p.Cout) {
-          float v = tot[i][j][r];
-          if (p.bias) v += p.bias[co];
-          if (p.relu) v = fmaxf(v, 0.f);
-          const long o = obase + (long)co * HW;
-          if (p.mask) v = p.mask[o] > 0.f ? v : 0.f;
-          p.y[o] = v;
-        }
-      }
-    }
+    const int d = wn * WTN + j * 32 + l31;
+    pv[j] = d <= dlast;
+    const int loc = yx0 + min(d, dlast);
+    const int dn = loc / HW;
+    obase[j] = (long)(n0 + dn) * p.Cout * HW + (loc - dn * HW);
   }
+  igemm_epilogue<TM, TN>(tot, p, HW, m0 + __builtin_amdgcn_readfirstlane(wm) * WTM, half, obase, pv);
 }
 
 // wp[m][stage][k'] from w [Cout][Cin][3][3].  transposed = 0: m = cout, reduction channel c = cin, tap as is;
@@ -1276,6 +1350,8 @@ int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float
     case CONV_DIRECT: {
       const long total = (long)M * ((C + V2_CC - 1) / V2_CC) * V2_KC;
       UMPR_REQUIRE(wpack_floats >= (size_t)total, "conv3x3: weight scratch too small");
+      // the kernels take their whole geometry from the template width
+      UMPR_REQUIRE(H == W && (W == 224 || W == 112 || W == 56 || W == 28 || W == 14), "conv3x3: the direct kernels need a square VGG map, not %dx%d", H, W);
       int blocks = (int)((total + 255) / 256);
       if (blocks > 4096) blocks = 4096;
       pack_weights_kernel<<<blocks, 256, 0, s>>>(w, wpack, M, C, Cin, transposed);
