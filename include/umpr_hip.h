@@ -510,6 +510,17 @@ int umpr_adam_step_clip(float* p, const float* g, float* m, float* v, long n, do
 int umpr_adam_step_dev_clip(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
                             const float* hyper, const float* state, void* stream);
 
+/* ---- Gradient accumulation: one optimiser step over several micro-batches ((loss / k).backward() k times, then step()) ----
+ * first != 0: acc[i][:] = grads[i][:] - acc is not read, so it needs no zeroing, whatever it holds (the inf or NaN of a skipped
+ * step included).  first == 0: acc[i][:] += grads[i][:], one IEEE fp32 add per element, so the chained sum over the micro-batches
+ * is the same bits on every run.  The factor 1 / k is not applied here: it goes into the grad_scale of umpr_grad_norm and of the
+ * Adam entry points, which then read acc in place of the gradient.  acc / grads / counts are HOST arrays of n_arenas (<= 8)
+ * device pointers / element counts, read during the call; any float-aligned pointers and any count >= 0 are accepted (16-byte
+ * accesses where acc[i] and grads[i] sit alike inside a 16-byte line, element by element where they do not); acc[i] and grads[i]
+ * must not overlap.  n_arenas == 0 or all counts 0 launches nothing.  One launch on a fixed grid; no allocation, no copy, no host
+ * synchronisation: capture-safe. */
+int umpr_grad_accumulate(float* const* acc, const float* const* grads, const long* counts, int n_arenas, int first, void* stream);
+
 /* ---- evaluate_mse (src/evaluate.py:12-13, `mse_loss(pred, labels, reduction='sum')` accumulated over batches) -----
  * acc[0] += sum_i (pred[i] - label[i])^2, acc[1] += n; acc = two device doubles the caller zeroed once and reads back
  * once after the last batch (the reference's `.item()` per batch is a host sync per batch). */

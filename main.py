@@ -3,6 +3,7 @@
 
     python main.py --data_dir synthetic --batch_size 64                       # single MI355X
     python main.py --data_dir synthetic --learning_rate 1e-3 --grad_clip 5.0  # clip the gradient to a global 2-norm of 5
+    python main.py --data_dir synthetic --batch_size 32 --accum_steps 8       # one Adam step per 8 batches of 32: an effective 256
     python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
                                                                                   # for every photo kept in 1 GB of HBM
     python main.py --data_dir data/music --freeze_conv True --pool5_store_gb 8    # freeze the conv base, train the classifier on
@@ -194,7 +195,7 @@ def main():
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
-                 "freeze_conv": False, "pool5_store_gb": 0.0}
+                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1}
 
 
 def check_flags(config):
@@ -208,6 +209,11 @@ def check_flags(config):
     if config.sparse_embedding and not config.train_embedding:
         sys.exit("--sparse_embedding needs --train_embedding True: it chooses how a trainable table is updated (the rows a step "
                  "names only, as torch.optim.SparseAdam would)")
+    if isinstance(config.accum_steps, bool) or not isinstance(config.accum_steps, int) or config.accum_steps < 1:
+        sys.exit(f"--accum_steps takes a whole number >= 1 (micro-batches per optimiser step), got {config.accum_steps!r}")
+    if config.accum_steps > 1 and config.sparse_embedding:
+        sys.exit("--accum_steps > 1 and --sparse_embedding True exclude each other: every micro-batch names other rows of the "
+                 "table (accumulate with --sparse_embedding False)")
     if config.pool5_store_gb > 0 and config.feature_store_gb > 0:
         sys.exit("--pool5_store_gb and --feature_store_gb exclude each other: --feature_store_gb belongs to --freeze_vgg True, "
                  "--pool5_store_gb to --freeze_conv True")

@@ -118,6 +118,7 @@ SIGNATURES = {
     "umpr_grad_norm": ("ppidfppzpp", "i"),
     "umpr_adam_step_clip": ("ppppldddddld" "pp", "i"),
     "umpr_adam_step_dev_clip": ("pppplddd" "ppp", "i"),
+    "umpr_grad_accumulate": ("pppiip", "i"),
     "umpr_debug_poison_lds": ("pp", "i"),
     "umpr_set_gemm_bf16": ("i", "i"),
     "umpr_set_conv_inference": ("i", "i"),

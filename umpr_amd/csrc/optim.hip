@@ -1,5 +1,6 @@
 // Gradient clipping by global norm inside the optimiser step: one deterministic 2-norm over the flat gradient arenas and the two
 // Adam kernels of text_ops.hip with the clip coefficient read from device memory (umpr_amd/optim.py::FusedAdam(max_grad_norm=)).
+// And the sum of the gradient arenas over the micro-batches of one optimiser step (FusedAdam.accumulate, --accum_steps).
 #include <math.h>
 
 #include "../../include/umpr_hip.h"
@@ -126,6 +127,64 @@ __global__ void adam_dev_clip_kernel(float* __restrict__ p, const float* __restr
   }
 }
 
+// Gradient accumulation over micro-batches (FusedAdam.accumulate): acc = g (FIRST: acc is never read, so whatever it holds - the
+// NaN or inf of a skipped step included - costs no zeroing pass) or acc += g, one fp32 add per element.  A pure HBM stream of 8
+// or 12 bytes per element on the fixed grid of the norm kernel above; elementwise, so the grid has no say in the result.  Per
+// arena: scalar elements in front of the first 16-byte boundary, float4s in grid-stride order (four independent loads per
+// stream and thread while at least four passes remain), scalar elements behind the last whole float4.  Where the two bases
+// sit differently inside a 16-byte line no float4 fits both, and the arena goes element by element.
+constexpr int GA_BLOCKS = GN_BLOCKS, GA_THREADS = GN_THREADS, GA_MAX_ARENAS = GN_MAX_ARENAS;
+constexpr long GA_SWEEP = (long)GA_BLOCKS * GA_THREADS;   // float4s (or, on the scalar path, floats) one pass of the grid covers
+
+struct AccArenas {
+  float* acc[GA_MAX_ARENAS];
+  const float* g[GA_MAX_ARENAS];
+  long n[GA_MAX_ARENAS];
+  int count;
+};
+
+template <bool FIRST>
+__device__ __forceinline__ float acc1(float a, float g) { return FIRST ? g : a + g; }
+template <bool FIRST>
+__device__ __forceinline__ float4 acc4(const float4 a, const float4 g) {
+  return FIRST ? g : make_float4(a.x + g.x, a.y + g.y, a.z + g.z, a.w + g.w);
+}
+
+template <bool FIRST>
+__global__ void __launch_bounds__(GA_THREADS) grad_accumulate_kernel(const AccArenas A) {
+  const long gid = (long)blockIdx.x * GA_THREADS + threadIdx.x;
+  const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int a = 0; a < A.count; ++a) {
+    float* __restrict__ acc = A.acc[a];
+    const float* __restrict__ g = A.g[a];
+    const long n = A.n[a];
+    if (n <= 0) continue;
+    if ((((uintptr_t)acc ^ (uintptr_t)g) & 15u) != 0) {
+      for (long i = gid; i < n; i += GA_SWEEP) acc[i] = acc1<FIRST>(FIRST ? 0.f : acc[i], g[i]);
+      continue;
+    }
+    long head = (long)(((16u - (unsigned)((uintptr_t)g & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    const long tail0 = head + 4 * n4;
+    float4* __restrict__ acc_4 = reinterpret_cast<float4*>(acc + head);
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g + head);
+    long i = gid;
+    for (; i + 3 * GA_SWEEP < n4; i += 4 * GA_SWEEP) {
+      const float4 q0 = g4[i], q1 = g4[i + GA_SWEEP], q2 = g4[i + 2 * GA_SWEEP], q3 = g4[i + 3 * GA_SWEEP];
+      const float4 a0 = FIRST ? none : acc_4[i], a1 = FIRST ? none : acc_4[i + GA_SWEEP];
+      const float4 a2 = FIRST ? none : acc_4[i + 2 * GA_SWEEP], a3 = FIRST ? none : acc_4[i + 3 * GA_SWEEP];
+      acc_4[i] = acc4<FIRST>(a0, q0);
+      acc_4[i + GA_SWEEP] = acc4<FIRST>(a1, q1);
+      acc_4[i + 2 * GA_SWEEP] = acc4<FIRST>(a2, q2);
+      acc_4[i + 3 * GA_SWEEP] = acc4<FIRST>(a3, q3);
+    }
+    for (; i < n4; i += GA_SWEEP) acc_4[i] = acc4<FIRST>(FIRST ? none : acc_4[i], g4[i]);
+    if (gid < head) acc[gid] = acc1<FIRST>(FIRST ? 0.f : acc[gid], g[gid]);
+    if (gid < n - tail0) acc[tail0 + gid] = acc1<FIRST>(FIRST ? 0.f : acc[tail0 + gid], g[tail0 + gid]);
+  }
+}
+
 inline int adam_blocks(long n) {      // the grid of umpr_adam_impl / umpr_adam_dev_impl
   long b = (n + 255) / 256;
   return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
@@ -157,6 +216,29 @@ int umpr_grad_norm(const float* const* grads, const long* counts, int n_arenas, 
   UMPR_LAUNCH_CHECK("grad_norm stage 1");
   grad_norm_finish_kernel<<<1, GN_THREADS, 0, S(stream)>>>(ws, max_norm, grad_scale, grad_scale_dev, state);
   UMPR_LAUNCH_CHECK("grad_norm stage 2");
+  return 0;
+}
+
+int umpr_grad_accumulate(float* const* acc, const float* const* grads, const long* counts, int n_arenas, int first,
+                         void* stream) {
+  UMPR_REQUIRE(n_arenas >= 0 && n_arenas <= GA_MAX_ARENAS, "grad_accumulate: %d arenas outside 0..%d", n_arenas, GA_MAX_ARENAS);
+  UMPR_REQUIRE(n_arenas == 0 || (acc != nullptr && grads != nullptr && counts != nullptr), "grad_accumulate: null arena table");
+  AccArenas A;
+  A.count = n_arenas;
+  long total = 0;
+  for (int a = 0; a < GA_MAX_ARENAS; ++a) {
+    A.acc[a] = a < n_arenas ? acc[a] : nullptr;
+    A.g[a] = a < n_arenas ? grads[a] : nullptr;
+    A.n[a] = a < n_arenas ? counts[a] : 0;
+    UMPR_REQUIRE(A.n[a] >= 0 && (A.n[a] == 0 || (A.acc[a] != nullptr && A.g[a] != nullptr)),
+                 "grad_accumulate: arena %d: bad pointer / count", a);
+    UMPR_REQUIRE((((uintptr_t)A.acc[a] | (uintptr_t)A.g[a]) & 3u) == 0, "grad_accumulate: arena %d is not aligned to a float", a);
+    total += A.n[a];
+  }
+  if (total == 0) return 0;
+  if (first) grad_accumulate_kernel<true><<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A);
+  else grad_accumulate_kernel<false><<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A);
+  UMPR_LAUNCH_CHECK("grad_accumulate");
   return 0;
 }
 

@@ -126,7 +126,15 @@ class FusedAdam:
     launches ``umpr_sparse_adam_rows`` behind the dense groups: the rows the step's batch named - ``model._sparse_rows``, written
     by the backward - are updated as ``torch.optim.SparseAdam(lr, betas, eps)`` updates them (no L2, eps added to sqrt(v)), every
     other row keeps each byte of its value and moments.  With clipping the row gradients are one more arena of the norm, and
-    the row kernel reads the same coefficient."""
+    the row kernel reads the same coefficient.
+
+    ``accumulate()`` makes one step out of several micro-batches, as ``(loss / k).backward()`` k times before ``step()`` does:
+    called behind each backward it folds the gradient arenas into accumulation arenas of the same size (``umpr_grad_accumulate``:
+    the first micro-batch overwrites them, the others add, one fp32 add per element in micro-batch order) and counts in
+    ``pending``.  The next ``step(grad_scale)`` then reads the accumulation arenas in place of the gradient arenas with the scale
+    ``grad_scale / pending`` - the mean over the micro-batches, which the norm of a clipped step sees as well - and sets
+    ``pending`` back to 0.  No early classifier update while anything is pending; not with a sparse table (its rows differ per
+    micro-batch) and not in graph mode.  An optimiser that never accumulates allocates and launches nothing for it."""
 
     def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None,
                  max_grad_norm=0.0):
@@ -135,6 +143,8 @@ class FusedAdam:
             raise ValueError(f"max_grad_norm must be finite and >= 0 (0 turns clipping off), got {max_grad_norm}")
         self.max_grad_norm = max_grad_norm
         self._clip = None           # device state of the clipping path, made by the first clipped step
+        self.pending = 0            # micro-batches folded into the accumulation arenas since the last step
+        self._acc = None            # (arena per group, pointer tables of umpr_grad_accumulate), made by the first accumulate()
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         self.sparse = None          # (name, parameter, m, v) of a table updated row-wise
         if getattr(model, "sparse_embedding", False):
@@ -247,6 +257,8 @@ class FusedAdam:
             return
         if not self._has_classifier:                         # frozen VGG: there is no slice to update early
             return
+        if self.pending > 0:                                 # the slice of the last micro-batch is not the group's gradient
+            return
         self._early = (float(grad_scale),)
         self._early_done = None
 
@@ -325,28 +337,64 @@ class FusedAdam:
         return {"norm": float(host[1]), "coef": float(host[0]), "clipped": int(cnt[5]), "skipped": int(cnt[6]),
                 "seen": int(cnt[4])}
 
-    def _step_clipped(self, grad_scale):
+    def _step_clipped(self, grad_scale, acc=None):
         state, ws, ws_bytes, ptrs, counts, n_arenas = self._clip_buffers()
-        n_arenas = self._sparse_arena(ptrs, counts, n_arenas)
         hyper = getattr(self, "_hyper", None)
-        for g in self.groups:                          # the norm reads every arena: all stale slices are zeroed first
-            for p in g.direct:
-                if getattr(p, "_umpr_fresh", False):   # no backward node wrote it since zero_grad: its gradient is zero
-                    p.grad.zero_()
-                    p._umpr_fresh = False
+        if acc is None:
+            n_arenas = self._sparse_arena(ptrs, counts, n_arenas)
+            for g in self.groups:                      # the norm reads every arena: all stale slices are zeroed first
+                self._zero_unwritten(g)
+        else:                                          # the norm of the accumulated gradient: the same counts, the other arenas
+            ptrs = self._acc[1]
         # every group carries the same grad_scale: in graph mode the norm kernel reads the first group's from device memory
         lib().call("umpr_grad_norm", ctypes.addressof(ptrs), ctypes.addressof(counts), n_arenas, self.max_grad_norm,
                    float(grad_scale), hyper[0] if hyper is not None else None, ws, ws_bytes, state, stream_ptr())
         for gi, g in enumerate(self.groups):
             if not g.numel:
                 continue
+            gg = g.g if acc is None else acc[gi]
             if hyper is not None:
-                lib().call("umpr_adam_step_dev_clip", g.p, g.g, g.m, g.v, g.numel, self.betas[0], self.betas[1], self.eps,
+                lib().call("umpr_adam_step_dev_clip", g.p, gg, g.m, g.v, g.numel, self.betas[0], self.betas[1], self.eps,
                            hyper[gi], state, stream_ptr())
             else:
-                lib().call("umpr_adam_step_clip", g.p, g.g, g.m, g.v, g.numel, self.lr, self.betas[0], self.betas[1], self.eps,
+                lib().call("umpr_adam_step_clip", g.p, gg, g.m, g.v, g.numel, self.lr, self.betas[0], self.betas[1], self.eps,
                            g.weight_decay, self.step_count, grad_scale, state, stream_ptr())
         self._step_sparse(grad_scale, state)
+
+    # ---- accumulation over micro-batches ---------------------------------------------------------------------------------------
+    def _zero_unwritten(self, g):
+        for p in g.direct:
+            if getattr(p, "_umpr_fresh", False):       # no backward node wrote it since zero_grad: its gradient is zero
+                p.grad.zero_()
+                p._umpr_fresh = False
+
+    def accumulate(self):
+        """Fold the gradient the last backward left in the arenas into the accumulation arenas: the step's first micro-batch
+        overwrites them (they are never zeroed, and what a skipped step left in them is never read), every later one adds."""
+        if self.sparse is not None:
+            raise NotImplementedError("FusedAdam.accumulate: not with a sparse table (--sparse_embedding True): every micro-batch "
+                                      "names other rows (accumulate with --sparse_embedding False)")
+        if getattr(self, "_hyper", None) is not None:
+            raise NotImplementedError("FusedAdam.accumulate: not in graph mode: a captured step is one batch, one update")
+        if self.groups[0].p.device.type != "cuda":
+            raise RuntimeError("FusedAdam.accumulate launches a HIP kernel: the model must be on a cuda device")
+        if self._early_done is not None:
+            raise RuntimeError("FusedAdam.accumulate: this backward was armed for an early update (arm_early) and the classifier "
+                               "slice has already been stepped with its gradient alone")
+        self._early = None
+        wait_for_gradients(self.groups[0].p.device)    # in-place gradients written from a side stream (umpr_amd/streams.py)
+        for g in self.groups:
+            self._zero_unwritten(g)
+        if self._acc is None:
+            live = [g for g in self.groups if g.numel]
+            arenas = [torch.empty_like(g.g) for g in self.groups]
+            table = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+            self._acc = (arenas, table([a for a in arenas if a.numel()]), table([g.g for g in live]),
+                         (ctypes.c_long * max(len(live), 1))(*[g.numel for g in live]), len(live))
+        _, acc_ptrs, grad_ptrs, counts, n_arenas = self._acc
+        lib().call("umpr_grad_accumulate", ctypes.addressof(acc_ptrs), ctypes.addressof(grad_ptrs), ctypes.addressof(counts),
+                   n_arenas, int(self.pending == 0), stream_ptr())
+        self.pending += 1
 
     # ---- the row-wise update of a sparse table ---------------------------------------------------------------------------------
     def _sparse_rows(self):
@@ -377,18 +425,24 @@ class FusedAdam:
         if self.groups[0].p.device.type != "cuda":
             raise RuntimeError("FusedAdam.step launches a HIP kernel: the model must be on a cuda device")
         self.step_count += 1
-        wait_for_gradients(self.groups[0].p.device)    # in-place gradients written from a side stream (umpr_amd/streams.py)
+        acc = None
+        if self.pending > 0:
+            # the step of a group of micro-batches: accumulate() has waited for and folded each of them, the last one included;
+            # the kernels below read the accumulation arenas, and the mean over the group rides on the gradient scale
+            acc, grad_scale, self.pending = self._acc[0], grad_scale / self.pending, 0
+        else:
+            wait_for_gradients(self.groups[0].p.device)    # in-place gradients written from a side stream (umpr_amd/streams.py)
         done, self._early_done, self._early = self._early_done, None, None
+        assert acc is None or done is None             # accumulate() refuses a backward that was stepped early
         if self.max_grad_norm > 0.0:
             assert done is None                        # arm_early never armed
-            return self._step_clipped(grad_scale)
+            return self._step_clipped(grad_scale, acc)
         for gi, g in enumerate(self.groups):
-            for p in g.direct:
-                if getattr(p, "_umpr_fresh", False):   # no backward node wrote it since zero_grad: its gradient is zero
-                    p.grad.zero_()
-                    p._umpr_fresh = False
+            if acc is None:
+                self._zero_unwritten(g)
             if not g.numel:
                 continue
+            gg = g.g if acc is None else acc[gi]
             ranges = [(0, g.numel)]
             if gi == 0 and done is not None:           # the classifier slice was updated during backward
                 lo, hi, ev = done
@@ -396,10 +450,10 @@ class FusedAdam:
                 torch.cuda.current_stream(g.p.device).wait_event(ev)
             for lo, hi in ranges:
                 if hi > lo and getattr(self, "_hyper", None) is not None:
-                    lib().call("umpr_adam_step_dev", g.p[lo:hi], g.g[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.betas[0],
+                    lib().call("umpr_adam_step_dev", g.p[lo:hi], gg[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.betas[0],
                                self.betas[1], self.eps, self._hyper[gi], stream_ptr())
                 elif hi > lo:
-                    lib().call("umpr_adam_step", g.p[lo:hi], g.g[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.lr,
+                    lib().call("umpr_adam_step", g.p[lo:hi], gg[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.lr,
                                self.betas[0], self.betas[1], self.eps, g.weight_decay, self.step_count, grad_scale,
                                stream_ptr())
         self._step_sparse(grad_scale, None)
@@ -484,6 +538,11 @@ class FusedAdam:
 
     def grad_arenas(self):
         return [g.g for g in self.groups if g.numel]
+
+    def accum_arenas(self):
+        """The accumulation arenas, one per entry of grad_arenas(), or None before the first accumulate().  After a step they
+        still hold the sum that step used."""
+        return None if self._acc is None else [a for a in self._acc[0] if a.numel()]
 
     def early_bucket(self):
         """(arena, lo, hi, parameters) of the classifier-weight slice of the weight arena, or None.  The slice is

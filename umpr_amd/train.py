@@ -43,13 +43,20 @@ def _one_like(loss):
     return t
 
 
-def train_step(model, opt: FusedAdam, batch, world=1, reducer=None):
+def train_step(model, opt: FusedAdam, batch, world=1, reducer=None, update=True):
     """model.train(); pred, loss = model(*batch); loss.mean(); zero_grad; backward; step  (main.py:32-37).
-    With world > 1 the gradients are summed over ranks (RCCL) - by `reducer` overlapped with backward if given."""
+    With world > 1 the gradients are summed over ranks (RCCL) - by `reducer` overlapped with backward if given.
+    `update=False` makes `batch` a micro-batch of a later step: forward, zero_grad, backward and opt.accumulate(), no step.  The
+    call with `update=True` that follows folds its own micro-batch in as well and takes ONE step on the mean gradient of the
+    group - `(loss / k).backward()` k times before `step()`; with nothing pending it is the plain step."""
     model.train()
     if (world > 1 or reducer is not None) and getattr(opt, "sparse", None) is not None:
         raise NotImplementedError("train_step: --sparse_embedding runs on one rank only: the table's sparse gradient has no arena "
                                   "to all-reduce (train with --sparse_embedding False on more than one)")
+    accumulating = not update or getattr(opt, "pending", 0) > 0
+    if accumulating and (world > 1 or reducer is not None):
+        raise NotImplementedError("train_step: gradient accumulation (update=False, --accum_steps) runs on one rank only: the "
+                                  "accumulated arenas have no exchange")
     n_active = getattr(batch, "n_active", world)     # ranks with a non-empty chunk of this batch (parallel.Shard)
     if batch[0].shape[0] == 0:
         # Fewer samples than ranks in a short last batch: DataParallel would run fewer replicas (main.py:82).  This rank
@@ -72,6 +79,13 @@ def train_step(model, opt: FusedAdam, batch, world=1, reducer=None):
     if loss.dim() > 0:               # main.py:34 takes the mean over DataParallel's per-replica losses; one process per
         loss = loss.mean()           # GPU returns a scalar, whose mean is itself (and costs five tiny kernels)
     opt.zero_grad()
+    if accumulating:
+        # no early update of the classifier slice: the gradient of one micro-batch is not the group's
+        loss.backward(gradient=_one_like(loss))
+        opt.accumulate()
+        if update:
+            opt.step(grad_scale=1.0 / n_active)
+        return pred, loss
     if world == 1 or reducer is not None:
         # the classifier slice may be updated as soon as its gradients are final: at once on one GPU, behind the reducer's
         # all-reduce of that slice when data parallel.  Without a reducer the exchange only happens after backward
@@ -114,7 +128,14 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     epoch's shuffle order, the position inside the epoch and the dropout counters all come from the checkpoint, so the
     resumed run visits the batches the uninterrupted run would have visited next.  `config.grad_clip` > 0 clips the gradient to
     that global 2-norm inside the optimiser step (FusedAdam(max_grad_norm=)); the log lines then carry the last norm and the
-    clipped / skipped counts."""
+    clipped / skipped counts.  `config.accum_steps` = k > 1 takes one optimiser step per k consecutive loader batches, on the mean
+    of their gradients (train_step(update=False) k - 1 times, then update=True), and one more for the k' < k batches an epoch may
+    end with.  `batch_counter` - validation interval, the 50000 limit, the checkpoint - then counts optimiser steps; checkpoints
+    are written right behind a step only, with `batch_in_epoch` the loader batches consumed, so a resumed run forms the same
+    groups.  Loss sums and log lines stay per loader batch."""
+    accum = int(getattr(config, "accum_steps", 1))
+    if accum > 1 and parallel.active():
+        raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
     log = logger.info if logger else print
     valid_mse = evaluate_mse(model, valid_dataloader)
     log(f'Initial validation mse is {valid_mse:.6f}')
@@ -134,29 +155,41 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
         if gen is not None and "epoch_rng" in meta:
             gen.set_state(meta["epoch_rng"].cpu())
         log(f'Resumed from {resume}: epoch {first_epoch}, batch {batch_counter} ({skip} batches into the epoch)')
+
+    def stepped(consumed):
+        """behind every optimiser step; `consumed`: loader batches of this epoch the step has used up"""
+        nonlocal batch_counter, best_loss, saved
+        batch_counter += 1
+        if batch_counter % valid_every == 0:
+            valid_mse = evaluate_mse(model, valid_dataloader)
+            log(f'Epoch {epoch:2d}; batch {batch_counter:5d}; train loss {total_loss / max(total_samples, 1):.6f}; '
+                f'valid mse {valid_mse:.6f}' + clip_note(opt))
+            if best_loss > valid_mse:        # valid_mse is all-reduced: every rank takes the same branch
+                best_loss = valid_mse
+                if rank == 0:
+                    save_checkpoint(model_path, model, opt, epoch, batch_counter, best_loss, batch_in_epoch=consumed,
+                                    epoch_rng=epoch_rng)
+                saved = True
+                if parallel.active():        # nobody runs ahead (and later loads) while rank 0 is still writing
+                    torch.distributed.barrier()
+
     for epoch in range(first_epoch, config.train_epochs):
-        total_loss, total_samples = 0.0, 0
+        total_loss, total_samples, consumed = 0.0, 0, 0
         t0 = time.perf_counter()
         epoch_rng = gen.get_state() if gen is not None else None
         for bi, batch in enumerate(train_dataloader):
+            consumed = bi + 1
             if epoch == first_epoch and bi < skip:   # consumed before the checkpoint was taken
                 continue
-            pred, loss = train_step(model, opt, batch, world, reducer)
+            update = consumed % accum == 0           # (always, without --accum_steps)
+            pred, loss = train_step(model, opt, batch, world, reducer, update)
             total_loss += loss.item() * len(pred)
             total_samples += len(pred)
-            batch_counter += 1
-            if batch_counter % valid_every == 0:
-                valid_mse = evaluate_mse(model, valid_dataloader)
-                log(f'Epoch {epoch:2d}; batch {batch_counter:5d}; train loss {total_loss / max(total_samples, 1):.6f}; '
-                    f'valid mse {valid_mse:.6f}' + clip_note(opt))
-                if best_loss > valid_mse:        # valid_mse is all-reduced: every rank takes the same branch
-                    best_loss = valid_mse
-                    if rank == 0:
-                        save_checkpoint(model_path, model, opt, epoch, batch_counter, best_loss, batch_in_epoch=bi + 1,
-                                        epoch_rng=epoch_rng)
-                    saved = True
-                    if parallel.active():        # nobody runs ahead (and later loads) while rank 0 is still writing
-                        torch.distributed.barrier()
+            if update:
+                stepped(consumed)
+        if accum > 1 and opt.pending > 0:            # the epoch ended inside a group: one step on the k' < k it holds
+            opt.step()
+            stepped(consumed)
         opt.epoch_end()
         dt = time.perf_counter() - t0
         log(f'Epoch {epoch:3d} done; train loss {total_loss / max(total_samples, 1):.6f}; '
