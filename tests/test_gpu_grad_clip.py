@@ -171,38 +171,72 @@ def test_adam_clip_kernel_vs_numpy(L, dev):
         assert err <= atol, (name, err)
 
 
-def test_adam_clip_kernels_with_coefficient_one_equal_the_plain_kernels(L, dev):
-    _, _, plain = _adam_inputs(dev)
-    _, _, plain_dev = _adam_inputs(dev)
-    _, _, clip = _adam_inputs(dev)
-    _, _, clip_dev = _adam_inputs(dev)
-    n = plain[0].numel()
+# The Adam launch: 256 threads, at most 8192 workgroups, grid-stride loop.  One thread; two workgroups, the second ragged; 391
+# workgroups; the smallest count at which every thread of the capped grid takes a second pass, with a ragged tail.
+ADAM_SIZES = [1, 257, 100003, 8192 * 256 + 77]
+ADAM_OFFSETS = [0, 1]       # floats: the optimiser passes slices of its arenas, so 16-byte alignment is not the kernel's to assume
+GUARD, GUARD_VALUE = 64, -7.5
+
+
+class _Guarded:
+    """`values` on the device, `off` floats behind a 256-byte boundary of a larger buffer with guard elements on both sides."""
+
+    def __init__(self, values, off, dev):
+        n = values.numel()
+        self.buf = torch.full((GUARD + off + n + GUARD,), GUARD_VALUE, dtype=torch.float32, device=dev)
+        self.t = self.buf[GUARD + off:GUARD + off + n]
+        self.t.copy_(values)
+        assert self.t.data_ptr() % 16 == 4 * off
+        self.lo, self.hi = GUARD + off, GUARD + off + n
+
+    def guards_untouched(self):
+        return bool((self.buf[:self.lo] == GUARD_VALUE).all()) and bool((self.buf[self.hi:] == GUARD_VALUE).all())
+
+
+def _guarded_set(start, off, dev):
+    return [_Guarded(t, off, dev) for t in start]
+
+
+@pytest.mark.parametrize("off", ADAM_OFFSETS)
+@pytest.mark.parametrize("n", ADAM_SIZES)
+def test_adam_clip_kernels_with_coefficient_one_equal_the_plain_kernels(L, dev, n, off):
+    g = torch.Generator().manual_seed(9)
+    start = [torch.randn(n, generator=g), torch.randn(n, generator=g) * 0.1, torch.zeros(n), torch.zeros(n)]
+    sets = [_guarded_set(start, off, dev) for _ in range(4)]
+    plain, plain_dev, clip, clip_dev = [[b.t for b in s] for s in sets]
     state = _state(1.0, 1.0, dev)
     for step in (1, 2, 3):
         L.call("umpr_adam_step", *plain, n, 1e-3, 0.9, 0.999, 1e-8, 1e-3, step, 0.5, st())
         L.call("umpr_adam_step_dev", *plain_dev, n, 0.9, 0.999, 1e-8, _hyper(step, 0.5, dev), st())
         L.call("umpr_adam_step_clip", *clip, n, 1e-3, 0.9, 0.999, 1e-8, 1e-3, step, 0.5, state, st())
         L.call("umpr_adam_step_dev_clip", *clip_dev, n, 0.9, 0.999, 1e-8, _hyper(step, 0.5, dev), state, st())
-    assert float((plain[0] - _adam_inputs(dev)[2][0]).abs().max()) > 1e-3      # the steps moved the parameters
+    assert float((plain[0] - start[0].to(dev)).abs().max()) > 1e-3      # the steps moved the parameters
     for k, name in ((0, "p"), (2, "m"), (3, "v")):
         for other in (plain_dev, clip, clip_dev):
             assert torch.equal(plain[k], other[k]), name
+    for s in sets:
+        for b in s:
+            assert b.guards_untouched()
 
 
-def test_adam_clip_kernels_leave_a_non_finite_step_untouched(L, dev):
+@pytest.mark.parametrize("off", ADAM_OFFSETS)
+@pytest.mark.parametrize("n", ADAM_SIZES)
+def test_adam_clip_kernels_leave_a_non_finite_step_untouched(L, dev, n, off):
     g = torch.Generator().manual_seed(10)
-    n = 100003
     start = [torch.randn(n, generator=g), torch.randn(n, generator=g), torch.rand(n, generator=g), torch.rand(n, generator=g)]
-    start[1][77] = float("inf")
+    start[1][min(77, n - 1)] = float("inf")
     state = _state(0.0, 0.0, dev)
     for name in ("umpr_adam_step_clip", "umpr_adam_step_dev_clip"):
-        pd, gd, md, vd = [t.to(dev) for t in start]
+        bufs = _guarded_set(start, off, dev)
+        pd, gd, md, vd = [b.t for b in bufs]
         if name.endswith("dev_clip"):
             L.call(name, pd, gd, md, vd, n, 0.9, 0.999, 1e-8, _hyper(1, 1.0, dev), state, st())
         else:
             L.call(name, pd, gd, md, vd, n, 1e-3, 0.9, 0.999, 1e-8, 1e-3, 1, 1.0, state, st())
         for got, ref in zip((pd, md, vd), (start[0], start[2], start[3])):
             assert torch.equal(got.cpu(), ref), name
+        for b in bufs:
+            assert b.guards_untouched()
 
 
 # ------------------------------------------------------------------------------------------------ UMPR-R against the oracle

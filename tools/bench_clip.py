@@ -66,16 +66,16 @@ def build(w, dev, max_grad_norm):
 def time_kernels(opt, reps=20):
     """Device-event time of the norm pass and of the Adam kernel (plain and with the coefficient) on this optimiser's arenas."""
     L = lib()
-    state, ws, ws_bytes, ptrs, counts, n_arenas = opt._clip_buffers()
+    c = opt._clip_buffers()
     g = opt.groups[0]
     n_all = sum(a.numel() for a in opt.grad_arenas())
 
     def norm():
-        L.call("umpr_grad_norm", ctypes.addressof(ptrs), ctypes.addressof(counts), n_arenas, 1e30, 1.0, None, ws, ws_bytes, state,
-               stream_ptr())
+        L.call("umpr_grad_norm", ctypes.addressof(c.ptrs), ctypes.addressof(c.counts), c.n_arenas, 1e30, 1.0, None, c.ws,
+               c.ws_bytes, c.state, stream_ptr())
 
     def adam_clip():      # on copies of p, m, v: the training state is left alone
-        L.call("umpr_adam_step_clip", p, g.g, m, v, g.numel, 1e-6, 0.9, 0.999, 1e-8, 1e-3, 1, 1.0, state, stream_ptr())
+        L.call("umpr_adam_step_clip", p, g.g, m, v, g.numel, 1e-6, 0.9, 0.999, 1e-8, 1e-3, 1, 1.0, c.state, stream_ptr())
 
     def adam_plain():
         L.call("umpr_adam_step", p, g.g, m, v, g.numel, 1e-6, 0.9, 0.999, 1e-8, 1e-3, 1, 1.0, stream_ptr())

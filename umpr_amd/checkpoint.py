@@ -45,11 +45,10 @@ def load_checkpoint(path, model, opt=None, map_location="cpu"):
     if opt is not None and isinstance(ck, dict) and "optimizer" in ck:
         opt.check_state_dict(ck["optimizer"])       # e.g. moments of a trainable VGG for a frozen one: before anything is overwritten
     model.load_state_dict(sd)
-    if opt is not None:
-        if isinstance(ck, dict) and "optimizer" in ck:
-            opt.load_state_dict(ck["optimizer"])
-        else:
-            opt.reattach()  # parameters were copied into place: nothing to restore, keep fresh moments
+    # a bare state_dict: model.load_state_dict copied the parameters INTO the optimiser's arena views, so they stay attached -
+    # nothing to restore, the moments stay fresh
+    if opt is not None and isinstance(ck, dict) and "optimizer" in ck:
+        opt.load_state_dict(ck["optimizer"])
     meta = {k: ck[k] for k in _META if isinstance(ck, dict) and k in ck}
     for n, m in model.named_modules():
         if hasattr(m, "_calls") and n in meta.get("rng_calls", {}):

@@ -1100,7 +1100,7 @@ int umpr_profile_read(int family, double* total_ms, double* total_work, long* la
   return 0;
 }
 
-// ------------------------------------------------------------------------------------------------ Adam
+// ------------------------------------------------------------------------------------------------ BCE head, squared error
 int umpr_bce_head_fwd(const float* att, long ld, const float* w, const float* b, const float* target, int B, int K,
                       float* result, float* loss, float* ws, size_t ws_bytes, void* stream) {
   return umpr_bce_head_fwd_impl(att, ld, w, b, target, B, K, result, loss, ws, ws_bytes, S(stream));
@@ -1110,25 +1110,6 @@ int umpr_bce_head_bwd(const float* att, long ld, const float* w, const float* re
                       float* db, float* ws, size_t ws_bytes, void* stream) {
   return umpr_bce_head_bwd_impl(att, ld, w, result, target, d_result, d_loss, B, K, d_att, ld_d, dw, db, ws, ws_bytes,
                                 S(stream));
-}
-
-int umpr_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
-                   double eps, double weight_decay, long step, double grad_scale, void* stream) {
-  UMPR_REQUIRE(step >= 1 && n >= 0, "adam: bad step/n");
-  if (n == 0) return 0;
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const double step_size = lr / bc1;
-  const double inv_bc2_sqrt = 1.0 / sqrt(bc2);
-  return umpr_adam_impl(p, g, m, v, n, (float)grad_scale, (float)weight_decay, (float)beta1, (float)beta2, (float)eps,
-                        (float)step_size, (float)inv_bc2_sqrt, S(stream));
-}
-
-int umpr_adam_step_dev(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
-                       const float* hyper, void* stream) {
-  UMPR_REQUIRE(n >= 0 && hyper != nullptr, "adam_dev: bad arguments");
-  if (n == 0) return 0;
-  return umpr_adam_dev_impl(p, g, m, v, n, (float)beta1, (float)beta2, (float)eps, hyper, S(stream));
 }
 
 int umpr_sq_err_accumulate(const float* pred, const float* label, long n, double* acc, void* stream) {

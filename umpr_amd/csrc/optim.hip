@@ -1,7 +1,12 @@
-// Gradient clipping by global norm inside the optimiser step: one deterministic 2-norm over the flat gradient arenas and the two
-// Adam kernels of text_ops.hip with the clip coefficient read from device memory (umpr_amd/optim.py::FusedAdam(max_grad_norm=)).
-// And the sum of the gradient arenas over the micro-batches of one optimiser step (FusedAdam.accumulate, --accum_steps).
+// The optimiser's kernels on the flat arenas (umpr_amd/optim.py::FusedAdam).  The dense Adam update: ONE element function, ONE
+// kernel template <DEV, CLIP> and ONE launcher behind the four entry points umpr_adam_step[_dev][_clip] - per-step scalars by
+// value or from device memory (graph mode), without or with the clip coefficient read from device memory - so that the four
+// forms are bit-identical at coefficient 1 by construction.  Gradient clipping by global norm (FusedAdam(max_grad_norm=)): one
+// deterministic 2-norm over the gradient arenas.  And the sum of the gradient arenas over the micro-batches of one optimiser
+// step (FusedAdam.accumulate, --accum_steps).
 #include <math.h>
+
+#include <type_traits>
 
 #include "../../include/umpr_hip.h"
 #include "umpr_common.h"
@@ -92,39 +97,71 @@ __global__ void __launch_bounds__(GN_THREADS) grad_norm_finish_kernel(const doub
   else if (coef < 1.f) cnt[UMPR_CLIP_CLIPPED] += 1u;
 }
 
-// adam_kernel / adam_dev_kernel (text_ops.hip) with the gradient scale multiplied by the clip coefficient - ONE float product of
-// the two scalars, so that coef == 1 leaves the scale, and with it every bit of the update, as the unclipped kernels have it.  A
-// step whose gradient norm was not finite touches nothing.
-__global__ void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long n, float gscale0, float wd, float b1, float b2, float eps,
-                                 float step_size, float inv_bc2_sqrt, const float* __restrict__ state) {
-  if (state[UMPR_CLIP_FINITE] == 0.f) return;
-  const float gscale = gscale0 * state[UMPR_CLIP_COEF];
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float pi = p[i];
-    const float gi = g[i] * gscale + wd * pi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) * inv_bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
-  }
+// Adam with coupled L2 exactly as torch.optim.Adam applies it (main.py:22-25), for one element:
+//   g += wd*p; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// in floats:  gi = g*gscale + wd*p;  mi = b1*m + (1-b1)*gi;  vi = b2*v + (1-b2)*gi*gi;  denom = sqrtf(vi)*inv_bc2_sqrt + eps;
+//             p - step_size*(mi/denom)
+// Which product of `a*b + c*d` goes into the fma is the compiler's choice, and with the kernel's scalars in another argument
+// order it chose the other one: left to it, two instantiations of the template below differed in the last bit of gi.  So the
+// fusions are written out - the ones every build of this update has made so far (profiles/r14_a_adam_unify.txt) - and
+// contraction is off for the rest: the bits are the source's, whatever the instantiation.
+__device__ __forceinline__ void adam_update(float& p, float g, float& m, float& v, float gscale, float wd, float b1, float b2,
+                                            float eps, float step_size, float inv_bc2_sqrt) {
+#pragma clang fp contract(off)
+  const float pi = p;
+  const float gi = fmaf(wd, pi, g * gscale);
+  const float mi = fmaf(1.f - b1, gi, b1 * m);
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi; v = vi;
+  const float denom = fmaf(sqrtf(vi), inv_bc2_sqrt, eps);
+  p = fmaf(-step_size, mi / denom, pi);
 }
 
-__global__ void adam_dev_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                     float* __restrict__ v, long n, float b1, float b2, float eps,
-                                     const float* __restrict__ hyper, const float* __restrict__ state) {
-  if (state[UMPR_CLIP_FINITE] == 0.f) return;
-  const float gscale = hyper[0] * state[UMPR_CLIP_COEF], step_size = hyper[1], inv_bc2_sqrt = hyper[2], wd = hyper[3];
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const float pi = p[i];
-    const float gi = g[i] * gscale + wd * pi;
-    const float mi = b1 * m[i] + (1.f - b1) * gi;
-    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) * inv_bc2_sqrt + eps;
-    p[i] = pi - step_size * (mi / denom);
+// Where one launch gets its per-step scalars.  By value from the host, or (DEV) from device memory: hyper[0..3] = grad_scale,
+// step_size = lr / (1 - b1^t), 1 / sqrt(1 - b2^t), weight_decay as the caller will use them for the NEXT launch - what a captured
+// hipGraph of a training step launches: the node's kernel arguments are frozen at capture, the bias corrections change every
+// step.  CLIP adds the 8-float state umpr_grad_norm left; the forms without it carry an empty struct in the pointer's place.
+struct AdamScalars { float gscale, step_size, inv_bc2_sqrt, wd; };
+struct NoClipState {};
+
+// The one dense Adam kernel.  CLIP: a step whose gradient norm was not finite touches nothing, and the gradient scale is
+// multiplied by the clip coefficient - ONE float product of the two scalars, so that coef == 1 leaves the scale, and with it
+// every bit of the update, as the forms without CLIP have it.
+template <bool DEV, bool CLIP>
+__global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                            long n, float b1, float b2, float eps, std::conditional_t<DEV, const float*, AdamScalars> hyper,
+                            std::conditional_t<CLIP, const float*, NoClipState> state) {
+  if constexpr (CLIP) {
+    if (state[UMPR_CLIP_FINITE] == 0.f) return;
   }
+  AdamScalars a;
+  if constexpr (DEV) a = AdamScalars{hyper[0], hyper[1], hyper[2], hyper[3]};
+  else a = hyper;
+  if constexpr (CLIP) a.gscale = a.gscale * state[UMPR_CLIP_COEF];
+  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    adam_update(p[i], g[i], m[i], v[i], a.gscale, a.wd, b1, b2, eps, a.step_size, a.inv_bc2_sqrt);
+}
+
+// 256 threads, min(ceil(n / 256), 8192) workgroups (n >= 1 here), grid-stride loop: a second pass of the grid from 8192 * 256
+// elements on.  Elementwise, so the grid has no say in the result.
+template <bool DEV, bool CLIP, class Hyper, class State>
+int adam_launch(const char* what, float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps,
+                Hyper hyper, State state, void* stream) {
+  if (n == 0) return 0;
+  const long blocks = (n + 255) / 256;
+  adam_kernel<DEV, CLIP><<<(int)(blocks > 8192 ? 8192 : blocks), 256, 0, static_cast<hipStream_t>(stream)>>>(
+      p, g, m, v, n, (float)b1, (float)b2, (float)eps, hyper, state);
+  UMPR_LAUNCH_CHECK(what);
+  return 0;
+}
+
+// The host forms' bias corrections, in double as torch computes them, rounded to float once.
+AdamScalars adam_host_scalars(double lr, double beta1, double beta2, double weight_decay, long step, double grad_scale) {
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const double step_size = lr / bc1;
+  const double inv_bc2_sqrt = 1.0 / sqrt(bc2);
+  return AdamScalars{(float)grad_scale, (float)step_size, (float)inv_bc2_sqrt, (float)weight_decay};
 }
 
 // Gradient accumulation over micro-batches (FusedAdam.accumulate): acc = g (FIRST: acc is never read, so whatever it holds - the
@@ -185,11 +222,6 @@ __global__ void __launch_bounds__(GA_THREADS) grad_accumulate_kernel(const AccAr
   }
 }
 
-inline int adam_blocks(long n) {      // the grid of umpr_adam_impl / umpr_adam_dev_impl
-  long b = (n + 255) / 256;
-  return (int)(b > 8192 ? 8192 : (b < 1 ? 1 : b));
-}
-
 inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 
 }  // namespace
@@ -242,28 +274,30 @@ int umpr_grad_accumulate(float* const* acc, const float* const* grads, const lon
   return 0;
 }
 
+int umpr_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
+                   double eps, double weight_decay, long step, double grad_scale, void* stream) {
+  UMPR_REQUIRE(step >= 1 && n >= 0, "adam: bad step/n");
+  return adam_launch<false, false>("adam", p, g, m, v, n, beta1, beta2, eps,
+                                   adam_host_scalars(lr, beta1, beta2, weight_decay, step, grad_scale), NoClipState{}, stream);
+}
+
+int umpr_adam_step_dev(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
+                       const float* hyper, void* stream) {
+  UMPR_REQUIRE(n >= 0 && hyper != nullptr, "adam_dev: bad arguments");
+  return adam_launch<true, false>("adam_dev", p, g, m, v, n, beta1, beta2, eps, hyper, NoClipState{}, stream);
+}
+
 int umpr_adam_step_clip(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
                         double eps, double weight_decay, long step, double grad_scale, const float* state, void* stream) {
   UMPR_REQUIRE(step >= 1 && n >= 0 && state != nullptr, "adam_clip: bad step/n/state");
-  if (n == 0) return 0;
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const double step_size = lr / bc1;
-  const double inv_bc2_sqrt = 1.0 / sqrt(bc2);
-  adam_clip_kernel<<<adam_blocks(n), 256, 0, S(stream)>>>(p, g, m, v, n, (float)grad_scale, (float)weight_decay, (float)beta1,
-                                                          (float)beta2, (float)eps, (float)step_size, (float)inv_bc2_sqrt, state);
-  UMPR_LAUNCH_CHECK("adam_clip");
-  return 0;
+  return adam_launch<false, true>("adam_clip", p, g, m, v, n, beta1, beta2, eps,
+                                  adam_host_scalars(lr, beta1, beta2, weight_decay, step, grad_scale), state, stream);
 }
 
 int umpr_adam_step_dev_clip(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
                             const float* hyper, const float* state, void* stream) {
   UMPR_REQUIRE(n >= 0 && hyper != nullptr && state != nullptr, "adam_dev_clip: bad arguments");
-  if (n == 0) return 0;
-  adam_dev_clip_kernel<<<adam_blocks(n), 256, 0, S(stream)>>>(p, g, m, v, n, (float)beta1, (float)beta2, (float)eps, hyper,
-                                                              state);
-  UMPR_LAUNCH_CHECK("adam_dev_clip");
-  return 0;
+  return adam_launch<true, true>("adam_dev_clip", p, g, m, v, n, beta1, beta2, eps, hyper, state, stream);
 }
 
 }  // extern "C"

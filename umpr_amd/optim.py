@@ -3,8 +3,12 @@
 The reference builds ``torch.optim.Adam`` with two parameter groups - names without 'bias' get coupled L2
 (weight_decay = l2_regularization), names with 'bias' get none - and an ``ExponentialLR`` stepped once per epoch.
 Here every trainable parameter of a group is re-pointed into ONE contiguous fp32 arena (same for its gradient and the
-two Adam moments), so an optimiser step is one ``umpr_adam_step`` launch per group, ``zero_grad`` is one memset, and
+two Adam moments), so an optimiser step is one dense Adam launch per group, ``zero_grad`` is one memset, and
 the data-parallel gradient exchange is a handful of large RCCL all-reduces on the arena instead of one per tensor.
+
+``FusedAdam.step`` is the one step path: gradient source (gradient or accumulation arenas), the clip norm if clipping is on,
+the per-group ranges, the sparse rows.  Every dense launch goes through ``FusedAdam._adam``, which picks one of the library's
+four entry points - ``umpr_adam_step[_dev][_clip]``, one kernel template in csrc/optim.hip - from graph mode and clipping.
 """
 from __future__ import annotations
 
@@ -12,6 +16,7 @@ import ctypes
 import math
 import os
 import weakref
+from typing import Any, NamedTuple
 
 import torch
 
@@ -108,6 +113,33 @@ class _Group:
                 self.zero_ranges.append([lo, lo + _pad(k)])
 
 
+class _Sparse(NamedTuple):
+    """A table updated row-wise: its parameter name, the parameter, dense moments [vocab][E]."""
+    name: str
+    table: Any
+    m: Any
+    v: Any
+
+
+class _Clip(NamedTuple):
+    """Device state of the clipping path and the two host tables umpr_grad_norm reads (n_arenas dense arenas in them)."""
+    state: Any
+    ws: Any
+    ws_bytes: int
+    ptrs: Any
+    counts: Any
+    n_arenas: int
+
+
+class _Accum(NamedTuple):
+    """One accumulation arena per group and the host tables of umpr_grad_accumulate over the n_arenas non-empty ones."""
+    arenas: list
+    acc_ptrs: Any
+    grad_ptrs: Any
+    counts: Any
+    n_arenas: int
+
+
 class FusedAdam:
     """Adam(betas=(0.9,0.999), eps=1e-8) with the reference's grouping; ``lr_decay`` per ``epoch_end()``.
 
@@ -136,22 +168,24 @@ class FusedAdam:
     ``pending`` back to 0.  No early classifier update while anything is pending; not with a sparse table (its rows differ per
     micro-batch) and not in graph mode.  An optimiser that never accumulates allocates and launches nothing for it."""
 
+    sparse = None       # _Sparse: a table updated row-wise (a model with sparse_embedding)
+    _hyper = None       # device float32 [groups][4] of enable_graph_mode: the per-step scalars of the device-scalar kernels
+
     def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None,
                  max_grad_norm=0.0):
         max_grad_norm = float(max_grad_norm)
         if not math.isfinite(max_grad_norm) or max_grad_norm < 0.0:
             raise ValueError(f"max_grad_norm must be finite and >= 0 (0 turns clipping off), got {max_grad_norm}")
         self.max_grad_norm = max_grad_norm
-        self._clip = None           # device state of the clipping path, made by the first clipped step
+        self._clip = None           # _Clip, made by the first clipped step
         self.pending = 0            # micro-batches folded into the accumulation arenas since the last step
-        self._acc = None            # (arena per group, pointer tables of umpr_grad_accumulate), made by the first accumulate()
+        self._acc = None            # _Accum, made by the first accumulate()
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
-        self.sparse = None          # (name, parameter, m, v) of a table updated row-wise
         if getattr(model, "sparse_embedding", False):
             table = model.embedding.weight
             (name,) = [n for n, p in named if p is table]
             named = [(n, p) for n, p in named if p is not table]
-            self.sparse = (name, table, torch.zeros_like(table), torch.zeros_like(table))
+            self.sparse = _Sparse(name, table, torch.zeros_like(table), torch.zeros_like(table))
         if order_key is None:
             # the VGG classifier's gradients are produced first in backward and are 89 % of all gradient bytes: put them
             # at the front of the arena so that one contiguous slice can be all-reduced while the conv backward runs
@@ -298,17 +332,15 @@ class FusedAdam:
         with torch.cuda.stream(self._early_stream):
             for h in handles:
                 h.wait()                                # orders this stream behind the collective, not the host
-            lib().call("umpr_adam_step", g.p[lo:hi], g.g[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.lr, self.betas[0],
-                       self.betas[1], self.eps, g.weight_decay, self.step_count + 1, scale, stream_ptr())
+            self._adam(0, lo, hi, g.g, self.step_count + 1, scale, None)
             ev = torch.cuda.Event()
             ev.record(self._early_stream)
         self._early_done = (lo, hi, ev)
 
     # ---- clipping by global norm (max_grad_norm > 0) -------------------------------------------------------------------------
     def _clip_buffers(self):
-        """(state, workspace, arena pointers, arena counts, number of arenas) of the clipping path; the arenas never move, so the
-        two host tables umpr_grad_norm reads are built once.  (A sparse table's row gradients take one more slot behind them,
-        which _sparse_arena refreshes per step.)"""
+        """The _Clip of the clipping path; the arenas never move, so the two host tables umpr_grad_norm reads are built once.
+        (A sparse table's row gradients take one more slot behind them, which _sparse_arena refreshes per step.)"""
         if self._clip is None:
             dev = self.groups[0].p.device
             arenas = self.grad_arenas()
@@ -318,13 +350,13 @@ class FusedAdam:
             state = torch.zeros(8, dtype=torch.float32, device=dev)
             ws_bytes = lib().size("umpr_grad_norm_ws_bytes")
             ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
-            self._clip = (state, ws, ws_bytes, ptrs, counts, len(arenas))
+            self._clip = _Clip(state, ws, ws_bytes, ptrs, counts, len(arenas))
         return self._clip
 
     @property
     def clip_state(self):
         """The 8-float device state umpr_grad_norm maintains (include/umpr_hip.h), or None while clipping is off."""
-        return self._clip_buffers()[0] if self.max_grad_norm > 0.0 else None
+        return self._clip_buffers().state if self.max_grad_norm > 0.0 else None
 
     def clip_stats(self):
         """{"norm", "coef", "clipped", "skipped", "seen"}: the last step's gradient norm (scaled, before clipping) and
@@ -332,34 +364,23 @@ class FusedAdam:
         SYNCHRONISES: call it where the loop logs, not per step."""
         if self.max_grad_norm <= 0.0:
             raise RuntimeError("clip_stats: clipping is off (FusedAdam(max_grad_norm=0))")
-        host = self._clip_buffers()[0].cpu()
+        host = self._clip_buffers().state.cpu()
         cnt = host.view(torch.int32)
         return {"norm": float(host[1]), "coef": float(host[0]), "clipped": int(cnt[5]), "skipped": int(cnt[6]),
                 "seen": int(cnt[4])}
 
-    def _step_clipped(self, grad_scale, acc=None):
-        state, ws, ws_bytes, ptrs, counts, n_arenas = self._clip_buffers()
-        hyper = getattr(self, "_hyper", None)
-        if acc is None:
-            n_arenas = self._sparse_arena(ptrs, counts, n_arenas)
-            for g in self.groups:                      # the norm reads every arena: all stale slices are zeroed first
-                self._zero_unwritten(g)
-        else:                                          # the norm of the accumulated gradient: the same counts, the other arenas
-            ptrs = self._acc[1]
+    def _grad_norm(self, grad_scale, accumulated):
+        """The one umpr_grad_norm call of a clipped step; returns the device state the Adam kernels then read."""
+        c = self._clip_buffers()
+        if accumulated:                                # the norm of the accumulated gradient: the same counts, the other arenas
+            ptrs, n_arenas = self._acc.acc_ptrs, c.n_arenas
+        else:
+            ptrs, n_arenas = c.ptrs, self._sparse_arena(c.ptrs, c.counts, c.n_arenas)
         # every group carries the same grad_scale: in graph mode the norm kernel reads the first group's from device memory
-        lib().call("umpr_grad_norm", ctypes.addressof(ptrs), ctypes.addressof(counts), n_arenas, self.max_grad_norm,
-                   float(grad_scale), hyper[0] if hyper is not None else None, ws, ws_bytes, state, stream_ptr())
-        for gi, g in enumerate(self.groups):
-            if not g.numel:
-                continue
-            gg = g.g if acc is None else acc[gi]
-            if hyper is not None:
-                lib().call("umpr_adam_step_dev_clip", g.p, gg, g.m, g.v, g.numel, self.betas[0], self.betas[1], self.eps,
-                           hyper[gi], state, stream_ptr())
-            else:
-                lib().call("umpr_adam_step_clip", g.p, gg, g.m, g.v, g.numel, self.lr, self.betas[0], self.betas[1], self.eps,
-                           g.weight_decay, self.step_count, grad_scale, state, stream_ptr())
-        self._step_sparse(grad_scale, state)
+        lib().call("umpr_grad_norm", ctypes.addressof(ptrs), ctypes.addressof(c.counts), n_arenas, self.max_grad_norm,
+                   float(grad_scale), self._hyper[0] if self._hyper is not None else None, c.ws, c.ws_bytes, c.state,
+                   stream_ptr())
+        return c.state
 
     # ---- accumulation over micro-batches ---------------------------------------------------------------------------------------
     def _zero_unwritten(self, g):
@@ -374,7 +395,7 @@ class FusedAdam:
         if self.sparse is not None:
             raise NotImplementedError("FusedAdam.accumulate: not with a sparse table (--sparse_embedding True): every micro-batch "
                                       "names other rows (accumulate with --sparse_embedding False)")
-        if getattr(self, "_hyper", None) is not None:
+        if self._hyper is not None:
             raise NotImplementedError("FusedAdam.accumulate: not in graph mode: a captured step is one batch, one update")
         if self.groups[0].p.device.type != "cuda":
             raise RuntimeError("FusedAdam.accumulate launches a HIP kernel: the model must be on a cuda device")
@@ -389,11 +410,11 @@ class FusedAdam:
             live = [g for g in self.groups if g.numel]
             arenas = [torch.empty_like(g.g) for g in self.groups]
             table = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
-            self._acc = (arenas, table([a for a in arenas if a.numel()]), table([g.g for g in live]),
-                         (ctypes.c_long * max(len(live), 1))(*[g.numel for g in live]), len(live))
-        _, acc_ptrs, grad_ptrs, counts, n_arenas = self._acc
-        lib().call("umpr_grad_accumulate", ctypes.addressof(acc_ptrs), ctypes.addressof(grad_ptrs), ctypes.addressof(counts),
-                   n_arenas, int(self.pending == 0), stream_ptr())
+            self._acc = _Accum(arenas, table([a for a in arenas if a.numel()]), table([g.g for g in live]),
+                               (ctypes.c_long * max(len(live), 1))(*[g.numel for g in live]), len(live))
+        a = self._acc
+        lib().call("umpr_grad_accumulate", ctypes.addressof(a.acc_ptrs), ctypes.addressof(a.grad_ptrs), ctypes.addressof(a.counts),
+                   a.n_arenas, int(self.pending == 0), stream_ptr())
         self.pending += 1
 
     # ---- the row-wise update of a sparse table ---------------------------------------------------------------------------------
@@ -408,8 +429,9 @@ class FusedAdam:
         rows = self._sparse_rows()
         if rows is None:
             return n_arenas
-        ptrs[n_arenas] = rows[1].data_ptr()
-        counts[n_arenas] = rows[2] * rows[1].shape[1]
+        _, row_grad, T = rows
+        ptrs[n_arenas] = row_grad.data_ptr()
+        counts[n_arenas] = T * row_grad.shape[1]
         return n_arenas + 1
 
     def _step_sparse(self, grad_scale, clip_state):
@@ -417,46 +439,55 @@ class FusedAdam:
         if rows is None:
             return
         row_id, row_grad, T = rows
-        _, p, m, v = self.sparse
+        p, m, v = self.sparse.table, self.sparse.m, self.sparse.v
         lib().call("umpr_sparse_adam_rows", p, m, v, p.shape[0], p.shape[1], row_id, row_grad, T, self.lr, self.betas[0],
                    self.betas[1], self.eps, self.step_count, float(grad_scale), clip_state, stream_ptr())
+
+    def _adam(self, gi, lo, hi, grads, step, grad_scale, clip_state):
+        """The one dense Adam launch: elements [lo, hi) of group `gi` from the arena `grads`, as step number `step`.  Graph mode
+        takes the per-step scalars from device memory (`step` and `grad_scale` are then in ``_hyper``), `clip_state` the clip
+        coefficient: the same kernel with two switches (csrc/optim.hip)."""
+        if hi <= lo:
+            return
+        g = self.groups[gi]
+        arenas = (g.p[lo:hi], grads[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo)
+        tail = (stream_ptr(),) if clip_state is None else (clip_state, stream_ptr())
+        if self._hyper is not None:
+            lib().call("umpr_adam_step_dev" if clip_state is None else "umpr_adam_step_dev_clip", *arenas, self.betas[0],
+                       self.betas[1], self.eps, self._hyper[gi], *tail)
+        else:
+            lib().call("umpr_adam_step" if clip_state is None else "umpr_adam_step_clip", *arenas, self.lr, self.betas[0],
+                       self.betas[1], self.eps, g.weight_decay, step, grad_scale, *tail)
 
     def step(self, grad_scale=1.0):
         if self.groups[0].p.device.type != "cuda":
             raise RuntimeError("FusedAdam.step launches a HIP kernel: the model must be on a cuda device")
         self.step_count += 1
-        acc = None
-        if self.pending > 0:
+        accumulated = self.pending > 0
+        if accumulated:
             # the step of a group of micro-batches: accumulate() has waited for and folded each of them, the last one included;
             # the kernels below read the accumulation arenas, and the mean over the group rides on the gradient scale
-            acc, grad_scale, self.pending = self._acc[0], grad_scale / self.pending, 0
+            grads, grad_scale, self.pending = self._acc.arenas, grad_scale / self.pending, 0
         else:
             wait_for_gradients(self.groups[0].p.device)    # in-place gradients written from a side stream (umpr_amd/streams.py)
+            grads = [g.g for g in self.groups]
+            for g in self.groups:                      # the norm reads every arena: all stale slices are zeroed before it
+                self._zero_unwritten(g)
         done, self._early_done, self._early = self._early_done, None, None
-        assert acc is None or done is None             # accumulate() refuses a backward that was stepped early
+        assert not (accumulated and done is not None)  # accumulate() refuses a backward that was stepped early
+        clip_state = None
         if self.max_grad_norm > 0.0:
             assert done is None                        # arm_early never armed
-            return self._step_clipped(grad_scale, acc)
+            clip_state = self._grad_norm(grad_scale, accumulated)
         for gi, g in enumerate(self.groups):
-            if acc is None:
-                self._zero_unwritten(g)
-            if not g.numel:
-                continue
-            gg = g.g if acc is None else acc[gi]
             ranges = [(0, g.numel)]
             if gi == 0 and done is not None:           # the classifier slice was updated during backward
                 lo, hi, ev = done
                 ranges = [(0, lo), (hi, g.numel)]
                 torch.cuda.current_stream(g.p.device).wait_event(ev)
             for lo, hi in ranges:
-                if hi > lo and getattr(self, "_hyper", None) is not None:
-                    lib().call("umpr_adam_step_dev", g.p[lo:hi], gg[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.betas[0],
-                               self.betas[1], self.eps, self._hyper[gi], stream_ptr())
-                elif hi > lo:
-                    lib().call("umpr_adam_step", g.p[lo:hi], gg[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo, self.lr,
-                               self.betas[0], self.betas[1], self.eps, g.weight_decay, self.step_count, grad_scale,
-                               stream_ptr())
-        self._step_sparse(grad_scale, None)
+                self._adam(gi, lo, hi, grads[gi], self.step_count, grad_scale, clip_state)
+        self._step_sparse(grad_scale, clip_state)
 
     def epoch_end(self):
         """ExponentialLR.step() (main.py:54)."""
@@ -471,16 +502,15 @@ class FusedAdam:
                 st["m"][n] = g.m[off:off + k].detach().cpu().clone()
                 st["v"][n] = g.v[off:off + k].detach().cpu().clone()
         if self.sparse is not None:
-            name, _, m, v = self.sparse
-            st["m"][name], st["v"][name] = m.detach().cpu().reshape(-1).clone(), v.detach().cpu().reshape(-1).clone()
+            s = self.sparse
+            st["m"][s.name], st["v"][s.name] = s.m.detach().cpu().reshape(-1).clone(), s.v.detach().cpu().reshape(-1).clone()
             st["sparse_embedding"] = True
         return st
 
     def _moment_sizes(self):
         want = {n: g.offsets[n][1] for g in self.groups for n in g.names}
-        sparse = getattr(self, "sparse", None)
-        if sparse is not None:
-            want[sparse[0]] = sparse[1].numel()
+        if self.sparse is not None:
+            want[self.sparse.name] = self.sparse.table.numel()
         return want
 
     def check_state_dict(self, st):
@@ -488,7 +518,7 @@ class FusedAdam:
         written with the VGG (or its conv base, --freeze_conv) frozen resumed with it trainable, or the other way round, does not; nor does one written under the other
         --train_embedding setting.  Nor does one written under the other --sparse_embedding setting: the table's moments have the
         same names and sizes there, but not the same meaning (lazily kept per row, no L2 in them)."""
-        was, now = bool(st.get("sparse_embedding", False)), getattr(self, "sparse", None) is not None
+        was, now = bool(st.get("sparse_embedding", False)), self.sparse is not None
         if was != now:
             raise ValueError("optimizer state does not match this run: the checkpoint was written with --sparse_embedding "
                              f"{was}, this run has --sparse_embedding {now}: pass the same --sparse_embedding")
@@ -528,13 +558,9 @@ class FusedAdam:
                 g.m[off:off + k].copy_(st["m"][n])
                 g.v[off:off + k].copy_(st["v"][n])
         if self.sparse is not None:
-            name, _, m, v = self.sparse
-            m.copy_(st["m"][name].view_as(m))
-            v.copy_(st["v"][name].view_as(v))
-
-    def reattach(self):
-        """No-op hook: ``model.load_state_dict`` copies INTO the arena views, so parameters stay attached."""
-        return None
+            s = self.sparse
+            s.m.copy_(st["m"][s.name].view_as(s.m))
+            s.v.copy_(st["v"][s.name].view_as(s.v))
 
     def grad_arenas(self):
         return [g.g for g in self.groups if g.numel]
@@ -542,7 +568,7 @@ class FusedAdam:
     def accum_arenas(self):
         """The accumulation arenas, one per entry of grad_arenas(), or None before the first accumulate().  After a step they
         still hold the sum that step used."""
-        return None if self._acc is None else [a for a in self._acc[0] if a.numel()]
+        return None if self._acc is None else [a for a in self._acc.arenas if a.numel()]
 
     def early_bucket(self):
         """(arena, lo, hi, parameters) of the classifier-weight slice of the weight arena, or None.  The slice is
