@@ -464,6 +464,22 @@ int umpr_photo_fetch_u8(const uint8_t* packed, size_t packed_bytes, const umpr_p
 int umpr_feature_fetch_f32(const float* fresh, int n_fresh, const int32_t* fresh_row, const int32_t* src_slot,
                            const int32_t* dst_slot, int n, int F, float* store, long n_slots, float* out, void* stream);
 
+/* ---- device-resident tokenised reviews (umpr_amd/reviews.py::ReviewStore) ------------------------------------------------------
+ * The text half of umpr_amd/data.py::batch_loader on the device.  `tokens` [T] holds every distinct sentence of a corpus once,
+ * sentence j at tokens[sent_off[j] .. sent_off[j+1]); per role (user, item, ui) sample n owns the sentences
+ * sid[ptr[n] .. ptr[n+1]); ratings [n_samples].  All of these are device memory.  `idx` is HOST memory (B sample indices), read
+ * and validated during the call and carried in the kernel arguments, 256 per launch: a batch of B <= 256 is one launch for all
+ * three roles and the labels.  ids_pair [2][B][S][L] (user half, then item half), ids_ui [B][S_ui][L_ui] (may be NULL with
+ * S_ui = L_ui = 0) and labels [B] are written in full, every element once: element [b][s][l] is the token if s is below the
+ * sample's sentence count and l below that sentence's length, `pad` otherwise; a count above S or a sentence longer than L is
+ * truncated.  A sample named twice gives two identical rows.  Refused without launching, the outputs untouched: a NULL tokens,
+ * sent_off, idx, ids_pair, labels or ratings, a NULL table of a role in use, B < 1, S or L < 1, L or L_ui > 256, S_ui / L_ui
+ * inconsistent with ids_ui, an index outside [0, n_samples).  No allocation or copy: capture-safe. */
+int umpr_review_collate(const int32_t* tokens, const int64_t* sent_off, long n_sent, const int64_t* ptr_u, const int32_t* sid_u,
+                        const int64_t* ptr_i, const int32_t* sid_i, const int64_t* ptr_ui, const int32_t* sid_ui,
+                        const float* ratings, long n_samples, const int32_t* idx, int B, int S, int L, int S_ui, int L_ui, long pad,
+                        int64_t* ids_pair, int64_t* ids_ui, float* labels, void* stream);
+
 /* ---- R-Net pre-training head (pretrain/pretrain_rnet.py:147-169): result = sigmoid(Linear(K -> 1)(att)),
  * loss = BCELoss(mean)(result, target) with torch's log clamp at -100.  att rows at att + b*ld (K = 256: [atte_u;atte_i]
  * as umpr_coattention_fwd leaves them).  ws: B floats.  Backward follows ATen's binary_cross_entropy_backward

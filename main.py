@@ -8,6 +8,8 @@
                                                                                   # for every photo kept in 1 GB of HBM
     python main.py --data_dir data/music --freeze_conv True --pool5_store_gb 8    # freeze the conv base, train the classifier on
                                                                                   # each photo's pool5 row kept in 8 GB of HBM
+    python main.py --data_dir data/music --review_net_only True --review_store True   # tokenised reviews kept in HBM: a batch
+                                                                                      # travels as indices, one kernel pads its ids
     python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
     python main.py --data_dir data/music --train_embedding True --sparse_embedding True   # ... updating only the rows a step names
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
@@ -138,12 +140,28 @@ def run_real(config, rank, world, log):
     store_name = 'Pool5 store' if config.pool5_store_gb > 0 else 'Feature store' if config.feature_store_gb > 0 else 'Photo store'
     known = lambda data: store and store.register(data.photo_paths())
     collate = _Collate(config.review_net_only, rank, world, store.index if store else None)
+    # --review_store True: each Dataset's tokenised reviews live on the device (umpr_amd/reviews.py::ReviewStore); the DataLoader
+    # runs over (index, photo paths) with the settings it would have, its workers do the photo half of the collate only, and the
+    # ids of a batch are written on the device from its indices.  Built for sharded batches, not run on more than one rank.
+    if config.review_store:
+        from umpr_amd.reviews import IndexView, PhotoCollate, ReviewStore, StoreLoader
+        collate = PhotoCollate(config.review_net_only, rank, world, store.index if store else None)
     workers = max(0, int(getattr(config, "loader_workers", 0)))
     # decode + resize + collate in worker processes, pinned staging buffers, batches prefetched ahead of the GPU; with
     # loader_workers = 0 everything runs on the training thread, as in the reference (main.py:70-73)
     dl = dict(collate_fn=collate, num_workers=workers, pin_memory=True)
     if workers:
         dl.update(prefetch_factor=2, persistent_workers=True)
+
+    def loader(data, name, **kw):
+        """The DataLoader of `data`, cut to this rank's chunks; with --review_store its text half comes from a ReviewStore"""
+        if not config.review_store:
+            return ShardedLoader(DataLoader(data, batch_size=config.batch_size, **kw, **dl), rank, world)
+        reviews = ReviewStore(data, config.device)
+        log(f'Review store ({name}): {reviews!r}')
+        return ShardedLoader(StoreLoader(DataLoader(IndexView(data), batch_size=config.batch_size, **kw, **dl), reviews, rank, world),
+                             rank, world)
+
     model = UMPR(config, w2v.embedding).to(config.device)
     os.makedirs(os.path.dirname(model_path) or '.', exist_ok=True)
     logger = None if rank else type('L', (), {'info': staticmethod(log)})
@@ -154,9 +172,8 @@ def run_real(config, rank, world, log):
         log(f'Training dataset contains {len(train_data)} samples.')
         known(train_data), known(valid_data)           # before the loaders exist: their workers copy the path table
         g = torch.Generator().manual_seed(0)  # same shuffle on every rank
-        train_dlr = ShardedLoader(DataLoader(train_data, batch_size=config.batch_size, shuffle=True, generator=g, **dl),
-                                  rank, world)
-        valid_dlr = ShardedLoader(DataLoader(valid_data, batch_size=config.batch_size, **dl), rank, world)
+        train_dlr = loader(train_data, 'train', shuffle=True, generator=g)
+        valid_dlr = loader(valid_data, 'valid')
         _, saved = training(train_dlr, valid_dlr, model, config, model_path, logger=logger, world=world, rank=rank)
         if store:
             log(f'{store_name} after training: {store.stats()}')
@@ -168,7 +185,7 @@ def run_real(config, rank, world, log):
             'interval): testing the model as it stands at the end of training')
     test_data = Dataset(os.path.join(d, 'test.csv'), photo_json, photo_path, w2v, config)
     known(test_data)
-    test_dlr = ShardedLoader(DataLoader(test_data, batch_size=config.batch_size, **dl), rank, world)
+    test_dlr = loader(test_data, 'test')
     log(f"Test end, test mse is {evaluate_mse(model, test_dlr):.6f}")
     if store:
         log(f'{store_name} after the test: {store.stats()}')
@@ -195,7 +212,7 @@ def main():
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
-                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1}
+                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False}
 
 
 def check_flags(config):
@@ -206,6 +223,8 @@ def check_flags(config):
         sys.exit(f"--train_embedding takes True or False, got {config.train_embedding!r}")
     if not isinstance(config.sparse_embedding, bool):
         sys.exit(f"--sparse_embedding takes True or False, got {config.sparse_embedding!r}")
+    if not isinstance(config.review_store, bool):
+        sys.exit(f"--review_store takes True or False, got {config.review_store!r}")
     if config.sparse_embedding and not config.train_embedding:
         sys.exit("--sparse_embedding needs --train_embedding True: it chooses how a trainable table is updated (the rows a step "
                  "names only, as torch.optim.SparseAdam would)")

@@ -237,6 +237,27 @@ def get_image(path, resize=(224, 224)):
         return np.zeros([3] + list(resize))
 
 
+def raw_photos(photo_paths, views_photos, photo_size=(224, 224), store=None):
+    """The photo half of batch_loader(resize_on_gpu=True): a photos.RawPhotos of `photo_paths` - per sample, per view, the photo
+    paths (Dataset.data[3]) - with `views_photos` = (views, photos per view), which an empty list cannot tell.  With `store=` a
+    photos.PhotoStore's index, photos the store already holds are not opened at all: they travel as an id."""
+    from .photos import RawPhotos, decode_for_gpu
+    paths = [p for views in photo_paths for view in views for p in view]
+    if store is not None:
+        if tuple(store.size) != tuple(photo_size):
+            raise ValueError(f"photo store of {store.size} photos, batch of {tuple(photo_size)}")
+        ids, hits = store.lookup(paths)
+        todo = [None if h else p for p, h in zip(paths, hits)]
+    else:
+        todo = paths
+    with ThreadPoolExecutor() as pool:
+        decoded = list(pool.map(lambda x: None if x is None else decode_for_gpu(x, photo_size), todo))
+    raw = RawPhotos.pack(decoded, (len(photo_paths),) + tuple(views_photos), photo_size)
+    if store is not None:
+        raw.ids, raw.hits, raw.store_key = torch.from_numpy(ids), torch.from_numpy(hits), store.key
+    return raw
+
+
 def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, shard=None, resize_on_gpu=False, store=None):
     """src/dataset.py:146-182.  `shard=(rank, world)` (data parallel, not in the reference): the review tensors are padded
     to the GLOBAL batch's common (max_count, max_len) exactly as the reference's single collate does before
@@ -258,20 +279,7 @@ def batch_loader(batch_list, ignore_photos=False, photo_size=(224, 224), pad=0, 
     ratings = [s[4] for s in mine]
     photos, raw = [], None
     if resize_on_gpu and not ignore_photos and batch_list:
-        from .photos import RawPhotos, decode_for_gpu
-        paths = [p for s in mine for view in s[3] for p in view]
-        if store is not None:
-            if tuple(store.size) != tuple(photo_size):
-                raise ValueError(f"photo store of {store.size} photos, batch of {tuple(photo_size)}")
-            ids, hits = store.lookup(paths)
-            todo = [None if h else p for p, h in zip(paths, hits)]
-        else:
-            todo = paths
-        with ThreadPoolExecutor() as pool:
-            decoded = list(pool.map(lambda x: None if x is None else decode_for_gpu(x, photo_size), todo))
-        raw = RawPhotos.pack(decoded, (len(mine), len(batch_list[0][3]), len(batch_list[0][3][0])), photo_size)
-        if store is not None:
-            raw.ids, raw.hits, raw.store_key = torch.from_numpy(ids), torch.from_numpy(hits), store.key
+        raw = raw_photos([s[3] for s in mine], (len(batch_list[0][3]), len(batch_list[0][3][0])), photo_size, store)
     elif not ignore_photos and mine:
         paths = [p for s in mine for view in s[3] for p in view]
         with ThreadPoolExecutor() as pool:
