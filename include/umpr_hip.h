@@ -537,6 +537,19 @@ int umpr_adam_step_dev_clip(float* p, const float* g, float* m, float* v, long n
  * synchronisation: capture-safe. */
 int umpr_grad_accumulate(float* const* acc, const float* const* grads, const long* counts, int n_arenas, int first, void* stream);
 
+/* ---- Exponential moving average of the parameters (torch.optim.swa_utils.AveragedModel with get_ema_multi_avg_fn(decay)) ----
+ * umpr_ema_update, first != 0: ema[i][:] = params[i][:] - ema is not read, so it needs no initialising pass, whatever it holds.
+ * first == 0: ema = fmaf(w, params - ema, ema) per element with w = (float)(1 - decay): the difference rounded to float, then one
+ * fused multiply-add - the bits of torch.lerp(ema, params, 1 - decay) on the CPU.  decay lies in the open interval (0.5, 1).
+ * umpr_arena_swap exchanges a[i][:] and b[i][:] bit for bit (NaN payloads, signed zeros, infinities); a[i] and b[i] must not
+ * overlap.  Tables, pointers, counts, alignment and the launch as for umpr_grad_accumulate: HOST arrays of n_arenas (<= 8) device
+ * pointers / element counts, any float-aligned pointers, any count >= 0, n_arenas == 0 or all counts 0 launches nothing; everything
+ * refused is refused before anything is written.  One launch each on a fixed grid; no allocation, no copy, no host
+ * synchronisation. */
+int umpr_ema_update(float* const* ema, const float* const* params, const long* counts, int n_arenas, double decay, int first,
+                    void* stream);
+int umpr_arena_swap(float* const* a, float* const* b, const long* counts, int n_arenas, void* stream);
+
 /* ---- evaluate_mse (src/evaluate.py:12-13, `mse_loss(pred, labels, reduction='sum')` accumulated over batches) -----
  * acc[0] += sum_i (pred[i] - label[i])^2, acc[1] += n; acc = two device doubles the caller zeroed once and reads back
  * once after the last batch (the reference's `.item()` per batch is a host sync per batch). */

@@ -4,6 +4,8 @@
     python main.py --data_dir synthetic --batch_size 64                       # single MI355X
     python main.py --data_dir synthetic --learning_rate 1e-3 --grad_clip 5.0  # clip the gradient to a global 2-norm of 5
     python main.py --data_dir synthetic --batch_size 32 --accum_steps 8       # one Adam step per 8 batches of 32: an effective 256
+    python main.py --data_dir synthetic --learning_rate 1e-3 --ema_decay 0.999    # validate, choose the checkpoint and test on an
+                                                                                  # exponential moving average of the weights
     python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
                                                                                   # for every photo kept in 1 GB of HBM
     python main.py --data_dir data/music --freeze_conv True --pool5_store_gb 8    # freeze the conv base, train the classifier on
@@ -97,6 +99,15 @@ def _agree(value, rank):
     return value
 
 
+def _averaged_test(config, opt, saved):
+    """The context the test phase runs in: with --ema_decay a run that wrote no checkpoint but took a step tests on the moving
+    average of the weights, swapped under the model (a checkpoint, when there is one, was loaded with weights="ema" instead)."""
+    import contextlib
+    if config.ema_decay > 0 and not config.test_only and not saved and opt is not None and opt.ema_ready:
+        return opt.swapped_ema()
+    return contextlib.nullcontext()
+
+
 def run_real(config, rank, world, log):
     """main.py:64-99 of the reference: Word2vec -> Dataset -> DataLoader(collate) -> training -> test."""
     from torch.utils.data import DataLoader
@@ -165,7 +176,7 @@ def run_real(config, rank, world, log):
     model = UMPR(config, w2v.embedding).to(config.device)
     os.makedirs(os.path.dirname(model_path) or '.', exist_ok=True)
     logger = None if rank else type('L', (), {'info': staticmethod(log)})
-    saved = False
+    saved, opt = False, None
     if not config.test_only:
         train_data = Dataset(os.path.join(d, 'train.csv'), photo_json, photo_path, w2v, config)
         valid_data = Dataset(os.path.join(d, 'valid.csv'), photo_json, photo_path, w2v, config)
@@ -174,19 +185,21 @@ def run_real(config, rank, world, log):
         g = torch.Generator().manual_seed(0)  # same shuffle on every rank
         train_dlr = loader(train_data, 'train', shuffle=True, generator=g)
         valid_dlr = loader(valid_data, 'valid')
-        _, saved = training(train_dlr, valid_dlr, model, config, model_path, logger=logger, world=world, rank=rank)
+        opt, saved = training(train_dlr, valid_dlr, model, config, model_path, logger=logger, world=world, rank=rank)
         if store:
             log(f'{store_name} after training: {store.stats()}')
     if config.test_only or saved:
-        load_checkpoint(model_path, model, map_location=config.device)
-        log(f'Testing the checkpoint {model_path}')
+        load_checkpoint(model_path, model, map_location=config.device, weights="ema" if config.ema_decay > 0 else "model")
+        log(f'Testing the checkpoint {model_path}' + (' (its moving average of the weights)' if config.ema_decay > 0 else ''))
     else:
         log('No checkpoint was written in this run (validation never improved at a multiple of the validation '
-            'interval): testing the model as it stands at the end of training')
+            'interval): testing the model as it stands at the end of training'
+            + (' (the moving average of its weights)' if config.ema_decay > 0 and opt.ema_ready else ''))
     test_data = Dataset(os.path.join(d, 'test.csv'), photo_json, photo_path, w2v, config)
     known(test_data)
     test_dlr = loader(test_data, 'test')
-    log(f"Test end, test mse is {evaluate_mse(model, test_dlr):.6f}")
+    with _averaged_test(config, opt, saved):
+        log(f"Test end, test mse is {evaluate_mse(model, test_dlr):.6f}")
     if store:
         log(f'{store_name} after the test: {store.stats()}')
 
@@ -212,7 +225,7 @@ def main():
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
-                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False}
+                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False, "ema_decay": 0.0}
 
 
 def check_flags(config):
@@ -233,6 +246,13 @@ def check_flags(config):
     if config.accum_steps > 1 and config.sparse_embedding:
         sys.exit("--accum_steps > 1 and --sparse_embedding True exclude each other: every micro-batch names other rows of the "
                  "table (accumulate with --sparse_embedding False)")
+    if isinstance(config.ema_decay, bool) or not isinstance(config.ema_decay, (int, float)):
+        sys.exit(f"--ema_decay takes a number, 0 (off) or a decay in (0.5, 1), got {config.ema_decay!r}")
+    if config.ema_decay != 0 and not 0.5 < config.ema_decay < 1:
+        sys.exit(f"--ema_decay takes 0 (off) or a decay in the open interval (0.5, 1), got {config.ema_decay!r}")
+    if config.ema_decay > 0 and config.sparse_embedding:
+        sys.exit("--ema_decay > 0 and --sparse_embedding True exclude each other: the sparse table lives outside the arenas the "
+                 "average is kept over (average with --sparse_embedding False)")
     if config.pool5_store_gb > 0 and config.feature_store_gb > 0:
         sys.exit("--pool5_store_gb and --feature_store_gb exclude each other: --feature_store_gb belongs to --freeze_vgg True, "
                  "--pool5_store_gb to --freeze_conv True")
@@ -276,10 +296,16 @@ def _main():
     valid_dlr = SyntheticLoader(max(1, per_rank // 4), config, config.synthetic_vocab, 5000 + 7919 * rank, config.device)
     model_path = config.model_path or './model/umpr_synthetic.pt'
     os.makedirs(os.path.dirname(model_path) or '.', exist_ok=True)
+    opt, saved = None, False
     if not config.test_only:
-        training(train_dlr, valid_dlr, model, config, model_path, logger=None if rank else type('L', (), {'info': staticmethod(log)}),
-                 world=world, rank=rank)
-    mse = evaluate_mse(model, valid_dlr)
+        opt, saved = training(train_dlr, valid_dlr, model, config, model_path,
+                              logger=None if rank else type('L', (), {'info': staticmethod(log)}), world=world, rank=rank)
+    if config.ema_decay > 0 and (saved or (config.test_only and os.path.exists(model_path))):
+        from umpr_amd.checkpoint import load_checkpoint
+        load_checkpoint(model_path, model, map_location=config.device, weights="ema")
+        log(f'Testing the moving average of the weights in {model_path}')
+    with _averaged_test(config, opt, saved):
+        mse = evaluate_mse(model, valid_dlr)
     log(f"Test end, test mse is {mse:.6f}")
 
 

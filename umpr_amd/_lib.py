@@ -120,6 +120,8 @@ SIGNATURES = {
     "umpr_adam_step_clip": ("ppppldddddld" "pp", "i"),
     "umpr_adam_step_dev_clip": ("pppplddd" "ppp", "i"),
     "umpr_grad_accumulate": ("pppiip", "i"),
+    "umpr_ema_update": ("pppidip", "i"),
+    "umpr_arena_swap": ("pppip", "i"),
     "umpr_debug_poison_lds": ("pp", "i"),
     "umpr_set_gemm_bf16": ("i", "i"),
     "umpr_set_conv_inference": ("i", "i"),

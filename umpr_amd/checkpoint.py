@@ -37,11 +37,25 @@ def save_checkpoint(path, model, opt=None, epoch=0, batch_counter=0, best_loss=N
     os.replace(tmp, path)
 
 
-def load_checkpoint(path, model, opt=None, map_location="cpu"):
+def load_checkpoint(path, model, opt=None, map_location="cpu", weights="model"):
     """Returns the metadata dict (epoch, batch_counter, best_loss).  Accepts a checkpoint of save_checkpoint or a bare
-    state_dict file (e.g. ``torch.save(reference_model.state_dict(), path)`` written on the reference side)."""
+    state_dict file (e.g. ``torch.save(reference_model.state_dict(), path)`` written on the reference side).
+    `weights="ema"` loads the state dict as `weights="model"` does, then copies each tensor of the moving average a run with
+    --ema_decay left in ``ck["optimizer"]["ema"]`` over the parameter of that name: the model to validate and test with."""
+    if weights not in ("model", "ema"):
+        raise ValueError(f"load_checkpoint: weights must be 'model' or 'ema', got {weights!r}")
     ck = torch.load(path, map_location=map_location, weights_only=True)
     sd = ck["model"] if isinstance(ck, dict) and "model" in ck and isinstance(ck["model"], dict) else ck
+    ema = None
+    if weights == "ema":                                # before anything is written
+        ema = ck["optimizer"].get("ema") if isinstance(ck, dict) and isinstance(ck.get("optimizer"), dict) else None
+        if not ema:
+            raise ValueError(f"{path} holds no moving average of the weights: it was not written by a run with --ema_decay "
+                             "(or before that run's first step); load it with weights='model' (--ema_decay 0)")
+        params = dict(model.named_parameters())
+        wrong = sorted(n for n, t in ema.items() if n not in params or params[n].numel() != t.numel())
+        if wrong:
+            raise ValueError(f"{path}: the moving average (--ema_decay) does not match the model's parameters: {wrong[:3]}")
     if opt is not None and isinstance(ck, dict) and "optimizer" in ck:
         opt.check_state_dict(ck["optimizer"])       # e.g. moments of a trainable VGG for a frozen one: before anything is overwritten
     model.load_state_dict(sd)
@@ -49,6 +63,10 @@ def load_checkpoint(path, model, opt=None, map_location="cpu"):
     # nothing to restore, the moments stay fresh
     if opt is not None and isinstance(ck, dict) and "optimizer" in ck:
         opt.load_state_dict(ck["optimizer"])
+    if ema is not None:
+        with torch.no_grad():
+            for n, t in ema.items():
+                params[n].copy_(t.view(params[n].shape))
     meta = {k: ck[k] for k in _META if isinstance(ck, dict) and k in ck}
     for n, m in model.named_modules():
         if hasattr(m, "_calls") and n in meta.get("rng_calls", {}):

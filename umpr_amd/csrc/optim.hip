@@ -3,7 +3,8 @@
 // value or from device memory (graph mode), without or with the clip coefficient read from device memory - so that the four
 // forms are bit-identical at coefficient 1 by construction.  Gradient clipping by global norm (FusedAdam(max_grad_norm=)): one
 // deterministic 2-norm over the gradient arenas.  And the sum of the gradient arenas over the micro-batches of one optimiser
-// step (FusedAdam.accumulate, --accum_steps).
+// step (FusedAdam.accumulate, --accum_steps).  And the exponential moving average of the parameter arenas (FusedAdam(ema_decay=),
+// --ema_decay) with the exchange of two sets of arenas that puts the average under the model for an evaluation.
 #include <math.h>
 
 #include <type_traits>
@@ -222,6 +223,108 @@ __global__ void __launch_bounds__(GA_THREADS) grad_accumulate_kernel(const AccAr
   }
 }
 
+// Exponential moving average of the parameters (FusedAdam(ema_decay=)): ema = p (FIRST: ema is never read, so it needs no
+// initialising pass, whatever it holds) or ema += w * (p - ema), w = 1 - decay, on the grid and with the access pattern of
+// grad_accumulate_kernel above (AccArenas: acc is the average, g the parameters).  8 or 12 bytes per element.  The subtraction
+// is rounded to float, then ONE fused multiply-add: what torch.lerp(ema, p, w) computes on the CPU for w < 0.5.  Written out
+// with contraction off, as adam_update is: the bits are the source's.
+__device__ __forceinline__ float ema1(float e, float p, float w) {
+#pragma clang fp contract(off)
+  const float d = p - e;
+  return fmaf(w, d, e);
+}
+template <bool FIRST>
+__device__ __forceinline__ float4 ema4(const float4 e, const float4 p, float w) {
+  return FIRST ? p : make_float4(ema1(e.x, p.x, w), ema1(e.y, p.y, w), ema1(e.z, p.z, w), ema1(e.w, p.w, w));
+}
+
+template <bool FIRST>
+__global__ void __launch_bounds__(GA_THREADS) ema_update_kernel(const AccArenas A, float w) {
+  const long gid = (long)blockIdx.x * GA_THREADS + threadIdx.x;
+  const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int a = 0; a < A.count; ++a) {
+    float* __restrict__ ema = A.acc[a];
+    const float* __restrict__ p = A.g[a];
+    const long n = A.n[a];
+    if (n <= 0) continue;
+    if ((((uintptr_t)ema ^ (uintptr_t)p) & 15u) != 0) {
+      for (long i = gid; i < n; i += GA_SWEEP) ema[i] = FIRST ? p[i] : ema1(ema[i], p[i], w);
+      continue;
+    }
+    long head = (long)(((16u - (unsigned)((uintptr_t)p & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    const long tail0 = head + 4 * n4;
+    float4* __restrict__ ema_4 = reinterpret_cast<float4*>(ema + head);
+    const float4* __restrict__ p4 = reinterpret_cast<const float4*>(p + head);
+    long i = gid;
+    for (; i + 3 * GA_SWEEP < n4; i += 4 * GA_SWEEP) {
+      const float4 q0 = p4[i], q1 = p4[i + GA_SWEEP], q2 = p4[i + 2 * GA_SWEEP], q3 = p4[i + 3 * GA_SWEEP];
+      const float4 e0 = FIRST ? none : ema_4[i], e1 = FIRST ? none : ema_4[i + GA_SWEEP];
+      const float4 e2 = FIRST ? none : ema_4[i + 2 * GA_SWEEP], e3 = FIRST ? none : ema_4[i + 3 * GA_SWEEP];
+      ema_4[i] = ema4<FIRST>(e0, q0, w);
+      ema_4[i + GA_SWEEP] = ema4<FIRST>(e1, q1, w);
+      ema_4[i + 2 * GA_SWEEP] = ema4<FIRST>(e2, q2, w);
+      ema_4[i + 3 * GA_SWEEP] = ema4<FIRST>(e3, q3, w);
+    }
+    for (; i < n4; i += GA_SWEEP) ema_4[i] = ema4<FIRST>(FIRST ? none : ema_4[i], p4[i], w);
+    if (gid < head) ema[gid] = FIRST ? p[gid] : ema1(ema[gid], p[gid], w);
+    if (gid < n - tail0) ema[tail0 + gid] = FIRST ? p[tail0 + gid] : ema1(ema[tail0 + gid], p[tail0 + gid], w);
+  }
+}
+
+// The exchange of two sets of arenas (FusedAdam.swapped_ema): a[k] <-> b[k], moves only, so every bit travels - NaN payloads,
+// signed zeros, infinities.  16 bytes per element, the same grid and access pattern; a[k] and b[k] do not overlap (refused by
+// the entry point), so every element is read and written by one thread only.
+struct SwapArenas {
+  float* a[GA_MAX_ARENAS];
+  float* b[GA_MAX_ARENAS];
+  long n[GA_MAX_ARENAS];
+  int count;
+};
+
+__global__ void __launch_bounds__(GA_THREADS) arena_swap_kernel(const SwapArenas A) {
+  const long gid = (long)blockIdx.x * GA_THREADS + threadIdx.x;
+  for (int k = 0; k < A.count; ++k) {
+    float* __restrict__ a = A.a[k];
+    float* __restrict__ b = A.b[k];
+    const long n = A.n[k];
+    if (n <= 0) continue;
+    if ((((uintptr_t)a ^ (uintptr_t)b) & 15u) != 0) {
+      for (long i = gid; i < n; i += GA_SWEEP) {
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+      }
+      continue;
+    }
+    long head = (long)(((16u - (unsigned)((uintptr_t)a & 15u)) & 15u) >> 2);
+    if (head > n) head = n;
+    const long n4 = (n - head) >> 2;
+    const long tail0 = head + 4 * n4;
+    float4* __restrict__ a4 = reinterpret_cast<float4*>(a + head);
+    float4* __restrict__ b4 = reinterpret_cast<float4*>(b + head);
+    long i = gid;
+    for (; i + 3 * GA_SWEEP < n4; i += 4 * GA_SWEEP) {
+      const float4 x0 = a4[i], x1 = a4[i + GA_SWEEP], x2 = a4[i + 2 * GA_SWEEP], x3 = a4[i + 3 * GA_SWEEP];
+      const float4 y0 = b4[i], y1 = b4[i + GA_SWEEP], y2 = b4[i + 2 * GA_SWEEP], y3 = b4[i + 3 * GA_SWEEP];
+      a4[i] = y0; a4[i + GA_SWEEP] = y1; a4[i + 2 * GA_SWEEP] = y2; a4[i + 3 * GA_SWEEP] = y3;
+      b4[i] = x0; b4[i + GA_SWEEP] = x1; b4[i + 2 * GA_SWEEP] = x2; b4[i + 3 * GA_SWEEP] = x3;
+    }
+    for (; i < n4; i += GA_SWEEP) {
+      const float4 x = a4[i], y = b4[i];
+      a4[i] = y; b4[i] = x;
+    }
+    if (gid < head) {
+      const float x = a[gid], y = b[gid];
+      a[gid] = y; b[gid] = x;
+    }
+    if (gid < n - tail0) {
+      const float x = a[tail0 + gid], y = b[tail0 + gid];
+      a[tail0 + gid] = y; b[tail0 + gid] = x;
+    }
+  }
+}
+
 inline hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 
 }  // namespace
@@ -271,6 +374,54 @@ int umpr_grad_accumulate(float* const* acc, const float* const* grads, const lon
   if (first) grad_accumulate_kernel<true><<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A);
   else grad_accumulate_kernel<false><<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A);
   UMPR_LAUNCH_CHECK("grad_accumulate");
+  return 0;
+}
+
+int umpr_ema_update(float* const* ema, const float* const* params, const long* counts, int n_arenas, double decay, int first,
+                    void* stream) {
+  UMPR_REQUIRE(n_arenas >= 0 && n_arenas <= GA_MAX_ARENAS, "ema_update: %d arenas outside 0..%d", n_arenas, GA_MAX_ARENAS);
+  UMPR_REQUIRE(n_arenas == 0 || (ema != nullptr && params != nullptr && counts != nullptr), "ema_update: null arena table");
+  UMPR_REQUIRE(decay > 0.5 && decay < 1.0, "ema_update: decay %g outside the open interval (0.5, 1)", decay);
+  AccArenas A;
+  A.count = n_arenas;
+  long total = 0;
+  for (int a = 0; a < GA_MAX_ARENAS; ++a) {
+    A.acc[a] = a < n_arenas ? ema[a] : nullptr;
+    A.g[a] = a < n_arenas ? params[a] : nullptr;
+    A.n[a] = a < n_arenas ? counts[a] : 0;
+    UMPR_REQUIRE(A.n[a] >= 0 && (A.n[a] == 0 || (A.acc[a] != nullptr && A.g[a] != nullptr)),
+                 "ema_update: arena %d: bad pointer / count", a);
+    UMPR_REQUIRE((((uintptr_t)A.acc[a] | (uintptr_t)A.g[a]) & 3u) == 0, "ema_update: arena %d is not aligned to a float", a);
+    total += A.n[a];
+  }
+  if (total == 0) return 0;
+  const float w = (float)(1.0 - decay);
+  if (first) ema_update_kernel<true><<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A, w);
+  else ema_update_kernel<false><<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A, w);
+  UMPR_LAUNCH_CHECK("ema_update");
+  return 0;
+}
+
+int umpr_arena_swap(float* const* a, float* const* b, const long* counts, int n_arenas, void* stream) {
+  UMPR_REQUIRE(n_arenas >= 0 && n_arenas <= GA_MAX_ARENAS, "arena_swap: %d arenas outside 0..%d", n_arenas, GA_MAX_ARENAS);
+  UMPR_REQUIRE(n_arenas == 0 || (a != nullptr && b != nullptr && counts != nullptr), "arena_swap: null arena table");
+  SwapArenas A;
+  A.count = n_arenas;
+  long total = 0;
+  for (int k = 0; k < GA_MAX_ARENAS; ++k) {
+    A.a[k] = k < n_arenas ? a[k] : nullptr;
+    A.b[k] = k < n_arenas ? b[k] : nullptr;
+    A.n[k] = k < n_arenas ? counts[k] : 0;
+    UMPR_REQUIRE(A.n[k] >= 0 && (A.n[k] == 0 || (A.a[k] != nullptr && A.b[k] != nullptr)),
+                 "arena_swap: arena %d: bad pointer / count", k);
+    UMPR_REQUIRE((((uintptr_t)A.a[k] | (uintptr_t)A.b[k]) & 3u) == 0, "arena_swap: arena %d is not aligned to a float", k);
+    const uintptr_t lo_a = (uintptr_t)A.a[k], lo_b = (uintptr_t)A.b[k], bytes = (uintptr_t)A.n[k] * sizeof(float);
+    UMPR_REQUIRE(A.n[k] == 0 || lo_a + bytes <= lo_b || lo_b + bytes <= lo_a, "arena_swap: arena %d: the two ranges overlap", k);
+    total += A.n[k];
+  }
+  if (total == 0) return 0;
+  arena_swap_kernel<<<GA_BLOCKS, GA_THREADS, 0, S(stream)>>>(A);
+  UMPR_LAUNCH_CHECK("arena_swap");
   return 0;
 }
 

@@ -33,13 +33,18 @@ def _align(n, a=256):
 class GraphedTrainStep:
     """Captures single-batch steps: one batch, one backward, one update per replay.  Gradient accumulation (FusedAdam.accumulate,
     --accum_steps) is not captured - FusedAdam refuses accumulate() once this class has put it into graph mode, and the
-    constructor refuses an optimiser that holds micro-batches waiting for their step."""
+    constructor refuses an optimiser that holds micro-batches waiting for their step.  A moving average of the weights
+    (FusedAdam(ema_decay=), --ema_decay) is not captured either: its first update is another kernel than the one a replay would
+    launch, so the constructor refuses an optimiser with ema_decay > 0."""
 
     def __init__(self, model: UMPR, opt, example_batch):
         assert model.review_net_only, "GraphedTrainStep captures the UMPR-R step (see the module docstring)"
         if getattr(opt, "pending", 0) > 0:
             raise NotImplementedError(f"GraphedTrainStep captures single-batch steps: this optimiser holds {opt.pending} "
                                       "accumulated micro-batches (FusedAdam.accumulate); take their step first")
+        if getattr(opt, "ema_decay", 0.0) > 0.0:
+            raise NotImplementedError("GraphedTrainStep does not capture a moving average of the weights (FusedAdam(ema_decay="
+                                      f"{opt.ema_decay})): its first update is another kernel than the captured one; use train_step")
         if model.embedding.weight.requires_grad:
             raise NotImplementedError("GraphedTrainStep does not capture a step with a trainable embedding table (train_embedding): "
                                       "its per-step sort of the token ids is not part of the captured graph; use train_step")

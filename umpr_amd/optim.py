@@ -12,6 +12,7 @@ four entry points - ``umpr_adam_step[_dev][_clip]``, one kernel template in csrc
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 import os
@@ -140,6 +141,15 @@ class _Accum(NamedTuple):
     n_arenas: int
 
 
+class _Ema(NamedTuple):
+    """One EMA arena per group and the host tables of umpr_ema_update / umpr_arena_swap over the n_arenas non-empty ones."""
+    arenas: list
+    ema_ptrs: Any
+    param_ptrs: Any
+    counts: Any
+    n_arenas: int
+
+
 class FusedAdam:
     """Adam(betas=(0.9,0.999), eps=1e-8) with the reference's grouping; ``lr_decay`` per ``epoch_end()``.
 
@@ -166,13 +176,30 @@ class FusedAdam:
     ``pending``.  The next ``step(grad_scale)`` then reads the accumulation arenas in place of the gradient arenas with the scale
     ``grad_scale / pending`` - the mean over the micro-batches, which the norm of a clipped step sees as well - and sets
     ``pending`` back to 0.  No early classifier update while anything is pending; not with a sparse table (its rows differ per
-    micro-batch) and not in graph mode.  An optimiser that never accumulates allocates and launches nothing for it."""
+    micro-batch) and not in graph mode.  An optimiser that never accumulates allocates and launches nothing for it.
+
+    ``ema_decay`` = d in (0.5, 1) keeps an exponential moving average of the trainable parameters beside the step, as
+    ``torch.optim.swa_utils.AveragedModel(model, multi_avg_fn=get_ema_multi_avg_fn(d))`` with ``update_parameters`` behind every
+    ``optimizer.step()`` does: one more arena per group (allocated by the first ``step()``), and every ``step()`` ends with ONE
+    ``umpr_ema_update`` over all groups on the calling stream, behind the last Adam launch and behind the wait for the early
+    classifier update.  The first update copies the parameters, every later one is ``ema = fmaf(1 - d, p - ema, ema)`` - the bits
+    of ``torch.lerp(ema, p, 1 - d)`` on the CPU.  It counts optimiser steps, so a group of accumulated micro-batches is one
+    update; a step that clipping skips still updates (the average moves towards the parameters that stayed) and no device flag
+    is read.  ``ema_tensors()`` shows the average per parameter name, ``swapped_ema()`` puts it under the model for an
+    evaluation, ``state_dict()`` carries it as "ema" / "ema_decay".  Not with a sparse table (it lives outside the arenas, and
+    averaging it would touch every row each step) and not in graph mode (the first update is another kernel than the captured
+    one).  Data parallel needs nothing: every rank holds the same parameters and computes the same bits - built, not run on
+    more than one rank.  0 (the default) is off: nothing is allocated, launched or stored for it."""
 
     sparse = None       # _Sparse: a table updated row-wise (a model with sparse_embedding)
     _hyper = None       # device float32 [groups][4] of enable_graph_mode: the per-step scalars of the device-scalar kernels
+    ema_decay = 0.0     # the moving average of the parameters is off
+    ema_ready = False   # True from the first update of the average on
+    _ema = None         # _Ema, made by the first step() with ema_decay > 0
+    _swapped = False    # inside swapped_ema(): the parameters hold the average, the EMA arenas the raw weights
 
     def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None,
-                 max_grad_norm=0.0):
+                 max_grad_norm=0.0, ema_decay=0.0):
         max_grad_norm = float(max_grad_norm)
         if not math.isfinite(max_grad_norm) or max_grad_norm < 0.0:
             raise ValueError(f"max_grad_norm must be finite and >= 0 (0 turns clipping off), got {max_grad_norm}")
@@ -180,6 +207,14 @@ class FusedAdam:
         self._clip = None           # _Clip, made by the first clipped step
         self.pending = 0            # micro-batches folded into the accumulation arenas since the last step
         self._acc = None            # _Accum, made by the first accumulate()
+        ema_decay = float(ema_decay)
+        if ema_decay != 0.0 and not 0.5 < ema_decay < 1.0:
+            raise ValueError(f"ema_decay must be 0 (off) or lie in the open interval (0.5, 1), got {ema_decay}")
+        if ema_decay > 0.0 and getattr(model, "sparse_embedding", False):
+            raise NotImplementedError("FusedAdam(ema_decay=): not with a sparse table (--sparse_embedding True): the table lives "
+                                      "outside the arenas, and averaging it would touch every row each step (average with "
+                                      "--sparse_embedding False)")
+        self.ema_decay = ema_decay
         named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
         if getattr(model, "sparse_embedding", False):
             table = model.embedding.weight
@@ -241,6 +276,9 @@ class FusedAdam:
         replayed) to refresh the scalars for the step about to be taken.  The update is bit-identical to the plain form.
         `hyper`: a device float32 [groups][4] view the CALLER keeps fresh from hyper_rows() (umpr_amd/graphs.py carries the scalars
         inside its one upload per step); prepare_step() is then not used."""
+        if self.ema_decay > 0.0:
+            raise NotImplementedError("FusedAdam.enable_graph_mode: not with ema_decay > 0: the first update of the average is "
+                                      "another kernel than the one a captured step would replay")
         dev = self.groups[0].p.device
         if hyper is not None:
             assert hyper.shape == (len(self.groups), 4) and hyper.dtype == torch.float32 and hyper.device == dev
@@ -287,6 +325,7 @@ class FusedAdam:
         UMPR_EARLY_ADAM=0 turns it off.  Worth 0.3-0.5 ms per step behind the all-reduce in the RCCL rehearsal (43.16 vs
         43.49 ms fp32, 16.06 vs 16.51 ms bf16); on a single GPU 0.1-0.3 ms in bf16 (9.56 vs 9.71 ms) and nothing in fp32.  Its stream is one more next to main / text / weight-gradient / RCCL:
         umpr_amd/__init__.py sets GPU_MAX_HW_QUEUES, the number of hardware queues they share."""
+        self._not_swapped("arm_early")
         if _EARLY_ADAM == "0" or self.max_grad_norm > 0.0:   # clipping: the coefficient needs every gradient first
             return
         if not self._has_classifier:                         # frozen VGG: there is no slice to update early
@@ -397,6 +436,7 @@ class FusedAdam:
                                       "names other rows (accumulate with --sparse_embedding False)")
         if self._hyper is not None:
             raise NotImplementedError("FusedAdam.accumulate: not in graph mode: a captured step is one batch, one update")
+        self._not_swapped("accumulate")
         if self.groups[0].p.device.type != "cuda":
             raise RuntimeError("FusedAdam.accumulate launches a HIP kernel: the model must be on a cuda device")
         if self._early_done is not None:
@@ -462,6 +502,7 @@ class FusedAdam:
     def step(self, grad_scale=1.0):
         if self.groups[0].p.device.type != "cuda":
             raise RuntimeError("FusedAdam.step launches a HIP kernel: the model must be on a cuda device")
+        self._not_swapped("step")
         self.step_count += 1
         accumulated = self.pending > 0
         if accumulated:
@@ -488,6 +529,75 @@ class FusedAdam:
             for lo, hi in ranges:
                 self._adam(gi, lo, hi, grads[gi], self.step_count, grad_scale, clip_state)
         self._step_sparse(grad_scale, clip_state)
+        if self.ema_decay > 0.0:
+            self._ema_update()
+
+    # ---- the exponential moving average of the parameters (ema_decay > 0) ------------------------------------------------------
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"FusedAdam.{what}: inside swapped_ema() the parameters hold the averaged weights; leave the "
+                               "context first")
+
+    def _ema_buffers(self):
+        """The _Ema: one more copy of the trainable parameters.  The arenas never move, so the host tables are built once."""
+        if self._ema is None:
+            live = [g for g in self.groups if g.numel]
+            arenas = [torch.empty_like(g.p) for g in self.groups]
+            table = lambda ts: (ctypes.c_void_p * max(len(ts), 1))(*[t.data_ptr() for t in ts])
+            self._ema = _Ema(arenas, table([a for a in arenas if a.numel()]), table([g.p for g in live]),
+                             (ctypes.c_long * max(len(live), 1))(*[g.numel for g in live]), len(live))
+        return self._ema
+
+    def _ema_update(self):
+        """behind the step's last launch on the calling stream (which has waited for the early classifier update's event)"""
+        e = self._ema_buffers()
+        lib().call("umpr_ema_update", ctypes.addressof(e.ema_ptrs), ctypes.addressof(e.param_ptrs), ctypes.addressof(e.counts),
+                   e.n_arenas, self.ema_decay, int(not self.ema_ready), stream_ptr())
+        self.ema_ready = True
+
+    def ema_bytes(self):
+        """what the EMA arenas take (or will take, before the first step): one more copy of the trainable parameters"""
+        return 4 * sum(g.numel for g in self.groups) if self.ema_decay > 0.0 else 0
+
+    def ema_tensors(self):
+        """{parameter name: view of the EMA arena in the parameter's shape}.  Inside swapped_ema() the views show the raw
+        weights."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("ema_tensors: the moving average is off (FusedAdam(ema_decay=0))")
+        if not self.ema_ready:
+            raise RuntimeError("ema_tensors: no average yet: the first step() makes it")
+        out = {}
+        for g, arena in zip(self.groups, self._ema.arenas):
+            for n, p in zip(g.names, g.params):
+                off, k = g.offsets[n]
+                out[n] = arena[off:off + k].view(p.shape)
+        return out
+
+    def _swap(self):
+        e = self._ema
+        lib().call("umpr_arena_swap", ctypes.addressof(e.param_ptrs), ctypes.addressof(e.ema_ptrs), ctypes.addressof(e.counts),
+                   e.n_arenas, stream_ptr())
+
+    @contextlib.contextmanager
+    def swapped_ema(self):
+        """Inside the context the model's parameters hold the averaged weights and the EMA arenas the raw ones: one
+        umpr_arena_swap launch over all groups on entry and one on exit (also when the body raises), on the calling stream.
+        step(), accumulate() and arm_early() raise while it is open.  The exchange is made by a library kernel, so no parameter's
+        ``_version`` moves.  That is right: the feature / pool5 stores key on VGG weights that are frozen, hence outside the
+        arenas, hence not swapped; nothing else caches a function of a trainable parameter across steps (the Adam kernels do
+        not move ``_version`` either)."""
+        if self.ema_decay <= 0.0 or not self.ema_ready:
+            raise RuntimeError("swapped_ema: no average to swap in: " + ("the moving average is off (FusedAdam(ema_decay=0))"
+                                                                         if self.ema_decay <= 0.0 else "the first step() makes it"))
+        if self._swapped:
+            raise RuntimeError("swapped_ema: already inside swapped_ema()")
+        self._swap()
+        self._swapped = True
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._swapped = False
 
     def epoch_end(self):
         """ExponentialLR.step() (main.py:54)."""
@@ -495,6 +605,7 @@ class FusedAdam:
 
     def state_dict(self):
         """Adam moments per parameter NAME (independent of the arena order), step count and current learning rate."""
+        self._not_swapped("state_dict")
         st = {"step": self.step_count, "lr": float(self.lr), "base_lr": float(self.base_lr), "m": {}, "v": {}}
         for g in self.groups:
             for n in g.names:
@@ -505,6 +616,10 @@ class FusedAdam:
             s = self.sparse
             st["m"][s.name], st["v"][s.name] = s.m.detach().cpu().reshape(-1).clone(), s.v.detach().cpu().reshape(-1).clone()
             st["sparse_embedding"] = True
+        if self.ema_decay > 0.0:
+            # the average per parameter name, like the moments; empty before the first update
+            st["ema"] = {n: t.detach().cpu().reshape(-1).clone() for n, t in self.ema_tensors().items()} if self.ema_ready else {}
+            st["ema_decay"] = float(self.ema_decay)
         return st
 
     def _moment_sizes(self):
@@ -517,12 +632,20 @@ class FusedAdam:
         """Raises unless `st` holds Adam moments for exactly the parameters this optimiser trains, in their sizes - a checkpoint
         written with the VGG (or its conv base, --freeze_conv) frozen resumed with it trainable, or the other way round, does not; nor does one written under the other
         --train_embedding setting.  Nor does one written under the other --sparse_embedding setting: the table's moments have the
-        same names and sizes there, but not the same meaning (lazily kept per row, no L2 in them)."""
+        same names and sizes there, but not the same meaning (lazily kept per row, no L2 in them).  Nor does one written with a
+        moving average (--ema_decay) for a run without one, or the other way round; another decay value is accepted, and the
+        run's own value holds."""
         was, now = bool(st.get("sparse_embedding", False)), self.sparse is not None
         if was != now:
             raise ValueError("optimizer state does not match this run: the checkpoint was written with --sparse_embedding "
                              f"{was}, this run has --sparse_embedding {now}: pass the same --sparse_embedding")
-        for key in ("m", "v"):
+        was, now = "ema" in st, self.ema_decay > 0.0
+        if was != now:
+            raise ValueError("optimizer state does not match this run: the checkpoint was written with --ema_decay "
+                             f"{float(st.get('ema_decay', 0.0))}, this run has --ema_decay {self.ema_decay}: pass "
+                             + (f"--ema_decay {float(st.get('ema_decay', 0.0))} (or another value in (0.5, 1))" if was
+                                else "--ema_decay 0"))
+        for key in ("m", "v") + (("ema",) if st.get("ema") else ()):
             have = {n: int(t.numel()) for n, t in st[key].items()}
             want = self._moment_sizes()
             if have != want:
@@ -561,6 +684,14 @@ class FusedAdam:
             s = self.sparse
             s.m.copy_(st["m"][s.name].view_as(s.m))
             s.v.copy_(st["v"][s.name].view_as(s.v))
+        if self.ema_decay > 0.0:
+            self.ema_ready = bool(st["ema"])
+            if self.ema_ready:
+                for g, arena in zip(self.groups, self._ema_buffers().arenas):
+                    arena.zero_()                       # the padding between parameters, as in the parameter arenas
+                    for n in g.names:
+                        off, k = g.offsets[n]
+                        arena[off:off + k].copy_(st["ema"][n])
 
     def grad_arenas(self):
         return [g.g for g in self.groups if g.numel]

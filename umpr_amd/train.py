@@ -132,7 +132,12 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     of their gradients (train_step(update=False) k - 1 times, then update=True), and one more for the k' < k batches an epoch may
     end with.  `batch_counter` - validation interval, the 50000 limit, the checkpoint - then counts optimiser steps; checkpoints
     are written right behind a step only, with `batch_in_epoch` the loader batches consumed, so a resumed run forms the same
-    groups.  Loss sums and log lines stay per loader batch."""
+    groups.  Loss sums and log lines stay per loader batch.  `config.ema_decay` = d > 0 keeps an exponential moving average of
+    the weights beside the step (FusedAdam(ema_decay=)): every validation behind a step then runs on the averaged weights, inside
+    `opt.swapped_ema()`, and says so in its log line, so the checkpoint is chosen by the average's validation MSE.  The
+    checkpoint itself is written outside the swap: "model" keeps the raw weights (an exact resume, the same state_dict
+    interchange), the average travels in ck["optimizer"]["ema"] (load_checkpoint(weights="ema")).  The initial validation is on
+    the raw weights: no average exists yet."""
     accum = int(getattr(config, "accum_steps", 1))
     if accum > 1 and parallel.active():
         raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
@@ -140,8 +145,13 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     valid_mse = evaluate_mse(model, valid_dataloader)
     log(f'Initial validation mse is {valid_mse:.6f}')
     start = time.perf_counter()
+    ema_decay = float(getattr(config, "ema_decay", 0.0))
+    averaged = {"ema_decay": ema_decay} if ema_decay > 0.0 else {}      # (off: the call is the one it was)
     opt = FusedAdam(model, config.learning_rate, config.l2_regularization, config.lr_decay,
-                    max_grad_norm=float(getattr(config, "grad_clip", 0.0)))
+                    max_grad_norm=float(getattr(config, "grad_clip", 0.0)), **averaged)
+    if averaged:
+        log(f'Moving average of the weights: decay {ema_decay}, {opt.ema_bytes() / 1e6:.0f} MB more; validation and the '
+            f'checkpoint choice run on the averaged weights')
     reducer = parallel.GradReducer(opt) if parallel.active() else None
     best_loss, batch_counter, first_epoch, skip, saved = 100, 0, 0, 0, False
     valid_every = int(getattr(config, "valid_every", 500))   # the reference hard-codes 500 (main.py:43)
@@ -161,9 +171,13 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
         nonlocal batch_counter, best_loss, saved
         batch_counter += 1
         if batch_counter % valid_every == 0:
-            valid_mse = evaluate_mse(model, valid_dataloader)
+            if averaged:
+                with opt.swapped_ema():
+                    valid_mse = evaluate_mse(model, valid_dataloader)
+            else:
+                valid_mse = evaluate_mse(model, valid_dataloader)
             log(f'Epoch {epoch:2d}; batch {batch_counter:5d}; train loss {total_loss / max(total_samples, 1):.6f}; '
-                f'valid mse {valid_mse:.6f}' + clip_note(opt))
+                f'valid mse{" (ema)" if averaged else ""} {valid_mse:.6f}' + clip_note(opt))
             if best_loss > valid_mse:        # valid_mse is all-reduced: every rank takes the same branch
                 best_loss = valid_mse
                 if rank == 0:
