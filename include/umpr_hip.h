@@ -526,6 +526,25 @@ int umpr_adam_step_clip(float* p, const float* g, float* m, float* v, long n, do
 int umpr_adam_step_dev_clip(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double eps,
                             const float* hyper, const float* state, void* stream);
 
+/* ---- Per-segment learning-rate and decay multipliers, coupled L2 or AdamW's decoupled decay, in ONE launch ----------------
+ * The four forms above behind one entry point: hyper == NULL takes the scalars from lr .. grad_scale as umpr_adam_step does,
+ * otherwise from hyper[4] in device memory (lr, weight_decay, step and grad_scale are then ignored); clip_state NULL or the state
+ * of umpr_grad_norm as in the _clip forms.  seg_end / seg_lr_mult / seg_wd_mult are HOST arrays of n_segs (1..16) entries, copied
+ * into the kernel's arguments: elements [seg_end[k-1], seg_end[k]) of the launch (seg_end[-1] = 0) are updated with the step size
+ * step_size * seg_lr_mult[k] and
+ *   decoupled == 0: the coupled L2 weight_decay * seg_wd_mult[k] - one float product each, so that multipliers of exactly 1 give
+ *     the bits of the plain forms;
+ *   decoupled != 0: torch.optim.AdamW - p *= 1 - d first, d = (lr * weight_decay) * (seg_lr_mult[k] * seg_wd_mult[k]), then Adam
+ *     on grad_scale * g alone.  hyper[3] then holds lr * weight_decay (in fp32) in place of weight_decay.
+ * The ends ascend strictly, every one but the last is a multiple of 64 elements and the last equals n; multipliers are finite,
+ * seg_lr_mult > 0, seg_wd_mult >= 0.  Anything else is refused, with a message, before anything is launched.  n == 0 is a
+ * successful no-op.  A step that clip_state marks non-finite touches nothing, the decoupled shrink included.  No allocation, no
+ * copy, no host synchronisation: capture-safe. */
+int umpr_adam_step_groups(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, long step, double grad_scale, const float* hyper /*or NULL*/,
+                          const float* clip_state /*or NULL*/, const long* seg_end, const float* seg_lr_mult,
+                          const float* seg_wd_mult, int n_segs, int decoupled, void* stream);
+
 /* ---- Gradient accumulation: one optimiser step over several micro-batches ((loss / k).backward() k times, then step()) ----
  * first != 0: acc[i][:] = grads[i][:] - acc is not read, so it needs no zeroing, whatever it holds (the inf or NaN of a skipped
  * step included).  first == 0: acc[i][:] += grads[i][:], one IEEE fp32 add per element, so the chained sum over the micro-batches

@@ -6,6 +6,9 @@
     python main.py --data_dir synthetic --batch_size 32 --accum_steps 8       # one Adam step per 8 batches of 32: an effective 256
     python main.py --data_dir synthetic --learning_rate 1e-3 --ema_decay 0.999    # validate, choose the checkpoint and test on an
                                                                                   # exponential moving average of the weights
+    python main.py --data_dir data/music --learning_rate 1e-3 --lr_scale visual_net.vgg16.=1e-3 --decoupled_decay True \
+                   --warmup_steps 500                                         # fine-tune the VGG at 1e-6 while the rest trains at
+                                                                              # 1e-3, AdamW's decay, 500 steps of linear warm-up
     python main.py --data_dir data/music --freeze_vgg True --feature_store_gb 1   # VGG as a fixed feature extractor, its output
                                                                                   # for every photo kept in 1 GB of HBM
     python main.py --data_dir data/music --freeze_conv True --pool5_store_gb 8    # freeze the conv base, train the classifier on
@@ -31,6 +34,7 @@ import torch
 from umpr_amd import parallel
 from umpr_amd.config import Config
 from umpr_amd.model import UMPR
+from umpr_amd.optim import parse_scales
 from umpr_amd.synthetic import make_batch
 from umpr_amd.train import evaluate_mse, training
 
@@ -225,7 +229,8 @@ def main():
 EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_emb": 50, "vgg_weights": "", "resume": "",
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
-                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False, "ema_decay": 0.0}
+                 "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False, "ema_decay": 0.0,
+                 "lr_scale": "", "wd_scale": "", "decoupled_decay": False, "warmup_steps": 0}
 
 
 def check_flags(config):
@@ -253,6 +258,20 @@ def check_flags(config):
     if config.ema_decay > 0 and config.sparse_embedding:
         sys.exit("--ema_decay > 0 and --sparse_embedding True exclude each other: the sparse table lives outside the arenas the "
                  "average is kept over (average with --sparse_embedding False)")
+    for option in ("lr_scale", "wd_scale"):            # the syntax here; the prefixes are checked against the model's names
+        try:                                           # by the optimiser (FusedAdam raises ValueError naming the prefix)
+            scales = parse_scales(getattr(config, option), option)
+        except ValueError as e:
+            sys.exit(str(e))
+        bad = [p for p, x in scales.items() if not (x > 0 if option == "lr_scale" else x >= 0) or x == float("inf")]
+        if bad:
+            sys.exit(f"--{option}: the multiplier of the prefix {bad[0]!r} must be finite and "
+                     + ("> 0" if option == "lr_scale" else ">= 0") + f", got {scales[bad[0]]}")
+    if not isinstance(config.decoupled_decay, bool):
+        sys.exit(f"--decoupled_decay takes True or False, got {config.decoupled_decay!r}")
+    if isinstance(config.warmup_steps, bool) or not isinstance(config.warmup_steps, int) or config.warmup_steps < 0:
+        sys.exit(f"--warmup_steps takes a whole number >= 0 (optimiser steps of linear warm-up, 0: none), got "
+                 f"{config.warmup_steps!r}")
     if config.pool5_store_gb > 0 and config.feature_store_gb > 0:
         sys.exit("--pool5_store_gb and --feature_store_gb exclude each other: --feature_store_gb belongs to --freeze_vgg True, "
                  "--pool5_store_gb to --freeze_conv True")

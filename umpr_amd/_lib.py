@@ -119,6 +119,7 @@ SIGNATURES = {
     "umpr_grad_norm": ("ppidfppzpp", "i"),
     "umpr_adam_step_clip": ("ppppldddddld" "pp", "i"),
     "umpr_adam_step_dev_clip": ("pppplddd" "ppp", "i"),
+    "umpr_adam_step_groups": ("ppppldddddld" "pp" "ppp" "ii" "p", "i"),
     "umpr_grad_accumulate": ("pppiip", "i"),
     "umpr_ema_update": ("pppidip", "i"),
     "umpr_arena_swap": ("pppip", "i"),

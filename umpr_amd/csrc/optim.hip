@@ -1,7 +1,9 @@
 // The optimiser's kernels on the flat arenas (umpr_amd/optim.py::FusedAdam).  The dense Adam update: ONE element function, ONE
 // kernel template <DEV, CLIP> and ONE launcher behind the four entry points umpr_adam_step[_dev][_clip] - per-step scalars by
 // value or from device memory (graph mode), without or with the clip coefficient read from device memory - so that the four
-// forms are bit-identical at coefficient 1 by construction.  Gradient clipping by global norm (FusedAdam(max_grad_norm=)): one
+// forms are bit-identical at coefficient 1 by construction.  The template's two further switches <SEG, DECOUPLED> - a table of up
+// to 16 segments with their own learning-rate and decay multipliers in one launch, and AdamW's decoupled decay - sit behind a
+// fifth entry point, umpr_adam_step_groups (FusedAdam(lr_scales=, wd_scales=, decoupled_decay=)).  Gradient clipping by global norm (FusedAdam(max_grad_norm=)): one
 // deterministic 2-norm over the gradient arenas.  And the sum of the gradient arenas over the micro-batches of one optimiser
 // step (FusedAdam.accumulate, --accum_steps).  And the exponential moving average of the parameter arenas (FusedAdam(ema_decay=),
 // --ema_decay) with the exchange of two sets of arenas that puts the average under the model for an evaluation.
@@ -118,20 +120,73 @@ __device__ __forceinline__ void adam_update(float& p, float g, float& m, float& 
   p = fmaf(-step_size, mi / denom, pi);
 }
 
+// AdamW's decoupled decay (FusedAdam(decoupled_decay=True), torch.optim.AdamW) for one element: the parameter shrinks first, the
+// gradient carries no decay term:
+//   p *= 1 - lr*wd; m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
+// in floats:  pi = p*keep, keep = 1 - decay, decay = lr*wd (one float per segment);  gi = g*gscale;  mi = b1*m + (1-b1)*gi;
+//             vi = b2*v + (1-b2)*gi*gi;  denom = sqrtf(vi)*inv_bc2_sqrt + eps;  pi - step_size*(mi/denom)
+// The same fusions as adam_update, written out, contraction off.
+__device__ __forceinline__ void adamw_update(float& p, float g, float& m, float& v, float gscale, float keep, float b1, float b2,
+                                             float eps, float step_size, float inv_bc2_sqrt) {
+#pragma clang fp contract(off)
+  const float pi = p * keep;
+  const float gi = g * gscale;
+  const float mi = fmaf(1.f - b1, gi, b1 * m);
+  const float vi = b2 * v + (1.f - b2) * gi * gi;
+  m = mi; v = vi;
+  const float denom = fmaf(sqrtf(vi), inv_bc2_sqrt, eps);
+  p = fmaf(-step_size, mi / denom, pi);
+}
+
 // Where one launch gets its per-step scalars.  By value from the host, or (DEV) from device memory: hyper[0..3] = grad_scale,
 // step_size = lr / (1 - b1^t), 1 / sqrt(1 - b2^t), weight_decay as the caller will use them for the NEXT launch - what a captured
 // hipGraph of a training step launches: the node's kernel arguments are frozen at capture, the bias corrections change every
 // step.  CLIP adds the 8-float state umpr_grad_norm left; the forms without it carry an empty struct in the pointer's place.
+// In the decoupled form the fourth scalar is lr * weight_decay, the fraction a parameter with multipliers 1 shrinks by.
 struct AdamScalars { float gscale, step_size, inv_bc2_sqrt, wd; };
 struct NoClipState {};
 
-// The one dense Adam kernel.  CLIP: a step whose gradient norm was not finite touches nothing, and the gradient scale is
-// multiplied by the clip coefficient - ONE float product of the two scalars, so that coef == 1 leaves the scale, and with it
-// every bit of the update, as the forms without CLIP have it.
-template <bool DEV, bool CLIP>
+// The segments of one launch (FusedAdam(lr_scales=, wd_scales=)): elements [end[k-1], end[k]) of the launch - end[-1] = 0 - take
+// step_size * lr_mult[k] and wd * wd_mult[k], ONE float product each, so that multipliers of exactly 1 leave every bit of the
+// update as the plain forms have it.  Every end but the last is a multiple of 64 elements, so the 64 consecutive elements one
+// wave handles in one pass of the grid (256-thread blocks, a grid stride that is a multiple of 256) lie in one segment whatever
+// the base pointers' alignment: the lookup is wave-uniform, and the table holds the ends in WAVES, end / 64, as 32-bit numbers -
+// the scalar unit compares those, it has no 64-bit less-than.  The last end, n, and every entry behind it are ceil(n / 64), which
+// no wave's number reaches; those entries repeat the last multipliers.  The table travels in the kernel arguments, as GradArenas
+// does.
+constexpr int ADAM_MAX_SEGS = 16, ADAM_THREADS = 256;
+struct AdamSegs {
+  unsigned end_wave[ADAM_MAX_SEGS];
+  float lr_mult[ADAM_MAX_SEGS];
+  float wd_mult[ADAM_MAX_SEGS];
+};
+struct NoSegs {};
+
+// One step of the lookup: a wave at or behind `end` takes the next segment's multipliers.  All six operands are wave-uniform.
+// Written as the scalar unit's compare and two selects: left to the compiler, the chain of selects between floats became 30
+// vector selects per element (it keeps floats in vector registers), and a count of the ends in front of the wave a vector
+// population count - on a kernel whose vector unit has the update itself to do.
+__device__ __forceinline__ void seg_pick(float& lr_mult, float& wd_mult, unsigned wave, unsigned end, float lr_next,
+                                         float wd_next) {
+  asm("s_cmp_ge_u32 %2, %3\n\ts_cselect_b32 %0, %4, %0\n\ts_cselect_b32 %1, %5, %1"
+      : "+s"(lr_mult), "+s"(wd_mult)
+      : "s"(wave), "s"(end), "s"(lr_next), "s"(wd_next)
+      : "scc");
+}
+
+// The one dense Adam kernel.  CLIP: a step whose gradient norm was not finite touches nothing - the decoupled shrink included -
+// and the gradient scale is multiplied by the clip coefficient - ONE float product of the two scalars, so that coef == 1 leaves
+// the scale, and with it every bit of the update, as the forms without CLIP have it.  SEG: per-segment multipliers, looked up
+// once per wave and pass from the wave's first element - a value every lane agrees on and the compiler is told so
+// (readfirstlane of the wave's number), which keeps the comparisons and both selected multipliers in scalar registers.
+// DECOUPLED: adamw_update in place of adam_update.
+template <bool DEV, bool CLIP, bool SEG, bool DECOUPLED>
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                             long n, float b1, float b2, float eps, std::conditional_t<DEV, const float*, AdamScalars> hyper,
-                            std::conditional_t<CLIP, const float*, NoClipState> state) {
+                            std::conditional_t<CLIP, const float*, NoClipState> state,
+                            const std::conditional_t<SEG, AdamSegs, NoSegs> segs) {
+#pragma clang fp contract(off)
+  static_assert(SEG || !DECOUPLED, "the decoupled form always carries a segment table (one segment when nothing is scaled)");
   if constexpr (CLIP) {
     if (state[UMPR_CLIP_FINITE] == 0.f) return;
   }
@@ -139,19 +194,36 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
   if constexpr (DEV) a = AdamScalars{hyper[0], hyper[1], hyper[2], hyper[3]};
   else a = hyper;
   if constexpr (CLIP) a.gscale = a.gscale * state[UMPR_CLIP_COEF];
-  for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    adam_update(p[i], g[i], m[i], v[i], a.gscale, a.wd, b1, b2, eps, a.step_size, a.inv_bc2_sqrt);
+  const long stride = (long)gridDim.x * blockDim.x;
+  if constexpr (!SEG) {
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride)
+      adam_update(p[i], g[i], m[i], v[i], a.gscale, a.wd, b1, b2, eps, a.step_size, a.inv_bc2_sqrt);
+  } else {
+    // the number of this wave's 64 elements among the launch's: the same in every lane, and the compiler is told so
+    unsigned wave = blockIdx.x * (ADAM_THREADS / 64) + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned wave_stride = gridDim.x * (ADAM_THREADS / 64);
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += stride, wave += wave_stride) {
+      float lr_mult = segs.lr_mult[0], wd_mult = segs.wd_mult[0];
+#pragma unroll
+      for (int k = 1; k < ADAM_MAX_SEGS; ++k)
+        seg_pick(lr_mult, wd_mult, wave, segs.end_wave[k - 1], segs.lr_mult[k], segs.wd_mult[k]);
+      const float step_size = a.step_size * lr_mult, wd = a.wd * wd_mult;
+      if constexpr (DECOUPLED) adamw_update(p[i], g[i], m[i], v[i], a.gscale, 1.f - wd, b1, b2, eps, step_size, a.inv_bc2_sqrt);
+      else adam_update(p[i], g[i], m[i], v[i], a.gscale, wd, b1, b2, eps, step_size, a.inv_bc2_sqrt);
+    }
+  }
 }
 
 // 256 threads, min(ceil(n / 256), 8192) workgroups (n >= 1 here), grid-stride loop: a second pass of the grid from 8192 * 256
 // elements on.  Elementwise, so the grid has no say in the result.
-template <bool DEV, bool CLIP, class Hyper, class State>
+template <bool DEV, bool CLIP, bool SEG = false, bool DECOUPLED = false, class Hyper, class State, class Segs = NoSegs>
 int adam_launch(const char* what, float* p, const float* g, float* m, float* v, long n, double b1, double b2, double eps,
-                Hyper hyper, State state, void* stream) {
+                Hyper hyper, State state, void* stream, Segs segs = Segs{}) {
   if (n == 0) return 0;
-  const long blocks = (n + 255) / 256;
-  adam_kernel<DEV, CLIP><<<(int)(blocks > 8192 ? 8192 : blocks), 256, 0, static_cast<hipStream_t>(stream)>>>(
-      p, g, m, v, n, (float)b1, (float)b2, (float)eps, hyper, state);
+  const long blocks = (n + ADAM_THREADS - 1) / ADAM_THREADS;
+  adam_kernel<DEV, CLIP, SEG, DECOUPLED>
+      <<<(int)(blocks > 8192 ? 8192 : blocks), ADAM_THREADS, 0, static_cast<hipStream_t>(stream)>>>(
+          p, g, m, v, n, (float)b1, (float)b2, (float)eps, hyper, state, segs);
   UMPR_LAUNCH_CHECK(what);
   return 0;
 }
@@ -449,6 +521,55 @@ int umpr_adam_step_dev_clip(float* p, const float* g, float* m, float* v, long n
                             const float* hyper, const float* state, void* stream) {
   UMPR_REQUIRE(n >= 0 && hyper != nullptr && state != nullptr, "adam_dev_clip: bad arguments");
   return adam_launch<true, true>("adam_dev_clip", p, g, m, v, n, beta1, beta2, eps, hyper, state, stream);
+}
+
+int umpr_adam_step_groups(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, long step, double grad_scale, const float* hyper,
+                          const float* clip_state, const long* seg_end, const float* seg_lr_mult, const float* seg_wd_mult,
+                          int n_segs, int decoupled, void* stream) {
+  UMPR_REQUIRE(n >= 0 && (hyper != nullptr || step >= 1), "adam_groups: bad step/n");
+  if (n == 0) return 0;
+  UMPR_REQUIRE((n + 63) / 64 <= 0xffffffffL, "adam_groups: n = %ld: more than 2^32 waves of 64 elements", n);
+  UMPR_REQUIRE(n_segs >= 1 && n_segs <= ADAM_MAX_SEGS, "adam_groups: %d segments outside 1..%d", n_segs, ADAM_MAX_SEGS);
+  UMPR_REQUIRE(seg_end != nullptr && seg_lr_mult != nullptr && seg_wd_mult != nullptr, "adam_groups: null segment table");
+  AdamSegs segs;
+  long prev = 0;
+  for (int k = 0; k < n_segs; ++k) {
+    const long end = seg_end[k];
+    const float a = seg_lr_mult[k], w = seg_wd_mult[k];
+    UMPR_REQUIRE(end > prev && end <= n, "adam_groups: segment %d ends at %ld: not behind %ld or past n = %ld", k, end, prev, n);
+    UMPR_REQUIRE(k == n_segs - 1 || end % 64 == 0, "adam_groups: segment %d ends at %ld, not a multiple of 64 elements", k, end);
+    UMPR_REQUIRE(k < n_segs - 1 || end == n, "adam_groups: the last segment ends at %ld, not at n = %ld", end, n);
+    UMPR_REQUIRE(isfinite(a) && a > 0.f, "adam_groups: segment %d: learning-rate multiplier %g is not finite and > 0", k, (double)a);
+    UMPR_REQUIRE(isfinite(w) && w >= 0.f, "adam_groups: segment %d: decay multiplier %g is not finite and >= 0", k, (double)w);
+    // decoupled: the segment shrinks by (lr * a) * (wd * w): its one multiplier of the launch's lr * wd is a * w, rounded once
+    segs.end_wave[k] = (unsigned)((end + 63) / 64);
+    segs.lr_mult[k] = a;
+    segs.wd_mult[k] = decoupled ? (float)((double)a * (double)w) : w;
+    prev = end;
+  }
+  for (int k = n_segs; k < ADAM_MAX_SEGS; ++k) {      // never selected: no wave's number reaches ceil(n / 64)
+    segs.end_wave[k] = segs.end_wave[n_segs - 1];
+    segs.lr_mult[k] = segs.lr_mult[n_segs - 1];
+    segs.wd_mult[k] = segs.wd_mult[n_segs - 1];
+  }
+  // the decoupled forms' fourth scalar: lr * weight_decay, rounded to float once (FusedAdam.hyper_rows makes the same double)
+  AdamScalars host{};
+  if (hyper == nullptr) {
+    host = adam_host_scalars(lr, beta1, beta2, weight_decay, step, grad_scale);
+    if (decoupled) host.wd = (float)(lr * weight_decay);
+  }
+  const char* what = "adam_groups";
+#define UMPR_ADAM_GROUPS(DEC)                                                                                                    \
+  (hyper != nullptr                                                                                                              \
+       ? (clip_state != nullptr                                                                                                  \
+              ? adam_launch<true, true, true, DEC>(what, p, g, m, v, n, beta1, beta2, eps, hyper, clip_state, stream, segs)        \
+              : adam_launch<true, false, true, DEC>(what, p, g, m, v, n, beta1, beta2, eps, hyper, NoClipState{}, stream, segs))   \
+       : (clip_state != nullptr                                                                                                  \
+              ? adam_launch<false, true, true, DEC>(what, p, g, m, v, n, beta1, beta2, eps, host, clip_state, stream, segs)        \
+              : adam_launch<false, false, true, DEC>(what, p, g, m, v, n, beta1, beta2, eps, host, NoClipState{}, stream, segs)))
+  return decoupled ? UMPR_ADAM_GROUPS(true) : UMPR_ADAM_GROUPS(false);
+#undef UMPR_ADAM_GROUPS
 }
 
 }  // extern "C"

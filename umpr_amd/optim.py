@@ -8,7 +8,8 @@ the data-parallel gradient exchange is a handful of large RCCL all-reduces on th
 
 ``FusedAdam.step`` is the one step path: gradient source (gradient or accumulation arenas), the clip norm if clipping is on,
 the per-group ranges, the sparse rows.  Every dense launch goes through ``FusedAdam._adam``, which picks one of the library's
-four entry points - ``umpr_adam_step[_dev][_clip]``, one kernel template in csrc/optim.hip - from graph mode and clipping.
+four entry points - ``umpr_adam_step[_dev][_clip]``, one kernel template in csrc/optim.hip - from graph mode and clipping, or,
+for a range with per-module multipliers or under decoupled decay, ``umpr_adam_step_groups`` with the segments ``plan()`` made.
 """
 from __future__ import annotations
 
@@ -70,10 +71,40 @@ def _parallel_active():
 
 
 _ALIGN = 64      # floats
+MAX_SEGMENTS = 16    # of one umpr_adam_step_groups launch (csrc/optim.hip::ADAM_MAX_SEGS)
 
 
 def _pad(k):
     return (k + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+def parse_scales(text, option="scale"):
+    """'visual_net.vgg16.=1e-3,embedding.=0.1' -> {'visual_net.vgg16.': 0.001, 'embedding.': 0.1}: what --lr_scale and --wd_scale
+    take.  '' is {}.  Raises ValueError on an entry without '=', an empty or repeated prefix, or a multiplier that is no number."""
+    out = {}
+    for item in (t.strip() for t in str(text).split(",")):
+        if not item:
+            continue
+        prefix, eq, value = item.rpartition("=")
+        prefix = prefix.strip()
+        if not eq or not prefix:
+            raise ValueError(f"--{option}: {item!r} is not <name prefix>=<multiplier>")
+        if prefix in out:
+            raise ValueError(f"--{option}: the prefix {prefix!r} is given twice")
+        try:
+            out[prefix] = float(value)
+        except ValueError:
+            raise ValueError(f"--{option}: the multiplier of the prefix {prefix!r} is no number: {value.strip()!r}") from None
+    return out
+
+
+def match_scale(name, scales):
+    """(multiplier, prefix) of the longest prefix in `scales` that `name` starts with, (1.0, None) if there is none"""
+    best = None
+    for prefix in scales:
+        if name.startswith(prefix) and (best is None or len(prefix) > len(best)):
+            best = prefix
+    return (1.0, None) if best is None else (float(scales[best]), best)
 
 
 class _Group:
@@ -150,6 +181,9 @@ class _Ema(NamedTuple):
     n_arenas: int
 
 
+_GROUP_DEFAULTS = {"lr_scale": {}, "wd_scale": {}, "decoupled_decay": False, "warmup_steps": 0}
+
+
 class FusedAdam:
     """Adam(betas=(0.9,0.999), eps=1e-8) with the reference's grouping; ``lr_decay`` per ``epoch_end()``.
 
@@ -189,17 +223,53 @@ class FusedAdam:
     evaluation, ``state_dict()`` carries it as "ema" / "ema_decay".  Not with a sparse table (it lives outside the arenas, and
     averaging it would touch every row each step) and not in graph mode (the first update is another kernel than the captured
     one).  Data parallel needs nothing: every rank holds the same parameters and computes the same bits - built, not run on
-    more than one rank.  0 (the default) is off: nothing is allocated, launched or stored for it."""
+    more than one rank.  0 (the default) is off: nothing is allocated, launched or stored for it.
 
-    sparse = None       # _Sparse: a table updated row-wise (a model with sparse_embedding)
+    ``lr_scales`` / ``wd_scales`` map parameter-name prefixes to multipliers of the learning rate / of the decay; the longest
+    prefix a name starts with wins, a name no prefix matches keeps 1.  ``decoupled_decay`` takes the decay out of the gradient
+    and shrinks the parameter instead, as ``torch.optim.AdamW`` does; ``warmup_steps`` = N > 0 ramps the learning rate linearly
+    over the first N optimiser steps.  For a parameter with multipliers (a, w), at optimiser step t (1-based, the one the bias
+    corrections use):  lr_t = lr * min(1, t / N) * a;  coupled (default): g' = grad_scale * clip_coef * g + (wd * w) * p, then Adam
+    with lr_t - today's update with a and w applied;  decoupled: p <- p * (1 - lr_t * wd * w), then Adam with lr_t on
+    grad_scale * clip_coef * g alone.  Bias parameters keep wd = 0 in both modes (a ``wd_scales`` entry has no effect on them),
+    the clip norm is that of the gradient before any decay term, and a step that clipping skips touches nothing, the shrink
+    included.  A sparse table takes lr_t with the a of its own name and has no decay, as before.  One launch still covers a whole
+    group: ``umpr_adam_step_groups`` carries up to 16 segments of (end, a, w) in its kernel arguments, ``plan()`` merges
+    neighbours with equal multipliers into one segment and cuts a range with more segments into several launches.  A range
+    whose multipliers are all 1 under coupled decay goes to the entry points it went to before, with the arguments it had:
+    the warm-up changes scalars only.  ``param_multipliers()`` shows (a, w) per name; ``state_dict()`` carries the four settings
+    as "param_groups" when any of them is set, and a checkpoint written under other settings is refused.  Graph mode works
+    unchanged: the multipliers are static kernel arguments and the warm-up rides in the hyper rows, whose fourth float is
+    lr_t(a = 1) * wd in decoupled mode.  Data parallel needs nothing: every rank computes the same scalars - built, not run on
+    more than one rank.  With all four at their defaults nothing is planned, launched or stored for them."""
+
+    sparse = None      # _Sparse: a table updated row-wise (a model with sparse_embedding)
     _hyper = None       # device float32 [groups][4] of enable_graph_mode: the per-step scalars of the device-scalar kernels
     ema_decay = 0.0     # the moving average of the parameters is off
     ema_ready = False   # True from the first update of the average on
     _ema = None         # _Ema, made by the first step() with ema_decay > 0
     _swapped = False    # inside swapped_ema(): the parameters hold the average, the EMA arenas the raw weights
+    lr_scales = {}      # per-module multipliers, decoupled decay and warm-up are off (__init__ binds dicts of its own)
+    wd_scales = {}
+    decoupled_decay = False
+    warmup_steps = 0
 
     def __init__(self, model, lr, l2_regularization, lr_decay=1.0, betas=(0.9, 0.999), eps=1e-8, order_key=None,
-                 max_grad_norm=0.0, ema_decay=0.0):
+                 max_grad_norm=0.0, ema_decay=0.0, lr_scales=None, wd_scales=None, decoupled_decay=False, warmup_steps=0):
+        if not isinstance(decoupled_decay, bool):
+            raise ValueError(f"decoupled_decay must be True or False, got {decoupled_decay!r}")
+        if isinstance(warmup_steps, bool) or not isinstance(warmup_steps, int) or warmup_steps < 0:
+            raise ValueError(f"warmup_steps must be a whole number >= 0 (0 turns the warm-up off), got {warmup_steps!r}")
+        self.lr_scales = {str(k): float(v) for k, v in (lr_scales or {}).items()}
+        self.wd_scales = {str(k): float(v) for k, v in (wd_scales or {}).items()}
+        self.decoupled_decay = decoupled_decay
+        self.warmup_steps = warmup_steps
+        for prefix, a in self.lr_scales.items():
+            if not math.isfinite(a) or a <= 0.0:
+                raise ValueError(f"lr_scales: the multiplier of the prefix {prefix!r} must be finite and > 0, got {a}")
+        for prefix, w in self.wd_scales.items():
+            if not math.isfinite(w) or w < 0.0:
+                raise ValueError(f"wd_scales: the multiplier of the prefix {prefix!r} must be finite and >= 0, got {w}")
         max_grad_norm = float(max_grad_norm)
         if not math.isfinite(max_grad_norm) or max_grad_norm < 0.0:
             raise ValueError(f"max_grad_norm must be finite and >= 0 (0 turns clipping off), got {max_grad_norm}")
@@ -228,9 +298,22 @@ class FusedAdam:
         named.sort(key=lambda np_: order_key(np_[0]))  # stable: model order inside each class
         if not named:
             raise ValueError("FusedAdam: the model has no trainable parameter")
+        # a prefix nothing starts with is a typing error, not a wish (the sparse table is trainable, and has no decay)
+        trainable = [n for n, _ in named] + ([self.sparse.name] if self.sparse is not None else [])
+        for prefix in self.lr_scales:
+            if not any(n.startswith(prefix) for n in trainable):
+                raise ValueError(f"lr_scales: the prefix {prefix!r} matches no trainable parameter")
+        for prefix in self.wd_scales:
+            if not any(n.startswith(prefix) and 'bias' not in n for n, _ in named):
+                raise ValueError(f"wd_scales: the prefix {prefix!r} matches no parameter with weight decay"
+                                 + (" (bias parameters and a sparse table have none)"
+                                    if any(n.startswith(prefix) for n in trainable) else ""))
         device = named[0][1].device
         self.groups = [_Group([(n, p) for n, p in named if 'bias' not in n], l2_regularization, device),
                        _Group([(n, p) for n, p in named if 'bias' in n], 0.0, device)]
+        # nothing scaled, coupled decay: _adam never plans (the warm-up alone changes scalars only)
+        self._plain = not (self.lr_scales or self.wd_scales or self.decoupled_decay)
+        self._plans = {}            # (group, lo, hi) -> the launches of plan() with their host tables, built on first use
         self.model = model
         self.base_lr = lr
         self.lr = lr
@@ -292,10 +375,83 @@ class FusedAdam:
 
     def hyper_rows(self, grad_scale=1.0):
         """[grad_scale, lr / (1 - b1^t), 1 / sqrt(1 - b2^t), weight_decay] per group for the step about to be taken (float64 on
-        the host, as the plain kernel's launcher computes them)."""
+        the host, as the plain kernel's launcher computes them).  lr is the warmed-up rate of step t (``lr_at``); with
+        ``decoupled_decay`` the fourth float is lr * weight_decay, the fraction an unscaled parameter shrinks by."""
         t = self.step_count + 1
-        return [[float(grad_scale), float(self.lr / (1.0 - self.betas[0] ** t)), float(1.0 / (1.0 - self.betas[1] ** t) ** 0.5),
-                 float(g.weight_decay)] for g in self.groups]
+        lr = self.lr_at(t)
+        return [[float(grad_scale), float(lr / (1.0 - self.betas[0] ** t)), float(1.0 / (1.0 - self.betas[1] ** t) ** 0.5),
+                 float(lr * g.weight_decay if self.decoupled_decay else g.weight_decay)] for g in self.groups]
+
+    # ---- per-module multipliers, decoupled decay, warm-up ------------------------------------------------------------------------
+    def lr_at(self, step):
+        """the learning rate of optimiser step `step` (1-based) before any multiplier: lr * min(1, step / warmup_steps)"""
+        return self.lr if step >= self.warmup_steps else self.lr * (step / self.warmup_steps)
+
+    def param_multipliers(self):
+        """{parameter name: (a, w)}: the learning-rate and decay multipliers of every trainable parameter, by longest prefix.
+        (w has no effect on a parameter without decay: a bias, a sparse table.)"""
+        names = [n for g in self.groups for n in g.names] + ([self.sparse.name] if self.sparse is not None else [])
+        return {n: (match_scale(n, self.lr_scales)[0], match_scale(n, self.wd_scales)[0]) for n in names}
+
+    def _spans(self, gi):
+        """[(start, stop, a, w)] over group `gi`'s arena: neighbours with equal multipliers merged, the padding behind a
+        parameter with the parameter.  A group without decay ignores w."""
+        g = self.groups[gi]
+        spans = []
+        for n in g.names:
+            off, k = g.offsets[n]
+            a, w = match_scale(n, self.lr_scales)[0], match_scale(n, self.wd_scales)[0] if g.weight_decay != 0.0 else 1.0
+            if spans and spans[-1][2:] == (a, w):
+                spans[-1] = (spans[-1][0], off + _pad(k), a, w)
+            else:
+                spans.append((off, off + _pad(k), a, w))
+        return spans
+
+    def plan(self, gi, lo, hi):
+        """The launches that update elements [lo, hi) of group `gi`: [(lo', hi', [(end, a, w), ...]), ...] with at most 16
+        segments each, `end` relative to lo'.  Every end but a launch's last is a multiple of 64: parameters start on 64-float
+        boundaries, and a range that does not (no caller has one) gets the floats up to the next boundary as a launch of their
+        own.  Pure host arithmetic."""
+        spans = self._spans(gi)
+        head = min(hi, _pad(lo))
+        launches = []
+        for l, h in ((lo, head), (head, hi)):
+            if h <= l:
+                continue
+            segs = [(min(stop, h), a, w) for start, stop, a, w in spans if stop > l and start < h]
+            for k in range(0, len(segs), MAX_SEGMENTS):
+                base = segs[k - 1][0] if k else l
+                chunk = segs[k:k + MAX_SEGMENTS]
+                launches.append((base, chunk[-1][0], [(end - base, a, w) for end, a, w in chunk]))
+        return launches
+
+    def _planned(self, gi, lo, hi):
+        """plan(gi, lo, hi) with the three host tables of each launch; None if every multiplier in the range is 1 and the
+        decay coupled: the range then goes to the plain entry points"""
+        key = (gi, lo, hi)
+        if key not in self._plans:
+            launches = self.plan(gi, lo, hi)
+            if not self.decoupled_decay and all(a == 1.0 and w == 1.0 for _, _, segs in launches for _, a, w in segs):
+                self._plans[key] = None
+            else:
+                self._plans[key] = [(l, h, (ctypes.c_long * len(s))(*[e for e, _, _ in s]),
+                                     (ctypes.c_float * len(s))(*[a for _, a, _ in s]),
+                                     (ctypes.c_float * len(s))(*[w for _, _, w in s]), len(s)) for l, h, s in launches]
+        return self._plans[key]
+
+    def group_summary(self):
+        """lines for the log: the multipliers per prefix with parameter counts, and the segments and launches per group"""
+        mult = self.param_multipliers()
+        lines = []
+        for what, scales, col in (("lr_scale", self.lr_scales, 0), ("wd_scale", self.wd_scales, 1)):
+            for prefix in scales:
+                hit = [n for n in mult if match_scale(n, scales)[1] == prefix]
+                lines.append(f"{what} {prefix!r} = {scales[prefix]:g}: {len(hit)} parameters")
+        for gi, g in enumerate(self.groups):
+            launches = self.plan(gi, 0, g.numel)
+            lines.append(f"group {gi} ({'weights' if gi == 0 else 'biases'}, {len(g.names)} parameters): "
+                         f"{sum(len(s) for _, _, s in launches)} segments in {len(launches)} launches")
+        return lines
 
     def prepare_step(self, grad_scale=1.0):
         rows = self.hyper_rows(grad_scale)
@@ -480,23 +636,37 @@ class FusedAdam:
             return
         row_id, row_grad, T = rows
         p, m, v = self.sparse.table, self.sparse.m, self.sparse.v
-        lib().call("umpr_sparse_adam_rows", p, m, v, p.shape[0], p.shape[1], row_id, row_grad, T, self.lr, self.betas[0],
+        lr = self.lr_at(self.step_count)               # warmed up, times the multiplier of the table's own name: host scalars
+        if self.lr_scales:
+            lr = lr * match_scale(self.sparse.name, self.lr_scales)[0]
+        lib().call("umpr_sparse_adam_rows", p, m, v, p.shape[0], p.shape[1], row_id, row_grad, T, lr, self.betas[0],
                    self.betas[1], self.eps, self.step_count, float(grad_scale), clip_state, stream_ptr())
 
     def _adam(self, gi, lo, hi, grads, step, grad_scale, clip_state):
         """The one dense Adam launch: elements [lo, hi) of group `gi` from the arena `grads`, as step number `step`.  Graph mode
         takes the per-step scalars from device memory (`step` and `grad_scale` are then in ``_hyper``), `clip_state` the clip
-        coefficient: the same kernel with two switches (csrc/optim.hip)."""
+        coefficient: the same kernel with two switches (csrc/optim.hip).  A range with a multiplier other than 1, or any range
+        under decoupled decay, goes through ``plan()`` to ``umpr_adam_step_groups`` - the kernel's other two switches - in as
+        many launches as the plan has; every other range is launched as it always was, with the warmed-up learning rate."""
         if hi <= lo:
             return
         g = self.groups[gi]
+        lr = self.lr_at(step)
+        planned = None if self._plain else self._planned(gi, lo, hi)
+        if planned is not None:
+            hyper = self._hyper[gi] if self._hyper is not None else None
+            for l, h, ends, lr_mult, wd_mult, n_segs in planned:
+                lib().call("umpr_adam_step_groups", g.p[l:h], grads[l:h], g.m[l:h], g.v[l:h], h - l, lr, self.betas[0],
+                           self.betas[1], self.eps, g.weight_decay, step, grad_scale, hyper, clip_state, ctypes.addressof(ends),
+                           ctypes.addressof(lr_mult), ctypes.addressof(wd_mult), n_segs, int(self.decoupled_decay), stream_ptr())
+            return
         arenas = (g.p[lo:hi], grads[lo:hi], g.m[lo:hi], g.v[lo:hi], hi - lo)
         tail = (stream_ptr(),) if clip_state is None else (clip_state, stream_ptr())
         if self._hyper is not None:
             lib().call("umpr_adam_step_dev" if clip_state is None else "umpr_adam_step_dev_clip", *arenas, self.betas[0],
                        self.betas[1], self.eps, self._hyper[gi], *tail)
         else:
-            lib().call("umpr_adam_step" if clip_state is None else "umpr_adam_step_clip", *arenas, self.lr, self.betas[0],
+            lib().call("umpr_adam_step" if clip_state is None else "umpr_adam_step_clip", *arenas, lr, self.betas[0],
                        self.betas[1], self.eps, g.weight_decay, step, grad_scale, *tail)
 
     def step(self, grad_scale=1.0):
@@ -620,7 +790,13 @@ class FusedAdam:
             # the average per parameter name, like the moments; empty before the first update
             st["ema"] = {n: t.detach().cpu().reshape(-1).clone() for n, t in self.ema_tensors().items()} if self.ema_ready else {}
             st["ema_decay"] = float(self.ema_decay)
+        if self._group_settings() != _GROUP_DEFAULTS:
+            st["param_groups"] = self._group_settings()    # (the warm-up has no state of its own: it follows "step")
         return st
+
+    def _group_settings(self):
+        return {"lr_scale": dict(self.lr_scales), "wd_scale": dict(self.wd_scales),
+                "decoupled_decay": self.decoupled_decay, "warmup_steps": self.warmup_steps}
 
     def _moment_sizes(self):
         want = {n: g.offsets[n][1] for g in self.groups for n in g.names}
@@ -634,7 +810,15 @@ class FusedAdam:
         --train_embedding setting.  Nor does one written under the other --sparse_embedding setting: the table's moments have the
         same names and sizes there, but not the same meaning (lazily kept per row, no L2 in them).  Nor does one written with a
         moving average (--ema_decay) for a run without one, or the other way round; another decay value is accepted, and the
-        run's own value holds."""
+        run's own value holds.  Nor does one written under another --lr_scale, --wd_scale, --decoupled_decay or --warmup_steps
+        (a checkpoint without "param_groups" was written with all four at their defaults): the moments would continue under
+        another update rule."""
+        was, now = {**_GROUP_DEFAULTS, **st.get("param_groups", {})}, self._group_settings()
+        for option in _GROUP_DEFAULTS:
+            if was[option] != now[option]:
+                show = lambda x: ",".join(f"{k}={v:g}" for k, v in x.items()) if isinstance(x, dict) else x
+                raise ValueError(f"optimizer state does not match this run: the checkpoint was written with --{option} "
+                                 f"{show(was[option])!r}, this run has --{option} {show(now[option])!r}: pass the same --{option}")
         was, now = bool(st.get("sparse_embedding", False)), self.sparse is not None
         if was != now:
             raise ValueError("optimizer state does not match this run: the checkpoint was written with --sparse_embedding "

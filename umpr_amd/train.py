@@ -7,7 +7,7 @@ import torch
 
 from . import parallel
 from .checkpoint import load_checkpoint, save_checkpoint
-from .optim import FusedAdam
+from .optim import FusedAdam, parse_scales
 
 
 def evaluate_mse(model, dataloader):
@@ -137,7 +137,10 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     `opt.swapped_ema()`, and says so in its log line, so the checkpoint is chosen by the average's validation MSE.  The
     checkpoint itself is written outside the swap: "model" keeps the raw weights (an exact resume, the same state_dict
     interchange), the average travels in ck["optimizer"]["ema"] (load_checkpoint(weights="ema")).  The initial validation is on
-    the raw weights: no average exists yet."""
+    the raw weights: no average exists yet.  `config.lr_scale` / `config.wd_scale` ("prefix=multiplier,..."),
+    `config.decoupled_decay` and `config.warmup_steps` give modules their own learning rate and decay, AdamW's decoupled decay
+    and a linear warm-up (FusedAdam(lr_scales=, wd_scales=, decoupled_decay=, warmup_steps=)); each is passed on only when it is
+    set, and the log then lists the multipliers per prefix and the segments per group."""
     accum = int(getattr(config, "accum_steps", 1))
     if accum > 1 and parallel.active():
         raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
@@ -147,8 +150,22 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     start = time.perf_counter()
     ema_decay = float(getattr(config, "ema_decay", 0.0))
     averaged = {"ema_decay": ema_decay} if ema_decay > 0.0 else {}      # (off: the call is the one it was)
+    grouped = {}                                                         # (each of the four passed on only when it is set)
+    if getattr(config, "lr_scale", ""):
+        grouped["lr_scales"] = parse_scales(config.lr_scale, "lr_scale")
+    if getattr(config, "wd_scale", ""):
+        grouped["wd_scales"] = parse_scales(config.wd_scale, "wd_scale")
+    if getattr(config, "decoupled_decay", False):
+        grouped["decoupled_decay"] = True
+    if getattr(config, "warmup_steps", 0):
+        grouped["warmup_steps"] = config.warmup_steps
     opt = FusedAdam(model, config.learning_rate, config.l2_regularization, config.lr_decay,
-                    max_grad_norm=float(getattr(config, "grad_clip", 0.0)), **averaged)
+                    max_grad_norm=float(getattr(config, "grad_clip", 0.0)), **averaged, **grouped)
+    if grouped:
+        log('Optimiser: ' + ('decoupled weight decay (AdamW)' if opt.decoupled_decay else 'coupled L2')
+            + (f', linear warm-up over {opt.warmup_steps} steps' if opt.warmup_steps else ''))
+        for line in opt.group_summary():
+            log('  ' + line)
     if averaged:
         log(f'Moving average of the weights: decay {ema_decay}, {opt.ema_bytes() / 1e6:.0f} MB more; validation and the '
             f'checkpoint choice run on the averaged weights')
