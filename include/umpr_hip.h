@@ -451,6 +451,25 @@ int umpr_photo_fetch_u8(const uint8_t* packed, size_t packed_bytes, const umpr_p
                         const int32_t* dst_slot, int n_photos, int dst_h, int dst_w, uint8_t* store, long n_slots, float* out,
                         void* stream);
 
+/* ---- augmented photo fetch (umpr_amd/photos.py::PhotoAugment): random crop and flip at the fetch -------------------------------
+ * umpr_photo_fetch_u8 with a window and a flip per photo.  With U [dst_h][dst_w][3] the resized uint8 image of photo i (what a
+ * slot holds planar) and crop[i] = (x0, y0, cw, ch, flip), HOST int32 [n_photos][5]:
+ *   A = resize_bilinear_u8(U[y0:y0+ch, x0:x0+cw], (dst_w, dst_h));  A = A[:, ::-1] if flip;  out[i] = lut[A] planar,
+ * bit for bit; a 0 x 0 descriptor without a src_slot gives zeros whatever its record says; (0, 0, dst_w, dst_h, 0) is
+ * umpr_photo_fetch_u8's photo.  A decoded photo is first resized exactly as there, uint8 only: into its dst_slot when it has one -
+ * a store slot always receives the plain image - else into the next free slot of `scratch` (device, 16-byte aligned, n_scratch
+ * slots of umpr_photo_store_slot_bytes).  Then one kernel writes `out` for the whole chunk from store and scratch, on the same
+ * stream.  store == NULL with n_slots == 0: everything goes through scratch.  xtaps [dst_w][4][dst_w] and ytaps [dst_h][4][dst_h]
+ * (device int32) hold, in row s-1, the concatenated data._column_taps(dst_w, s) / data._row_taps(dst_h, s); the kernel clamps
+ * their indices into the window.  Refused without launching, `out`, `store` and `scratch` untouched: all that umpr_photo_fetch_u8
+ * refuses; a window outside the image or with cw < 1 or ch < 1; a flip outside {0, 1}; fewer scratch slots than decoded photos
+ * without a dst_slot; a null table; scratch or out not 16-byte aligned; dst_h or dst_w above 4096 (the kernel stages the source
+ * of an output tile in LDS, and its bound on that source is proven for such sides).  No allocation or copy: capture-safe. */
+int umpr_photo_fetch_augment_u8(const uint8_t* packed, size_t packed_bytes, const umpr_photo_desc* desc, const int32_t* src_slot,
+                                const int32_t* dst_slot, const int32_t* crop, int n_photos, int dst_h, int dst_w, uint8_t* store,
+                                long n_slots, uint8_t* scratch, long n_scratch, const int32_t* xtaps, const int32_t* ytaps,
+                                float* out, void* stream);
+
 /* ---- device-resident VGG features (umpr_amd/photos.py::FeatureStore) -----------------------------------------------------------
  * With a frozen VGG (--freeze_vgg) the F floats the stack yields for a photo are a constant of the run.  `store` (device memory)
  * holds n_slots rows of F fp32; `fresh` [n_fresh][F] holds the rows the VGG has just computed for the photos the store lacks.

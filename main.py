@@ -13,6 +13,8 @@
                                                                                   # for every photo kept in 1 GB of HBM
     python main.py --data_dir data/music --freeze_conv True --pool5_store_gb 8    # freeze the conv base, train the classifier on
                                                                                   # each photo's pool5 row kept in 8 GB of HBM
+    python main.py --data_dir data/music --photo_store_gb 1 --photo_flip True --photo_crop 0.3   # augment the photos of every
+                                                                              # training step on the GPU: random crop >= 30 %, flip
     python main.py --data_dir data/music --review_net_only True --review_store True   # tokenised reviews kept in HBM: a batch
                                                                                       # travels as indices, one kernel pads its ids
     python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
@@ -230,7 +232,8 @@ EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_
                  "loader_workers": 0, "valid_every": 500, "dtype": "fp32", "photo_store_gb": 0.0, "grad_clip": 0.0,
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
                  "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False, "ema_decay": 0.0,
-                 "lr_scale": "", "wd_scale": "", "decoupled_decay": False, "warmup_steps": 0}
+                 "lr_scale": "", "wd_scale": "", "decoupled_decay": False, "warmup_steps": 0, "photo_flip": False,
+                 "photo_crop": 1.0}
 
 
 def check_flags(config):
@@ -290,6 +293,19 @@ def check_flags(config):
     if config.pool5_store_gb > 0 and not config.freeze_conv:
         sys.exit("--pool5_store_gb needs --freeze_conv True: the store keeps the conv base's pool5 for every photo, which is a "
                  "constant of the run only while the conv base does not train")
+    if not isinstance(config.photo_flip, bool):
+        sys.exit(f"--photo_flip takes True or False, got {config.photo_flip!r}")
+    if isinstance(config.photo_crop, bool) or not isinstance(config.photo_crop, (int, float)) or not 0.08 <= config.photo_crop <= 1:
+        sys.exit(f"--photo_crop takes the smallest share of the image a random crop keeps, 0.08 <= s <= 1 (1: no crop), got "
+                 f"{config.photo_crop!r}")
+    if (config.photo_flip or config.photo_crop < 1) and not config.review_net_only:      # UMPR-R has no photos: accepted, ignored
+        for option in ("feature_store_gb", "pool5_store_gb"):
+            if getattr(config, option) > 0:
+                sys.exit(f"--photo_flip / --photo_crop and --{option} > 0 exclude each other: a stored feature would freeze one "
+                         "draw of the augmentation (augment with --photo_store_gb, which keeps the plain photo)")
+        if config.data_dir == "synthetic":
+            sys.exit("--photo_flip / --photo_crop need decoded photos (a --data_dir with train.csv and photos/): the synthetic "
+                     "batches carry float photo tensors, which are not augmented")
 
 
 def _main():

@@ -108,6 +108,7 @@ SIGNATURES = {
     "umpr_photo_resize_u8": ("pzpiiipp", "i"),
     "umpr_photo_store_slot_bytes": ("ii", "z"),
     "umpr_photo_fetch_u8": ("pzpppiiiplpp", "i"),
+    "umpr_photo_fetch_augment_u8": ("pzppppiiiplplpppp", "i"),
     "umpr_feature_fetch_f32": ("pipppiiplpp", "i"),
     "umpr_review_collate": ("pplppppppplpiiiiilpppp", "i"),
     "umpr_bce_head_fwd": ("plpppiipppzp", "i"),

@@ -1061,6 +1061,15 @@ class UMPR(nn.Module):
                                  "base only (the classifier trains) - choose one")
             self.visual_net.vgg16[0].features.requires_grad_(False)
             self.visual_net.vgg16[0].frozen_conv = True
+        # not in the reference: `--photo_flip True` / `--photo_crop s` (s < 1) augment the item photos of every training forward -
+        # a random resized crop that keeps at least the share s of the image, a fair horizontal flip - on the device, at the
+        # fetch (photos.PhotoAugment).  Off: no submodule is registered.  Nothing to augment in UMPR-R.
+        photo_flip, photo_crop = bool(getattr(config, "photo_flip", False)), float(getattr(config, "photo_crop", 1.0))
+        if (photo_flip or photo_crop < 1.0) and not config.review_net_only:
+            from .photos import PhotoAugment
+            self.photo_augment = PhotoAugment(flip=photo_flip, min_area=photo_crop)
+        else:
+            self.photo_augment = None
         self.last_loss_terms = None
         # Parameters whose backward node can write the gradient straight into the optimiser's arena (_grad_targets):
         # everything in the review / control nets (GRU weights accumulate in place across their uses) and, set by VGG16
@@ -1256,7 +1265,15 @@ class UMPR(nn.Module):
                                                   for v in (user_reviews, item_reviews, ui_reviews)]
         # a batch collated against a photos.FeatureStore (frozen VGG): its photos are never materialised, see below
         feature_store = self._feature_store(photos) if not self.review_net_only else None
-        if feature_store is None:
+        if self.photo_augment is not None and self.training and torch.is_grad_enabled():
+            # a training forward: a fresh crop / flip of every photo (evaluation, no_grad and validation fetch the plain photos)
+            from .photos import RawPhotos
+            if feature_store is not None or not isinstance(photos, RawPhotos):
+                raise RuntimeError("photo_flip / photo_crop augment the resized uint8 photos on the device: the batch must carry "
+                                   "them as a photos.RawPhotos (batch_loader(resize_on_gpu=True)) collated against no feature or "
+                                   f"pool5 store, got {'a stored feature batch' if feature_store is not None else type(photos).__name__}")
+            photos = self.photo_augment(photos, device, non_blocking=True)
+        elif feature_store is None:
             photos = photos.to(device, non_blocking=True)
         labels = _c(labels.to(device, non_blocking=True).float())
         emb = self.embedding.weight

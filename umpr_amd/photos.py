@@ -11,6 +11,10 @@ the host form.
 decoded once per run, every later use ships no pixels and is a table lookup on the device (umpr_photo_fetch_u8), still
 bit-identical.  No eviction: once the slots are used up, further photos are decoded every time.
 
+``PhotoAugment`` (off unless asked for) draws a random crop window and a flip per photo of a training batch and fetches the photos
+augmented (umpr_photo_fetch_augment_u8): the window of the resized uint8 image - a store slot, or a scratch slot - resized back
+with the same integer resize, bit-identical to doing so on the host.  A store slot always holds the plain image.
+
 ``FeatureStore`` (off unless asked for, frozen VGG only) keeps what the VGG makes of a photo instead: 1000 floats, 4 000 B against
 the photo's 150 528 B.  A resident photo is then neither decoded nor resized nor run through the VGG: ``features`` resizes only the
 photos the store lacks, runs the VGG once on those, and one kernel (umpr_feature_fetch_f32) builds the dense feature tensor the
@@ -324,6 +328,152 @@ class PhotoStore(PhotoTable):
     def __repr__(self):
         return (f"PhotoStore({self.size[0]}x{self.size[1]}, {self.used}/{self.slots} slots of {self.slot_bytes} B on "
                 f"{self.device}, {len(self.index.ids)} photos registered)")
+
+
+def tap_tables(size):
+    """(xt int32 [dw][4*dw], yt int32 [dh][4*dh]) for umpr_photo_fetch_augment_u8: row s-1 holds the concatenated
+    data._column_taps(dw, s) / data._row_taps(dh, s), the taps resize_bilinear_u8 uses for a source of extent s."""
+    dw, dh = size
+    xt = np.stack([np.concatenate(_column_taps(dw, s)) for s in range(1, dw + 1)]).astype(np.int32)
+    yt = np.stack([np.concatenate(_row_taps(dh, s)) for s in range(1, dh + 1)]).astype(np.int32)
+    return xt, yt
+
+
+def _mix64(x):
+    """splitmix64's output function on a uint64 array (wrapping arithmetic)."""
+    with np.errstate(over="ignore"):
+        x = x + np.uint64(0x9E3779B97F4A7C15)
+        x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return x ^ (x >> np.uint64(31))
+
+
+class PhotoAugment(torch.nn.Module):
+    """Random resized crop and horizontal flip of a batch's photos at the fetch (umpr_photo_fetch_augment_u8): the photo's resized
+    uint8 image - its PhotoStore slot, or a scratch slot - is cropped to a window, resized back with the integer resize the loader
+    uses and mirrored, on the device.  `draw` is torchvision's RandomResizedCrop on the dh x dw image, scale (min_area, 1), ratio
+    (3/4, 4/3); `min_area` = 1 keeps the whole image, `flip` adds a fair coin.  Counter-based randomness: every number is a hash of
+    (seed, call, photo index in the batch, draw number), seed = torch.initial_seed() and the data-parallel rank, so no global
+    generator is touched and the draws do not depend on the store, the hits or the loader workers.  `_calls` counts the augmented
+    fetches and travels in a checkpoint's rng_calls.  No parameters, no buffers: the scratch slots and the tap tables are plain
+    attributes, made on first use and kept."""
+
+    TRIES = 10
+    RATIO = (3.0 / 4.0, 4.0 / 3.0)
+
+    def __init__(self, flip=False, min_area=1.0, size=(224, 224)):
+        super().__init__()
+        if not 0.0 < float(min_area) <= 1.0:
+            raise ValueError(f"PhotoAugment: min_area must lie in (0, 1], got {min_area!r}")
+        self.flip, self.min_area = bool(flip), float(min_area)
+        self.size = (int(size[0]), int(size[1]))       # (dw, dh)
+        self._calls = 0
+        self._tables = self._scratch = None
+
+    def extra_repr(self):
+        return f"flip={self.flip}, min_area={self.min_area}, size={self.size}"
+
+    @staticmethod
+    def seed():
+        from . import parallel
+        rank = torch.distributed.get_rank() if parallel.active() else 0
+        return (torch.initial_seed() * 1000003 + rank) & 0xFFFFFFFFFFFFFFFF
+
+    def _uniform(self, key, k):
+        """Draw number k of every photo: float64 in [0, 1) from the top 53 bits of the hash."""
+        return (_mix64(key + np.uint64(k)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+    def draw(self, call, n):
+        """int32 [n][5] = (x0, y0, cw, ch, flip) of augmented fetch number `call` for photos 0 .. n-1."""
+        dw, dh = self.size
+        index = np.arange(n, dtype=np.uint64)
+        key = _mix64(_mix64(_mix64(np.full(n, self.seed(), dtype=np.uint64)) + np.uint64(int(call) & 0xFFFFFFFFFFFFFFFF)) + index)
+        out = np.zeros((n, 5), dtype=np.int32)
+        out[:, 2], out[:, 3] = dw, dh
+        if self.min_area < 1.0:
+            # the fall-back after TRIES failures: the largest centred window whose ratio lies in RATIO
+            if dw / dh < self.RATIO[0]:
+                cw, ch = dw, min(dh, int(np.rint(dw / self.RATIO[0])))
+            elif dw / dh > self.RATIO[1]:
+                cw, ch = min(dw, int(np.rint(dh * self.RATIO[1]))), dh
+            else:
+                cw, ch = dw, dh
+            cw, ch = np.full(n, cw, dtype=np.int64), np.full(n, ch, dtype=np.int64)
+            x0, y0 = (dw - cw) // 2, (dh - ch) // 2
+            found = np.zeros(n, dtype=bool)
+            lo, hi = np.log(self.RATIO[0]), np.log(self.RATIO[1])
+            for t in range(self.TRIES):
+                area = dh * dw * (self.min_area + (1.0 - self.min_area) * self._uniform(key, 2 * t))
+                ratio = np.exp(lo + (hi - lo) * self._uniform(key, 2 * t + 1))
+                w = np.rint(np.sqrt(area * ratio)).astype(np.int64)
+                h = np.rint(np.sqrt(area / ratio)).astype(np.int64)
+                take = ~found & (w >= 1) & (w <= dw) & (h >= 1) & (h <= dh)
+                cw, ch = np.where(take, w, cw), np.where(take, h, ch)
+                found |= take
+            # the offset: uniform over the positions at which the window fits
+            px = np.minimum((self._uniform(key, 2 * self.TRIES) * (dw - cw + 1)).astype(np.int64), dw - cw)
+            py = np.minimum((self._uniform(key, 2 * self.TRIES + 1) * (dh - ch + 1)).astype(np.int64), dh - ch)
+            out[:, 0], out[:, 1] = np.where(found, px, x0), np.where(found, py, y0)
+            out[:, 2], out[:, 3] = cw, ch
+        if self.flip:
+            out[:, 4] = _mix64(key + np.uint64(2 * self.TRIES + 2)) >> np.uint64(63)
+        return out
+
+    def _device_state(self, device, need, slot_bytes):
+        """The tap tables on `device` and `need` scratch slots (grown to the largest count seen, at most a batch's photos)."""
+        if self._tables is None or self._tables[0].device != device:
+            self._tables = tuple(torch.from_numpy(t).to(device) for t in tap_tables(self.size))
+            self._scratch = None
+        if need and (self._scratch is None or self._scratch.numel() < need * slot_bytes):
+            self._scratch = torch.empty(need * slot_bytes, dtype=torch.uint8, device=device)
+        return self._tables[0], self._tables[1], self._scratch
+
+    def forward(self, raw, device, non_blocking=False):
+        """RawPhotos.to(device) with a fresh draw per photo, on the current stream: float32 [B, V, P, 3, dh, dw].  With a
+        PhotoStore the plan, the fills and the bookkeeping are PhotoStore.fetch's: a slot receives the plain image."""
+        from ._lib import UmprHipError, lib
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("PhotoAugment runs on an MI355X only (no CPU path)")
+        if raw.size != self.size:
+            raise UmprHipError(f"PhotoAugment was built for {self.size} photos, the batch is {raw.size}")
+        dw, dh = raw.size
+        n = int(np.prod(raw.geometry))
+        if raw.data.dtype != torch.uint8 or raw.data.dim() != 1 or raw.data.numel() < n * DESC.itemsize:
+            raise UmprHipError(f"RawPhotos: buffer of {raw.data.numel()} bytes cannot hold the {n} photo descriptors")
+        store = PhotoStore.find(raw.store_key) if raw.store_key is not None else None
+        if store is None and raw.store_key is not None and bool(raw.hits.any()):
+            raise UmprHipError(f"RawPhotos: {int(raw.hits.sum())} photos were left to photo store {raw.store_key}, which is not "
+                               f"registered in this process")
+        if store is not None:
+            if device.index is not None and device != store.device:
+                raise UmprHipError(f"PhotoStore on {store.device} asked for photos on {device}")
+            device = store.device
+            src, dst, full = store.plan(raw)
+        else:
+            device = torch.device("cuda", torch.cuda.current_device() if device.index is None else device.index)
+            src = dst = np.full(n, -1, dtype=np.int32)
+        self._calls += 1
+        crop = np.ascontiguousarray(self.draw(self._calls, n))
+        with torch.cuda.device(device):
+            out = torch.empty(raw.shape, dtype=torch.float32, device=device)
+            if n == 0:
+                return out
+            slot_bytes = lib().size("umpr_photo_store_slot_bytes", dh, dw)
+            need = int(((src < 0) & (dst < 0) & (raw.descriptors()["rows"] > 0)).sum())
+            xt, yt, scratch = self._device_state(device, need, slot_bytes)
+            stream = torch.cuda.current_stream(device)
+            if store is not None and store._insert_event is not None and stream != store._insert_stream:
+                stream.wait_event(store._insert_event)     # slots filled on another stream
+            packed = raw.data.to(device, non_blocking=non_blocking)
+            lib().call("umpr_photo_fetch_augment_u8", packed, packed.numel(), raw.data, src.ctypes.data, dst.ctypes.data,
+                       crop.ctypes.data, n, dh, dw, store.buffer if store is not None else None, store.slots if store is not None else 0,
+                       scratch, need, xt, yt, out, stream.cuda_stream)
+            if store is not None and store.commit(raw, src, dst, full):   # as PhotoStore.fetch: resident once the fill is enqueued
+                store._insert_event = torch.cuda.Event()
+                store._insert_event.record(stream)
+                store._insert_stream = stream
+        return out
 
 
 def vgg_fingerprint(vgg):

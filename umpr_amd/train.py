@@ -140,7 +140,9 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     the raw weights: no average exists yet.  `config.lr_scale` / `config.wd_scale` ("prefix=multiplier,..."),
     `config.decoupled_decay` and `config.warmup_steps` give modules their own learning rate and decay, AdamW's decoupled decay
     and a linear warm-up (FusedAdam(lr_scales=, wd_scales=, decoupled_decay=, warmup_steps=)); each is passed on only when it is
-    set, and the log then lists the multipliers per prefix and the segments per group."""
+    set, and the log then lists the multipliers per prefix and the segments per group.  A model built with `config.photo_flip` /
+    `config.photo_crop` augments its photos in every train_step (model.UMPR.photo_augment; validation sees plain photos): one log
+    line says so."""
     accum = int(getattr(config, "accum_steps", 1))
     if accum > 1 and parallel.active():
         raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
@@ -169,6 +171,11 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     if averaged:
         log(f'Moving average of the weights: decay {ema_decay}, {opt.ema_bytes() / 1e6:.0f} MB more; validation and the '
             f'checkpoint choice run on the averaged weights')
+    augment = getattr(model, "photo_augment", None)
+    if augment is not None:
+        log('Photo augmentation at the fetch, training forwards only: '
+            + (f'random crop of {augment.min_area:.0%} to 100% of the image, sides 3:4 to 4:3' if augment.min_area < 1 else 'no crop')
+            + ('; horizontal flip with probability 1/2' if augment.flip else '; no flip'))
     reducer = parallel.GradReducer(opt) if parallel.active() else None
     best_loss, batch_counter, first_epoch, skip, saved = 100, 0, 0, 0, False
     valid_every = int(getattr(config, "valid_every", 500))   # the reference hard-codes 500 (main.py:43)
