@@ -15,6 +15,8 @@ import torch
 import torch.nn.functional as F
 
 import classifier_reference as CR
+import vgg_bf16_decisions as VB
+import vgg_decisions as V
 from conftest import ROOT, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -76,9 +78,12 @@ def q(t):
 
 
 def test_layout_roundtrip_and_pads(L, dev):
-    """fp32 -> CB8-PF -> fp32 is the bf16 rounding of the input; every pad / guard pixel of the tensor is zero."""
+    """fp32 -> CB8-PF -> fp32 is the bf16 rounding of the input; every pad / guard pixel of the tensor is zero.  The device bytes
+    equal the Python encoding (vgg_bf16_decisions.encode: the layout written down from its description) of q(x) bit for bit - lanes
+    c >= C of the last plane and everything outside the real pixels zero, in a buffer that starts as 0xFF bytes - and the
+    converter's read-back equals the Python decoding.  C = 3 (the image), 12 and 70 are off the 8-lane plane."""
     g = torch.Generator().manual_seed(1)
-    for shape in [(2, 64, 14, 14), (3, 8, 28, 28), (1, 24, 56, 56)]:
+    for shape in [(2, 64, 14, 14), (3, 8, 28, 28), (1, 24, 56, 56), (2, 3, 14, 14), (1, 12, 28, 28), (3, 70, 6, 10)]:
         x = torch.randn(shape, generator=g)
         y = to_cb8(L, x, dev)
         back = from_cb8(L, y, shape, dev)
@@ -89,6 +94,10 @@ def test_layout_roundtrip_and_pads(L, dev):
         assert torch.isfinite(img).all()
         total = float(img.abs().sum())
         assert abs(total - float(q(x).abs().sum())) <= 1e-3 * total              # nothing but the real pixels is non-zero
+        ps = VB.plane_stride(y.numel(), C)
+        assert VB.nonzero_outside(y, N, C, H, W) == 0, shape
+        assert torch.equal(y.cpu(), VB.encode(q(x), ps)), shape
+        assert torch.equal(VB.decode(y, N, C, H, W), back.double()), shape
 
 
 # the 12 bf16 conv layers of VGG16 (the first, 3 -> 64, runs the fp32 first-layer kernel) + batches that make tiles
@@ -129,7 +138,7 @@ def test_conv3x3_bf16(L, dev, N, Cin, Cout, HW):
     # tensor that is not a real pixel
     img = yd.view(torch.bfloat16).float()
     assert torch.isfinite(img).all()
-    assert abs(float(img.abs().sum()) - float(y.abs().sum())) <= 2e-3 * float(y.abs().sum()) + 1e-3
+    assert VB.nonzero_outside(yd, N, Cout, HW, HW) == 0
     # data gradient, plain and with the ReLU mask of the layer below fused
     gzd = to_cb8(L, gz_q, dev)
     nbx = L.size("umpr_bf16_tensor_bytes", N, Cin, HW, HW)
@@ -140,11 +149,13 @@ def test_conv3x3_bf16(L, dev, N, Cin, Cout, HW):
     tol = 2.0 ** -8 * xq.grad.abs() + 1e-3 * float(xq.grad.abs().max())
     log(f"bf16 conv dgrad {N},{Cin},{Cout},{HW}: relL2 {rel_l2(dx, xq.grad):.2e} max|err| {float(err.max()):.2e} bad {int((err > tol).sum())}")
     assert int((err > tol).sum()) == 0
+    assert VB.nonzero_outside(dxd, N, Cin, HW, HW) == 0, "plain data gradient: non-zero pad / guard elements"
     mask_src = torch.randn(N, Cin, HW, HW, generator=g)
     md = to_cb8(L, mask_src, dev)
     L.call("umpr_conv3x3_bf16_bwd_data", gzd, wd, md, dxd, N, Cin, HW, HW, Cout, ws, wsb, st())
     dxm = from_cb8(L, dxd, (N, Cin, HW, HW), dev)
     assert torch.equal(dxm, dx * (q(mask_src) > 0)), "masked data gradient differs from mask x plain"
+    assert VB.nonzero_outside(dxd, N, Cin, HW, HW) == 0, "masked data gradient: non-zero pad / guard elements"
     # weight / bias gradient: fp32 outputs, bf16 products are exact in fp32 - only the summation order differs
     dw = torch.full(w.shape, float("nan"), device=dev)
     db = torch.full(b.shape, float("nan"), device=dev)
@@ -156,25 +167,53 @@ def test_conv3x3_bf16(L, dev, N, Cin, Cout, HW):
     assert ew <= 1e-4 * sw + 1e-6 and eb <= 1e-4 * sb + 1e-5
 
 
-def test_maxpool_bf16(L, dev):
-    g = torch.Generator().manual_seed(5)
-    N, C, H, W = 3, 16, 28, 28
-    x = q(torch.relu(torch.randn(N, C, H, W, generator=g) + 0.3)).requires_grad_(True)
+def _pool_input(N, C, H, W, seed):
+    """bf16-exact values on a quarter grid (ties everywhere); by window index mod 7: 0 an all-zero window, 1 a window whose
+    maximum is negative, 2 four equal positive values, 3 a positive maximum shared by elements (0,1) and (1,0)"""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.round(torch.randn(N, C, H, W, generator=g) * 4) / 4 + 0.0
+    win = x.reshape(N, C, H // 2, 2, W // 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(-1, 4).clone()
+    kind = torch.arange(win.shape[0]) % 7
+    win[kind == 0] = 0.0
+    win[kind == 1] = -win[kind == 1].abs() - 0.25
+    win[kind == 2] = 1.5
+    win[kind == 3] = torch.minimum(win[kind == 3], torch.tensor(3.0)) * torch.tensor([1.0, 0.0, 0.0, 1.0]) \
+        + torch.tensor([0.0, 4.0, 4.0, 0.0])
+    x = win.reshape(N, C, H // 2, W // 2, 2, 2).permute(0, 1, 2, 4, 3, 5).reshape(N, C, H, W).contiguous()
+    assert torch.equal(q(x), x)
+    return x
+
+
+# the five pool shapes of the network at N = 2, the shape this test always ran, and the smallest the entry point accepts
+@pytest.mark.parametrize("N,C,H,W", [(3, 16, 28, 28), (2, 64, 224, 224), (2, 128, 112, 112), (2, 256, 56, 56), (2, 512, 28, 28),
+                                     (2, 512, 14, 14), (1, 8, 2, 2), (3, 16, 4, 6)])
+def test_maxpool_bf16(L, dev, N, C, H, W):
+    """Forward equal to F.max_pool2d, backward equal to vgg_decisions.pool_backward (the gradient goes to the window's FIRST
+    maximum, and nowhere if that maximum is not > 0), both exactly, on positive ties, all-zero windows and windows with a negative
+    maximum; y and gx start as 0xFF bytes and afterwards every element that is not a real pixel - lead, tail, pad column, zero
+    rows - is exactly zero."""
+    x = _pool_input(N, C, H, W, 5 + C + H)
+    g = torch.Generator().manual_seed(6)
     y_ref = F.max_pool2d(x, 2, 2)
     gy = q(torch.randn(y_ref.shape, generator=g))
-    y_ref.backward(gy)
-    xd = to_cb8(L, x.detach(), dev)
+    gx_ref = V.pool_backward(x.double(), gy.double())
+    xd = to_cb8(L, x, dev)
     yd = torch.full((L.size("umpr_bf16_tensor_bytes", N, C, H // 2, W // 2),), 0xFF, dtype=torch.uint8, device=dev)
     L.call("umpr_maxpool2_bf16_fwd", xd, yd, N, C, H, W, st())
-    assert torch.equal(from_cb8(L, yd, (N, C, H // 2, W // 2), dev), y_ref.detach())
+    assert torch.equal(from_cb8(L, yd, (N, C, H // 2, W // 2), dev), y_ref)
+    assert VB.nonzero_outside(yd, N, C, H // 2, W // 2) == 0
     gyd = to_cb8(L, gy, dev)
     gxd = torch.full((L.size("umpr_bf16_tensor_bytes", N, C, H, W),), 0xFF, dtype=torch.uint8, device=dev)
     L.call("umpr_maxpool2_bf16_bwd_relu", xd, gyd, gxd, N, C, H, W, st())
     gx = from_cb8(L, gxd, (N, C, H, W), dev)
-    # ties (several equal maxima in a window, likely among the ReLU zeros) route to the FIRST maximum on both sides only if
-    # torch does the same; zeros never receive gradient through the fused ReLU mask, so compare where x > 0
-    assert torch.equal(gx, x.grad * (x.detach() > 0))
+    assert torch.equal(gx.double(), gx_ref)
+    # and torch's own backward, as this test always compared: the same tie rule; the fused ReLU mask keeps x > 0 only
+    xa = x.clone().requires_grad_(True)
+    F.max_pool2d(xa, 2, 2).backward(gy)
+    assert torch.equal(gx, xa.grad * (x > 0))
     assert torch.isfinite(gxd.view(torch.bfloat16).float()).all()
+    assert VB.nonzero_outside(gxd, N, C, H, W) == 0
+    assert torch.equal(VB.decode(gxd, N, C, H, W), gx_ref)
 
 
 @pytest.mark.parametrize("M,N,K,ta,tb,ws", [(300, 384, 300, 0, 1, 0), (1000, 128, 128, 0, 0, 0), (384, 300, 5000, 1, 0, 1),
