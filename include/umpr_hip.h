@@ -69,6 +69,17 @@ long umpr_debug_wino_fix_count(void);
  * Pure host arithmetic: makes no HIP call, runs without a GPU. */
 int umpr_debug_conv3x3_plan(int pass, int N, int Cin, int Cout, int H, int W, int inference, size_t* ws_bytes, size_t* v_bytes);
 
+/* Test aid: the gradients of one conv layer that a 2x2 max-pool follows, on the Winograd kernels whatever the plan says for the
+ * shape (H, W even; f4 = 1: the 4x4 tile, H and W multiples of 4 or, data gradient only, any even size; f4 = 0: the 2x2 tile,
+ * weight gradient only).  y [N][Cout][H][W] is the layer's output, g_pooled [N][Cout][H/2][W/2] the gradient of the pooled map.
+ * fold = 1: the gradient readers form the un-pooled gradient themselves (what umpr_vgg16_features_bwd does for pools 2-5);
+ * fold = 0: umpr_maxpool2_bwd_relu writes it to `unpooled` [N][Cout][H][W] first and the same kernels read that.
+ * dx [N][Cin][H][W] (NULL: no data gradient, else f4 must be 1), dw [Cout][Cin][3][3] + db [Cout] (dw NULL: no weight gradient;
+ * x [N][Cin][H][W] is the layer's input).  ws: scratch of ws_bytes; the call fails if it is too small. */
+int umpr_debug_wino_pool_fold(const float* y, const float* g_pooled, const float* w, const float* x, float* unpooled, float* dx,
+                              float* dw, float* db, int N, int Cin, int Cout, int H, int W, int f4, int fold, float* ws,
+                              size_t ws_bytes, void* stream);
+
 /* ---- K1-K3: embedding lookup + bidirectional packed GRU + the reference's double un-sort ---------------------
  * Replaces nn.Embedding (model.py:262-264) + ImprovedRnn.forward (model.py:12-21) for one review tensor.
  * ids [N*L] int64; emb [vocab][E]; GRU weights in nn.GRU layout (gate order r,z,n): w_ih [192][E], w_hh [192][64],

@@ -5,7 +5,8 @@ the GPU must not fork+exec another GPU program on this pool).  Runs, one after t
   * tools/check_exchange_world1.py (gradient exchange on the RCCL backend at world size 1),
   * ten model-level oracle comparisons of the text path with UMPR_POISON_WS=1 (workspaces pre-filled with NaN bytes),
   * the VGG feature entry points at exact workspace size with UMPR_WGRAD_STREAM=0 (read when the library loads); the run leaves
-    its gradient digests beside the logs for tests/test_gpu_workspace_layouts.py to compare with the side-stream run.
+    its gradient digests beside the logs for tests/test_gpu_workspace_layouts.py to compare with the side-stream run,
+  * the VGG feature backward with UMPR_POOL_FOLD=0 (read when the library loads), likewise for tests/test_gpu_pool_fold.py.
 This launcher itself never touches the GPU.  Each job writes gpurun_out/<name>.log; the exit codes go to
 gpurun_out/gpu_children.rc as `<name> <rc>` lines."""
 import os
@@ -32,6 +33,11 @@ def main():
     jobs.append(("wgrad_stream0_check", dict(env, UMPR_WGRAD_STREAM="0"),
                  [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_workspace_layouts.py"), "-q", "-x", "-m", "gpu",
                   "-p", "no:cacheprovider", "-k", "test_vgg_features_at_exact_workspace_size"]))
+    # UMPR_POOL_FOLD=0 (read when the library loads): the VGG backward with the stand-alone pool backward of pools 2-5; the run
+    # leaves its gradient digests beside the logs for tests/test_gpu_pool_fold.py to compare with the folded run
+    jobs.append(("pool_fold0_check", dict(env, UMPR_POOL_FOLD="0"),
+                 [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_pool_fold.py"), "-q", "-x", "-m", "gpu",
+                  "-p", "no:cacheprovider", "-k", "test_whole_backward_runs"]))
     with open(os.path.join(OUT, "gpu_children.rc"), "w") as rcf:
         for name, e, cmd in jobs:
             with open(os.path.join(OUT, name + ".log"), "w") as f:

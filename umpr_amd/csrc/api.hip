@@ -132,6 +132,28 @@ int umpr_debug_conv3x3_plan(int pass, int N, int Cin, int Cout, int H_, int W, i
   if (v_bytes) *v_bytes = p.v_floats * sizeof(float);
   return p.algo;
 }
+int umpr_debug_wino_pool_fold(const float* y, const float* g_pooled, const float* w, const float* x, float* unpooled, float* dx,
+                              float* dw, float* db, int N, int Cin, int Cout, int H_, int W, int f4, int fold, float* ws,
+                              size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H_ > 0 && W > 0 && (H_ % 2) == 0 && (W % 2) == 0 && y && g_pooled && ws,
+               "debug_wino_pool_fold: bad arguments");
+  UMPR_REQUIRE(fold || unpooled, "debug_wino_pool_fold: the un-folded run needs the buffer for the un-pooled gradient");
+  UMPR_REQUIRE(!dx || (f4 && w), "debug_wino_pool_fold: the data gradient runs on the 4x4 tile and needs the weights");
+  UMPR_REQUIRE(!dw || (x && (!f4 || ((H_ % 4) == 0 && (W % 4) == 0))), "debug_wino_pool_fold: the weight gradient on the 4x4 tile has no edge tiles");
+  hipStream_t s = S(stream);
+  ConvHints h;
+  const float* g = g_pooled;
+  if (fold) { h.pooled_dy = true; h.pool_y = y; }
+  else {
+    if (int rc = umpr_maxpool2_bwd_relu_impl(y, g_pooled, unpooled, (long)N * Cout, H_, W, s)) return rc;
+    g = unpooled;
+  }
+  if (dx)
+    if (int rc = umpr_wino_conv3x3(g, w, 1, nullptr, nullptr, dx, N, Cin, Cout, H_, W, 0, ws, ws_bytes / sizeof(float), true, h, s)) return rc;
+  if (dw)
+    if (int rc = umpr_wino_wgrad(g, x, dw, db, N, Cin, Cout, H_, W, 0, ws, ws_bytes / sizeof(float), f4 != 0, h, s)) return rc;
+  return 0;
+}
 
 // ------------------------------------------------------------------------------------------------ GRU
 // split-K slabs of the dW_ih product ([384][Ep] each, two slabs per unit): 256 units = up to 128 splits of the [384 x Ep] x N*L
@@ -758,8 +780,8 @@ struct WgradSchedule {
   void wgrad_may_start(int ci) {   // `s` has enqueued the output gradient of layer ci
     if (side) { (void)hipEventRecord(g_wside.ready[ci], s); (void)hipStreamWaitEvent(sw, g_wside.ready[ci], 0); }
   }
-  void wgrad_enqueued(int ci, int slot) {   // the wgrad of layer ci is on `sw` and reads `slot`
-    if (side) { (void)hipEventRecord(g_wside.done[ci], sw); reader[slot] = ci; }
+  void wgrad_enqueued(int ci, int slot) {   // the wgrad of layer ci is on `sw` and reads `slot` (-1: the caller's own buffer)
+    if (side) { (void)hipEventRecord(g_wside.done[ci], sw); if (slot >= 0) reader[slot] = ci; }
   }
   void finish() {   // `s` owns the results again: every weight gradient is complete behind this wait
     if (side) (void)hipStreamWaitEvent(s, g_wside.done[0], 0);
@@ -785,18 +807,48 @@ int umpr_vgg16_features_bwd(const float* images, const float* const* params, int
   WgradSchedule sched(s);
   const float* g = d_pool5; int gslot = -1;   // gslot: slot index holding g (-1: the caller's d_pool5)
   int ci = 12;
+  // Pool backward, blocks 1-4 (pools 2-5): both readers of the un-pooled gradient of the block's last convolution - the input
+  // transform of its data gradient and the dy transform of its weight gradient - form it themselves from the conv output and
+  // the POOLED gradient g (ConvHints::pooled_dy), so no slot is claimed for it and g stays where it is: the caller's d_pool5
+  // (gslot -1, safe behind finish()) or the slot the previous block's last data gradient wrote.  Block 0 (conv1_2: direct
+  // kernels), and any block whose plans have no such reader (umpr_conv3x3_pool_fold_ok), run the stand-alone kernel into a slot.
+  // Slot rotation, default plans (c = claim(): it waits for the side-stream reader the slot still has; every claim writes the slot
+  // after the one its kernel reads, and a slot is rewritten three claims after it was written):
+  //   layer 12: wgrad reads d_pool5          | dgrad reads d_pool5, c -> slot 0
+  //   layer 11: wgrad reads slot 0           | dgrad reads slot 0,  c -> slot 1
+  //   layer 10: wgrad reads slot 1           | dgrad reads slot 1,  c -> slot 2                       (slot 2 = pooled, block 3)
+  //   layer  9: wgrad reads slot 2 (pooled)  | dgrad reads slot 2,  c -> slot 0 (waits for wgrad 11)
+  //   layer  8: wgrad reads slot 0           | dgrad reads slot 0,  c -> slot 1 (waits for wgrad 10)
+  //   layer  7: wgrad reads slot 1           | dgrad reads slot 1,  c -> slot 2 (waits for wgrad 9)   (slot 2 = pooled, block 2)
+  //   layer  6: wgrad reads slot 2 (pooled)  | dgrad reads slot 2,  c -> slot 0 (waits for wgrad 8)
+  //   layer  5: wgrad reads slot 0           | dgrad reads slot 0,  c -> slot 1 (waits for wgrad 7)
+  //   layer  4: wgrad reads slot 1           | dgrad reads slot 1,  c -> slot 2 (waits for wgrad 6)   (slot 2 = pooled, block 1)
+  //   layer  3: wgrad reads slot 2 (pooled)  | dgrad reads slot 2,  c -> slot 0 (waits for wgrad 5)
+  //   layer  2: wgrad reads slot 0           | dgrad reads slot 0,  c -> slot 1 (waits for wgrad 4)   (slot 1 = pooled, block 0)
+  //   pool 1 backward reads slot 1,                                 c -> slot 2 (waits for wgrad 3)
+  //   layer  1: wgrad reads slot 2           | dgrad reads slot 2,  c -> slot 0 (waits for wgrad 2)
+  //   layer  0: wgrad reads slot 0
+  // A slot's side-stream reader is always named in reader[] before the claim that rewrites it, because wgrad_enqueued names the
+  // slot of the g the weight gradient was given - pooled or not.
   for (int b = 4; b >= 0; --b) {
     const int hw = L.conv_hw[ci];
-    // pool backward + ReLU mask of the conv output feeding it -> gradient w.r.t. the conv pre-activation
-    int cs = sched.claim();
-    if (int rc = umpr_maxpool2_bwd_relu_impl(acts + L.conv_off[ci], g, W.slot[cs], (long)n * kBlockCh[b], hw, hw, s)) return rc;
-    g = W.slot[cs]; gslot = cs;
+    const float* pool_y = acts + L.conv_off[ci];   // the conv output that fed the pool
+    const bool fold = b >= 1 && umpr_conv3x3_pool_fold_ok(n, L.conv_cin[ci], L.conv_cout[ci], hw, hw);
+    int cs;
+    if (!fold) {
+      // pool backward + ReLU mask of the conv output feeding it -> gradient w.r.t. the conv pre-activation
+      cs = sched.claim();
+      if (int rc = umpr_maxpool2_bwd_relu_impl(pool_y, g, W.slot[cs], (long)n * kBlockCh[b], hw, hw, s)) return rc;
+      g = W.slot[cs]; gslot = cs;
+    }
     for (int j = kConvPerBlock[b] - 1; j >= 0; --j, --ci) {
       const int cin = L.conv_cin[ci], cout = L.conv_cout[ci];
       const float* xin = ci == 0 ? images : (j == 0 ? acts + L.pool_off[b - 1] : acts + L.conv_off[ci - 1]);
+      const bool pooled = fold && j == kConvPerBlock[b] - 1;   // g is the pooled gradient
       sched.wgrad_may_start(ci);
       ConvHints hints;   // the slot the training forward of this layer wrote; the call fails unless its plan reads exactly that
       if (L.v_floats[ci]) { hints.v_slot = const_cast<float*>(acts) + L.v_off[ci]; hints.v_slot_floats = L.v_floats[ci]; }
+      if (pooled) { hints.pooled_dy = true; hints.pool_y = pool_y; }
       if (int rcw = umpr_conv3x3_wgrad(g, xin, grads[2 * ci], grads[2 * ci + 1], n, cin, cout, hw, hw, 0, W.scratch,
                                        W.scratch_bytes, hints, sched.sw))
         return rcw;
@@ -804,8 +856,10 @@ int umpr_vgg16_features_bwd(const float* images, const float* const* params, int
       if (ci == 0) break;
       // input came straight from a conv+ReLU (j > 0): mask by it; from a pool (j == 0): the pool backward masks
       const float* mask = j > 0 ? xin : nullptr;
+      ConvHints dh;
+      if (pooled) { dh.pooled_dy = true; dh.pool_y = pool_y; }
       cs = sched.claim();
-      if (int rc = umpr_conv3x3_run(g, params[2 * ci], 1, nullptr, mask, W.slot[cs], n, cin, cout, hw, hw, 0, W.wt, W.wt_floats, ConvHints(), s))
+      if (int rc = umpr_conv3x3_run(g, params[2 * ci], 1, nullptr, mask, W.slot[cs], n, cin, cout, hw, hw, 0, W.wt, W.wt_floats, dh, s))
         return rc;
       g = W.slot[cs]; gslot = cs;
     }

@@ -1311,6 +1311,17 @@ size_t umpr_conv3x3_pack_floats(int N, int Cin, int Cout, int H, int W) {
   return f > t ? f : t;
 }
 
+// Whether the two gradients of a layer that a 2x2 max-pool follows can read the POOLED gradient (ConvHints::pooled_dy): the data
+// gradient's reader is wino4_input_kernel, the weight gradient's wino4_dy_kernel (no edge tiles by its plan) or wino_dy[_pair]_kernel.
+// Any other plan (the direct kernels of conv1_2, the 2x2 tile's data gradient under UMPR_WINO_F4 = 0) has no such reader and its
+// caller runs umpr_maxpool2_bwd_relu_impl first.  UMPR_POOL_FOLD = 0: never (the sequence of kernels before the fold existed).
+bool umpr_conv3x3_pool_fold_ok(int N, int Cin, int Cout, int H, int W) {
+  static const bool on = umpr_env_on("UMPR_POOL_FOLD");
+  if (!on || (H % 2) != 0 || (W % 2) != 0) return false;
+  const ConvAlgo wg = umpr_conv3x3_plan(CONV_WGRAD, N, Cin, Cout, H, W, false).algo;
+  return umpr_conv3x3_plan(CONV_DGRAD, N, Cin, Cout, H, W, false).algo == CONV_WINO4 && (wg == CONV_WINO4 || wg == CONV_WINO2);
+}
+
 // Forward (transposed = 0):  y[N][Cout] = relu?(conv(x[N][Cin], w) + bias)
 // Data gradient (transposed = 1):  y[N][Cin] = conv^T(x[N][Cout], w) * [mask > 0]
 // w is always the parameter [Cout][Cin][3][3]; wpack: scratch of umpr_conv3x3_pack_floats(...) floats.
@@ -1330,6 +1341,9 @@ int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float
                  "conv3x3: the V slot does not fit this call (%d -> %d at %dx%d, slot %zu floats, plan %zu)", Cin, Cout, H, W,
                  hints.v_slot_floats, plan.v_floats);
   else if ((algo == CONV_WINO2 || algo == CONV_WINO4) && !fits) algo = plan.direct;   // scratch of a direct call only
+  if (hints.pooled_dy)   // only wino4_input_kernel can read a pooled gradient: the caller asked umpr_conv3x3_pool_fold_ok first
+    UMPR_REQUIRE(transposed && algo == CONV_WINO4 && hints.pool_y, "conv3x3: no reader with a pooled source for this call (%d -> %d at %dx%d)",
+                 Cin, Cout, H, W);
   if (algo == CONV_DIRECT && !wpack) algo = CONV_GENERIC;                             // a forward without scratch
   const int family = transposed ? UMPR_K_CONV_DGRAD : UMPR_K_CONV_IGEMM;   // one family for every algorithm, with the direct
   const double work = 2.0 * NP * M * C * 9;                                // conv's FLOP count
@@ -1410,6 +1424,9 @@ int umpr_conv3x3_wgrad(const float* gz, const float* x, float* dw, float* db, in
                  "conv3x3 wgrad: the V slot does not match this layer (%d -> %d at %dx%d, slot %zu floats, plan %zu)", Cin, Cout,
                  H, W, hints.v_slot_floats, plan.v_floats);
   else if ((algo == CONV_WINO2 || algo == CONV_WINO4) && !fits) algo = plan.direct;   // workspace of a direct call only
+  if (hints.pooled_dy)   // only the Winograd dy transforms can read a pooled gradient
+    UMPR_REQUIRE((algo == CONV_WINO2 || algo == CONV_WINO4) && hints.pool_y,
+                 "conv3x3 wgrad: no reader with a pooled source for this call (%d -> %d at %dx%d)", Cin, Cout, H, W);
   const double work = 2.0 * N * H * W * Cout * Cin * 9;   // one family for every algorithm, with the direct algorithm's FLOP count
   if (algo == CONV_WINO2 || algo == CONV_WINO4) {
     UmprProfScope prof(UMPR_K_CONV_WGRAD, work, s);

@@ -96,8 +96,14 @@ enum ConvAlgo { CONV_GENERIC = 0 /* gather kernel, any shape */, CONV_C3 = 1 /* 
                 CONV_DIRECT = 2 /* LDS-patch v2 kernels, VGG map widths */, CONV_WINO2 = 3, CONV_WINO4 = 4 };
 // What only the caller knows about a call.  inference: no backward pass will read this forward's decisions; pool_follows: a 2x2
 // max-pool reads this forward's output; v_slot: where a training forward on the 4x4 tile leaves its transformed input and the
-// weight gradient of the same layer reads it back (v_slot_floats must equal the plan's v_floats).
-struct ConvHints { bool inference = false, pool_follows = false; float* v_slot = nullptr; size_t v_slot_floats = 0; };
+// weight gradient of the same layer reads it back (v_slot_floats must equal the plan's v_floats).  pooled_dy + pool_y (data and
+// weight gradient of a layer a 2x2 max-pool follows): the gradient argument is the POOLED gradient [N][Cout][H/2][W/2] and pool_y
+// the layer's output [N][Cout][H][W]; the Winograd readers form the un-pooled gradient themselves, element for element what
+// umpr_maxpool2_bwd_relu_impl would have written.  Only where umpr_conv3x3_pool_fold_ok says so; the call fails otherwise.
+struct ConvHints {
+  bool inference = false, pool_follows = false; float* v_slot = nullptr; size_t v_slot_floats = 0;
+  bool pooled_dy = false; const float* pool_y = nullptr;
+};
 struct ConvPlan {
   ConvAlgo algo;
   ConvAlgo direct;    // what runs instead when the caller's scratch is too small for the planned Winograd call
@@ -107,6 +113,8 @@ struct ConvPlan {
 };
 ConvPlan umpr_conv3x3_plan(ConvPass pass, int N, int Cin, int Cout, int H, int W, bool inference);
 size_t umpr_conv3x3_pack_floats(int N, int Cin, int Cout, int H, int W);
+// UMPR_POOL_FOLD (default on) and both gradient plans of the layer have readers with a pooled source (ConvHints::pooled_dy)
+bool umpr_conv3x3_pool_fold_ok(int N, int Cin, int Cout, int H, int W);
 int umpr_conv3x3_run(const float* x, const float* w, int transposed, const float* bias, const float* mask, float* y,
                      int N, int Cin, int Cout, int H, int W, int relu, float* wpack, size_t wpack_floats,
                      const ConvHints& hints, hipStream_t s);

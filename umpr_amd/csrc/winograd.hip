@@ -23,6 +23,31 @@ constexpr int WK = 32;    // channels per GEMM stage
 constexpr int WBM = 128;  // output-channel tile
 constexpr int WBN = 128;  // tile-index tile
 
+// "Pooled source" of the gradient readers (ConvHints::pool_y): the layer's output fed a 2x2 max-pool, and the reader gets that
+// output y and the POOLED gradient instead of the un-pooled one.  It forms the four un-pooled gradients of a window (a = the
+// window's top row of y, b = its bottom row) with exactly the expression of maxpool2_bwd_relu_kernel (conv3x3.hip): the first
+// maximum in the order (0,0), (0,1), (1,0), (1,1) takes gy, and nothing does unless that maximum is > 0.
+__device__ __forceinline__ void pool_window_grad(const float2 a, const float2 b, const float gy, float2& ga, float2& gb) {
+  int arg = 0;
+  float m = a.x;
+  if (a.y > m) { m = a.y; arg = 1; }
+  if (b.x > m) { m = b.x; arg = 2; }
+  if (b.y > m) { m = b.y; arg = 3; }
+  const float g = m > 0.f ? gy : 0.f;
+  ga = make_float2(arg == 0 ? g : 0.f, arg == 1 ? g : 0.f);
+  gb = make_float2(arg == 2 ? g : 0.f, arg == 3 ? g : 0.f);
+}
+// A value formed by pool_window_grad, made as opaque to the compiler as the load it replaces.  The folded readers must round
+// like the un-folded ones, bit for bit, and hipcc contracts a * b + c into an fma (or not) by what it knows about the operands: the
+// transform that follows has to see the same thing in both instantiations - a value of unknown origin, scalar or float4 as loaded.
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ float as_loaded(float v) { asm volatile("" : "+v"(v)); return v; }
+__device__ __forceinline__ float4 as_loaded(const float4 v) {
+  f32x4_t q = {v.x, v.y, v.z, v.w};
+  asm volatile("" : "+v"(q));
+  return make_float4(q.x, q.y, q.z, q.w);
+}
+
 // U[xi][mt][s][k][m_local]  (mt = m / 128, s = c / 32, k = c % 32), zero padded in both m and c
 __global__ void wino_weights_kernel(const float* __restrict__ w, float* __restrict__ U, int M, int C, int CinW,
                                     int transposed) {
@@ -423,10 +448,15 @@ __global__ __launch_bounds__(256) void wino_absmax_kernel(const float* __restric
 // bit 2w+1 = "... a column that is not constant along y" (w = 2wy + wx; the zero padding counts as input).  If every row of the
 // patch is constant along x, horizontally adjacent outputs of the window see the same 3x3xC inputs and tie (exactly, for exactly
 // equal inputs, in exact arithmetic); likewise columns / vertical neighbours; both / diagonal.  See the pool rule of wino4_output_kernel.
-template <bool EDGE, bool PF>
+// POOL (data gradient of a layer a max-pool follows): x is the POOLED gradient [N][C][H/2][W/2] and pool_y the layer's output
+// [N][C][H][W]; d is formed window by window (pool_window_grad).  The 6x6 tile starts one pixel before a window boundary, so it
+// touches 4x4 whole windows (rows 4ty-2 .. 4ty+5 of y); H and W are even, so a window never straddles the border of the map.
+template <bool EDGE, bool PF, bool POOL = false>
 __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restrict__ x, float* __restrict__ V, int N, int C,
                                                           int Cpad, int H, int W, long Tpad, long Tw, Wino4C wc,
-                                                          unsigned int* __restrict__ zero, unsigned int* __restrict__ bits) {
+                                                          unsigned int* __restrict__ zero, unsigned int* __restrict__ bits,
+                                                          const float* __restrict__ pool_y = nullptr) {
+  static_assert(!(PF && POOL), "the tie bits belong to a forward, the pooled source to a data gradient");
   if (zero && blockIdx.x == 0 && threadIdx.x == 0) *zero = 0u;   // the fix-up list counter of this pass (see WinoFix)
   const float tol = PF ? 1.52587890625e-05f * __uint_as_float(bits[-1]) : 0.f;   // bits[-1]: max |x| (wino_absmax_kernel)
   const int TH = (H + 3) / 4, TW = (W + 3) / 4;
@@ -451,24 +481,86 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float* __restric
     float e[6][6];   // e[a] = (row a of d) B  - the horizontal transform, applied as each row arrives
     float prev[6];
     unsigned rowL = 0, rowR = 0, colEq[5];   // PF: row a constant over columns 0..3 / 2..5; colEq[a] bit b: d[a][b] == d[a+1][b]
+    // POOL: the un-pooled gradient of the window row the current tile row lies in, formed when its first tile row arrives.
+    // Window row wr = rows 4ty-2+2wr, 4ty-1+2wr of y (tile rows 2wr-1, 2wr); window column q = columns 4tx-2+2q, 4tx-1+2q (tile
+    // columns 2q-1, 2q).  A window outside the map is read as window (0, 0) of the plane and dropped by the same predicates that
+    // drop the un-pooled gradient's own padding below.
+    // !EDGE: a thread loads only its two middle windows.  Tile column 0 lies in the left neighbour tile's third window and tile
+    // column 5 in the right neighbour's second: consecutive lanes hold consecutive tiles of one channel (Tw is a multiple of 64),
+    // so both come from the neighbour lanes by a shuffle.  Where that lane is another tile row's, a padding tile's or another
+    // image's, the value is dropped anyway (okl / okr); lanes 0 and 63 have no such neighbour and load that window themselves.
+    float2 pga[4], pgb[4];   // top / bottom row of the four windows
+    const int lane = threadIdx.x & 63;
+    float side[6];           // lanes 0 / 63: tile column 0 / 5 of the un-pooled gradient
+    if (POOL && !EDGE && (lane == 0 || lane == 63)) {
+      const bool left = lane == 0;
+      const int Wo = W / 2;
+      const float* ysrc = pool_y + ((long)n * C + c) * H * W;
+      const float* gsrc = x + ((long)n * C + c) * (H / 2) * Wo;
+#pragma unroll
+      for (int wr = 0; wr < 4; ++wr) {
+        const int wy = 2 * ty - 1 + wr;
+        const bool ok = wy >= 0 && wy < H / 2 && (left ? okl : okr);
+        const float* yp = ysrc + (ok ? (long)(2 * wy) * W + x0 + (left ? -2 : 4) : 0);
+        float2 ga, gb;
+        pool_window_grad(*reinterpret_cast<const float2*>(yp), *reinterpret_cast<const float2*>(yp + W),
+                         gsrc[ok ? wy * Wo + 2 * tx + (left ? -1 : 2) : 0], ga, gb);
+        if (wr > 0) side[2 * wr - 1] = left ? ga.y : ga.x;
+        if (wr < 3) side[2 * wr] = left ? gb.y : gb.x;
+      }
+    }
 #pragma unroll
     for (int a = 0; a < 6; ++a) {
       const int yy = 4 * ty - 1 + a;
       const bool oky = yy >= 0 && yy < H;
       const float* row = src + (oky ? yy * W : 0) + x0;
+      if (POOL && (a == 0 || (a & 1))) {
+        const int Wo = W / 2, wy = 2 * ty - 1 + ((a + 1) >> 1);   // oky <=> 0 <= wy < H / 2
+        const float* ysrc = pool_y + ((long)n * C + c) * H * W;
+        const float* gsrc = x + ((long)n * C + c) * (H / 2) * Wo;
+        if (EDGE) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int wx = 2 * tx - 1 + q;
+            const bool ok = oky && wx >= 0 && wx < Wo;
+            const float* yp = ysrc + (ok ? (long)(2 * wy) * W + 2 * wx : 0);
+            pool_window_grad(*reinterpret_cast<const float2*>(yp), *reinterpret_cast<const float2*>(yp + W), gsrc[ok ? wy * Wo + wx : 0],
+                             pga[q], pgb[q]);
+          }
+        } else {   // W % 4 == 0: the two middle windows exist whenever the row does, and load as one float4 per row of y
+          const float* yr = ysrc + (oky ? (long)(2 * wy) * W : 0) + x0;
+          const float* gr = gsrc + (oky ? wy * Wo : 0) + 2 * tx;
+          const float4 ma = *reinterpret_cast<const float4*>(yr), mb = *reinterpret_cast<const float4*>(yr + W);
+          const float2 gm = *reinterpret_cast<const float2*>(gr);
+          pool_window_grad(make_float2(ma.x, ma.y), make_float2(mb.x, mb.y), gm.x, pga[1], pgb[1]);
+          pool_window_grad(make_float2(ma.z, ma.w), make_float2(mb.z, mb.w), gm.y, pga[2], pgb[2]);
+        }
+      }
+      const float2* pg = (a & 1) ? pga : pgb;   // POOL: this tile row of the un-pooled gradient (odd tile rows are window tops)
       float d[6];
       if (EDGE) {
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
           const int xx = x0 - 1 + b;
           const bool ok = oky && xx >= 0 && xx < W;
-          const float v = row[ok ? b - 1 : 0 - x0];   // invalid: element (yy or 0, 0) of the plane, always in range
+          float v;
+          if (POOL) v = as_loaded((b & 1) ? pg[(b + 1) >> 1].x : pg[(b + 1) >> 1].y);
+          else v = row[ok ? b - 1 : 0 - x0];   // invalid: element (yy or 0, 0) of the plane, always in range
           d[b] = ok ? v : 0.f;
         }
       } else {
-        const float l = row[okl ? -1 : 0];
-        const float4 m = *reinterpret_cast<const float4*>(row);
-        const float rr = row[okr ? 4 : 0];
+        float l, rr;
+        float4 m;
+        if (POOL) {
+          float lv = __shfl_up(pg[2].y, 1, 64), rv = __shfl_down(pg[1].x, 1, 64);
+          if (lane == 0) lv = side[a];
+          if (lane == 63) rv = side[a];
+          l = as_loaded(lv); m = as_loaded(make_float4(pg[1].x, pg[1].y, pg[2].x, pg[2].y)); rr = as_loaded(rv);
+        } else {
+          l = row[okl ? -1 : 0];
+          m = *reinterpret_cast<const float4*>(row);
+          rr = row[okr ? 4 : 0];
+        }
         d[0] = oky && okl ? l : 0.f; d[1] = oky ? m.x : 0.f; d[2] = oky ? m.y : 0.f; d[3] = oky ? m.z : 0.f;
         d[4] = oky ? m.w : 0.f; d[5] = oky && okr ? rr : 0.f;
       }
@@ -914,7 +1006,11 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
       fx.tie_bits = tie_bits;
     }
   }
-  if (f4 && edge) {
+  if (hints.pooled_dy) {   // data gradient with the pool backward folded into the input transform (x: the pooled gradient)
+    UMPR_REQUIRE(f4 && transposed && hints.pool_y && !fix, "winograd: the pooled source needs a data gradient on the 4x4 tile");
+    if (edge) wino4_input_kernel<true, false, true><<<nblk((long)S * WK * TT * WBN, 16384), 256, 0, s>>>(x, V, N, C, S * WK, H, W, Tpad, TT * WBN, wino4_consts(), nullptr, nullptr, hints.pool_y);
+    else wino4_input_kernel<false, false, true><<<nblk((long)S * WK * TT * WBN, 16384), 256, 0, s>>>(x, V, N, C, S * WK, H, W, Tpad, TT * WBN, wino4_consts(), nullptr, nullptr, hints.pool_y);
+  } else if (f4 && edge) {
     if (tie_bits) wino4_input_kernel<true, true><<<nblk((long)S * WK * TT * WBN, 16384), 256, 0, s>>>(x, V, N, C, S * WK, H, W, Tpad, TT * WBN, wino4_consts(), fx.count, tie_bits);
     else wino4_input_kernel<true, false><<<nblk((long)S * WK * TT * WBN, 16384), 256, 0, s>>>(x, V, N, C, S * WK, H, W, Tpad, TT * WBN, wino4_consts(), fx.count, nullptr);
   } else if (f4) {
@@ -969,8 +1065,10 @@ int umpr_wino_conv3x3(const float* x, const float* w, int transposed, const floa
 namespace {
 
 // Gy[xi][m][t] = (A g A^T)[xi],  g = dy[n][m][2ty..2ty+1][2tx..2tx+1];  columns t in [T, Tw) are written as zeros
+// POOL: dy is the pooled gradient and pool_y the layer's output (pool_window_grad): a 2x2 tile is one window
+template <bool POOL>
 __global__ void wino_dy_kernel(const float* __restrict__ dy, float* __restrict__ Gy, int N, int Mch, int H, int W,
-                               long Tpad, long Tw, int Mpad) {
+                               long Tpad, long Tw, int Mpad, const float* __restrict__ pool_y) {
   const int TH = H / 2, TW = W / 2;
   const long T = (long)N * TH * TW;
   const long total = (long)Mch * Tw;
@@ -987,9 +1085,15 @@ __global__ void wino_dy_kernel(const float* __restrict__ dy, float* __restrict__
     const int tx = (int)(t % TW);
     const long r = t / TW;
     const int ty = (int)(r % TH), n = (int)(r / TH);
-    const float* src = dy + (((long)n * Mch + m) * H + 2 * ty) * W + 2 * tx;
-    const float2 g0 = *reinterpret_cast<const float2*>(src);
-    const float2 g1 = *reinterpret_cast<const float2*>(src + W);
+    const long o = (((long)n * Mch + m) * H + 2 * ty) * W + 2 * tx;
+    float2 g0, g1;
+    if (POOL) {
+      pool_window_grad(*reinterpret_cast<const float2*>(pool_y + o), *reinterpret_cast<const float2*>(pool_y + o + W),
+                       dy[((long)n * Mch + m) * TH * TW + (long)ty * TW + tx], g0, g1);
+    } else {
+      g0 = *reinterpret_cast<const float2*>(dy + o);
+      g1 = *reinterpret_cast<const float2*>(dy + o + W);
+    }
     // A g (4x2): rows g0, g0+g1, g0-g1, -g1;  then (A g) A^T per row: p, p+q, p-q, -q
     const float rp[4] = {g0.x, g0.x + g1.x, g0.x - g1.x, -g1.x};
     const float rq[4] = {g0.y, g0.y + g1.y, g0.y - g1.y, -g1.y};
@@ -1004,8 +1108,9 @@ __global__ void wino_dy_kernel(const float* __restrict__ dy, float* __restrict__
 }
 
 // two horizontally adjacent tiles per thread (even tile rows): float4 loads of dy, float2 stores
+template <bool POOL>
 __global__ void wino_dy_pair_kernel(const float* __restrict__ dy, float* __restrict__ Gy, int N, int Mch, int H, int W,
-                                    long Tpad, long Tw, int Mpad) {
+                                    long Tpad, long Tw, int Mpad, const float* __restrict__ pool_y) {
   const int TH = H / 2, TW = W / 2;
   const long T = (long)N * TH * TW;
   const long Tw2 = Tw / 2;
@@ -1023,9 +1128,20 @@ __global__ void wino_dy_pair_kernel(const float* __restrict__ dy, float* __restr
     const int tx = (int)(t % TW);
     const long r = t / TW;
     const int ty = (int)(r % TH), n = (int)(r / TH);
-    const float* src = dy + (((long)n * Mch + m) * H + 2 * ty) * W + 2 * tx;
-    const float4 g0 = *reinterpret_cast<const float4*>(src);        // row 0: tile 0 (x, y), tile 1 (z, w)
-    const float4 g1 = *reinterpret_cast<const float4*>(src + W);    // row 1
+    const long o = (((long)n * Mch + m) * H + 2 * ty) * W + 2 * tx;
+    float4 g0, g1;   // row 0: tile 0 (x, y), tile 1 (z, w); row 1
+    if (POOL) {      // two windows: float4 rows of y, one float2 of the pooled gradient (tx and TW are even)
+      const float4 y0 = *reinterpret_cast<const float4*>(pool_y + o), y1 = *reinterpret_cast<const float4*>(pool_y + o + W);
+      const float2 gp = *reinterpret_cast<const float2*>(dy + ((long)n * Mch + m) * TH * TW + (long)ty * TW + tx);
+      float2 a0, b0, a1, b1;
+      pool_window_grad(make_float2(y0.x, y0.y), make_float2(y1.x, y1.y), gp.x, a0, b0);
+      pool_window_grad(make_float2(y0.z, y0.w), make_float2(y1.z, y1.w), gp.y, a1, b1);
+      g0 = make_float4(a0.x, a0.y, a1.x, a1.y);
+      g1 = make_float4(b0.x, b0.y, b1.x, b1.y);
+    } else {
+      g0 = *reinterpret_cast<const float4*>(dy + o);
+      g1 = *reinterpret_cast<const float4*>(dy + o + W);
+    }
     const float2 rp[4] = {make_float2(g0.x, g0.z), make_float2(g0.x + g1.x, g0.z + g1.z),
                           make_float2(g0.x - g1.x, g0.z - g1.z), make_float2(-g1.x, -g1.z)};
     const float2 rq[4] = {make_float2(g0.y, g0.w), make_float2(g0.y + g1.y, g0.w + g1.w),
@@ -1089,19 +1205,33 @@ __global__ __launch_bounds__(256) void wino_wgrad_finish_wide_kernel(const float
 
 // db partial sums: one wave per (image, channel) plane, float4 loads, shuffle reduction (the workgroup-per-plane tree above
 // spends most of its time in eight barriers for 3 KB of data)
+// POOL: dy is the pooled gradient and pool_y the layer's output: the four elements of each float4 are formed from their
+// windows (a float4 may straddle rows, so element by element) and summed in the order above
+template <bool POOL>
 __global__ __launch_bounds__(256) void wino_bias_part_wave_kernel(const float* __restrict__ dy, float* __restrict__ part, long HW,
-                                                                  long planes) {
+                                                                  long planes, const float* __restrict__ pool_y, int W) {
   const int lane = threadIdx.x & 63;
   const long pl = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (pl >= planes) return;
   const float4* src = reinterpret_cast<const float4*>(dy + pl * HW);
+  const float* yp = pool_y + pl * HW;
+  const float* gp = dy + pl * (HW / 4);
+  auto elem = [&](long e) {   // un-pooled gradient of flat element e of the plane
+    const int r = (int)(e / W), c = (int)(e - (long)r * W);
+    const float* w = yp + (long)(r & ~1) * W + (c & ~1);
+    float2 ga, gb;
+    pool_window_grad(*reinterpret_cast<const float2*>(w), *reinterpret_cast<const float2*>(w + W), gp[(r >> 1) * (W / 2) + (c >> 1)], ga, gb);
+    const float2 row = (r & 1) ? gb : ga;
+    return (c & 1) ? row.y : row.x;
+  };
+  auto load = [&](long i) { return POOL ? make_float4(elem(4 * i), elem(4 * i + 1), elem(4 * i + 2), elem(4 * i + 3)) : src[i]; };
   float a0 = 0.f, a1 = 0.f;
   long i = lane;
   for (; i + 64 < HW / 4; i += 128) {
-    const float4 u = src[i], w = src[i + 64];
+    const float4 u = load(i), w = load(i + 64);
     a0 += (u.x + u.y) + (u.z + u.w); a1 += (w.x + w.y) + (w.z + w.w);
   }
-  for (; i < HW / 4; i += 64) { const float4 u = src[i]; a0 += (u.x + u.y) + (u.z + u.w); }
+  for (; i < HW / 4; i += 64) { const float4 u = load(i); a0 += (u.x + u.y) + (u.z + u.w); }
   const float a = wave_sum(a0 + a1);
   if (lane == 0) part[pl] = a;
 }
@@ -1151,9 +1281,13 @@ __device__ __forceinline__ void wino4_a(const Wino4C& c, const float g0, const f
 // bias_part (optional, !EDGE only): [Mch][Tw / 64] - the sum of the gradient pixels each WAVE transformed (64 consecutive tiles of
 // one channel: Tw is a multiple of 64), the first stage of the bias gradient; wino_bias_sum_waves_kernel adds them per channel in a
 // fixed order.  Replaces a separate pass over dy (wino_bias_part_wave_kernel: 0.35 ms per step of pure re-reading).
-template <bool EDGE>
+// POOL (!EDGE only): dy is the pooled gradient and pool_y the layer's output; a 4x4 tile is four whole windows
+// (pool_window_grad), and the rows enter the transform and the bias sum exactly as the un-pooled gradient's would.
+template <bool EDGE, bool POOL = false>
 __global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__ dy, float* __restrict__ Gy, int N, int Mch, int H,
-                                                       int W, long Tpad, long Tw, int Mpad, Wino4C wc, float* __restrict__ bias_part) {
+                                                       int W, long Tpad, long Tw, int Mpad, Wino4C wc, float* __restrict__ bias_part,
+                                                       const float* __restrict__ pool_y = nullptr) {
+  static_assert(!(EDGE && POOL), "a weight gradient on the 4x4 tile has no edge tiles");
   const int TH = (H + 3) / 4, TW = (W + 3) / 4;
   const long T = (long)N * TH * TW;
   const long total = (long)Mch * Tw;
@@ -1172,6 +1306,22 @@ __global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__
       const int ty = (int)(r % TH), n = (int)(r / TH);
       const float* src = dy + (((long)n * Mch + m) * H + 4 * ty) * W + 4 * tx;
       float e[4][6];   // (row of g) A^T
+      float4 pg[4];    // POOL: the four rows of the un-pooled gradient
+      if (POOL) {
+        const float* ysrc = pool_y + (((long)n * Mch + m) * H + 4 * ty) * W + 4 * tx;
+        const float* gsrc = dy + (((long)n * Mch + m) * (H / 2) + 2 * ty) * (W / 2) + 2 * tx;
+#pragma unroll
+        for (int wr = 0; wr < 2; ++wr) {
+          const float4 y0 = *reinterpret_cast<const float4*>(ysrc + (long)(2 * wr) * W);
+          const float4 y1 = *reinterpret_cast<const float4*>(ysrc + (long)(2 * wr + 1) * W);
+          const float2 gp = *reinterpret_cast<const float2*>(gsrc + (long)wr * (W / 2));
+          float2 a0, b0, a1, b1;
+          pool_window_grad(make_float2(y0.x, y0.y), make_float2(y1.x, y1.y), gp.x, a0, b0);
+          pool_window_grad(make_float2(y0.z, y0.w), make_float2(y1.z, y1.w), gp.y, a1, b1);
+          pg[2 * wr] = as_loaded(make_float4(a0.x, a0.y, a1.x, a1.y));
+          pg[2 * wr + 1] = as_loaded(make_float4(b0.x, b0.y, b1.x, b1.y));
+        }
+      }
 #pragma unroll
       for (int a = 0; a < 4; ++a) {
         if (EDGE) {   // gradient rows / columns past the border do not exist: zero
@@ -1186,7 +1336,7 @@ __global__ __launch_bounds__(256) void wino4_dy_kernel(const float* __restrict__
           wino4_a(wc, d[0], d[1], d[2], d[3], e[a]);
           continue;
         }
-        const float4 g = *reinterpret_cast<const float4*>(src + (long)a * W);
+        const float4 g = POOL ? pg[a] : *reinterpret_cast<const float4*>(src + (long)a * W);
         bsum += (g.x + g.y) + (g.z + g.w);
         wino4_a(wc, g.x, g.y, g.z, g.w, e[a]);
       }
@@ -1500,15 +1650,24 @@ int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N
   const bool edge = f4 && ((H % 4) != 0 || (W % 4) != 0);
   static const bool bias_fuse = umpr_env_on("UMPR_WINO_BIAS_FUSE");     // 0: the separate pass over dy
   const bool fused_bias = db && f4 && !edge && bias_fuse && (g.Tpad % 64) == 0;
+  const bool pooled = hints.pooled_dy;   // dy is the pooled gradient, hints.pool_y the layer's output: the pool backward is folded in
+  const float* py = hints.pool_y;
+  if (pooled) UMPR_REQUIRE(py && !edge, "winograd wgrad: the pooled source needs the layer's output and whole tiles");
   if (f4 && edge)
     wino4_dy_kernel<true><<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, wino4_consts(), nullptr);
+  else if (f4 && pooled)
+    wino4_dy_kernel<false, true><<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, wino4_consts(),
+                                                                                  fused_bias ? BP : nullptr, py);
   else if (f4)
     wino4_dy_kernel<false><<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, wino4_consts(),
                                                                             fused_bias ? BP : nullptr);
-  else if ((W / 2) % 2 == 0)
-    wino_dy_pair_kernel<<<nblk((long)Cout * g.Tpad / 2, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad);
-  else
-    wino_dy_kernel<<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad);
+  else if ((W / 2) % 2 == 0) {
+    if (pooled) wino_dy_pair_kernel<true><<<nblk((long)Cout * g.Tpad / 2, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, py);
+    else wino_dy_pair_kernel<false><<<nblk((long)Cout * g.Tpad / 2, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, nullptr);
+  } else {
+    if (pooled) wino_dy_kernel<true><<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, py);
+    else wino_dy_kernel<false><<<nblk((long)Cout * g.Tpad, 16384), 256, 0, s>>>(dy, Gy, N, Cout, H, W, g.Tpad, g.Tpad, g.Mpad, nullptr);
+  }
   UMPR_LAUNCH_CHECK("wino_dy");
   if (hints.v_slot) {   // the forward pass left this layer's transformed input in the caller's slot (checked against the plan
                         // by umpr_conv3x3_wgrad; this is the layout it must match)
@@ -1546,7 +1705,8 @@ int umpr_wino_wgrad(const float* dy, const float* x, float* dw, float* db, int N
   } else if (db) {  // P is free again after the finish kernel (same stream): N * Cout partial sums fit in it
     UMPR_REQUIRE((size_t)N * Cout <= (size_t)g.splits * g.planes * g.Mpad * g.Cpad && ((long)H * W) % 4 == 0,
                  "winograd wgrad: bias-gradient scratch");
-    wino_bias_part_wave_kernel<<<(unsigned)(((long)N * Cout + 3) / 4), 256, 0, s>>>(dy, P, (long)H * W, (long)N * Cout);
+    if (pooled) wino_bias_part_wave_kernel<true><<<(unsigned)(((long)N * Cout + 3) / 4), 256, 0, s>>>(dy, P, (long)H * W, (long)N * Cout, py, W);
+    else wino_bias_part_wave_kernel<false><<<(unsigned)(((long)N * Cout + 3) / 4), 256, 0, s>>>(dy, P, (long)H * W, (long)N * Cout, nullptr, W);
     UMPR_LAUNCH_CHECK("wino_bias_part");
     wino_bias_sum_kernel<<<(Cout + 255) / 256, 256, 0, s>>>(P, db, N, Cout, accumulate);
     UMPR_LAUNCH_CHECK("wino_bias_sum");
