@@ -196,6 +196,20 @@ int umpr_coattention_fwd(const float* Gu, const float* Gi, const float* M, int B
 int umpr_coattention_fwd_bf16(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                               float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax,
                               int32_t* argcol, float* rowmax, int32_t* argrow, float* ws, size_t ws_bytes, void* stream);
+/* Token validity for the masked forms below: valid[n][l] = l < min(max(lengths[n], 0), L) && ids[n][l] != pad_id, one uint8
+ * per token of ids [N][L].  One launch, no allocation, copy or host synchronisation (safe inside a stream capture).  Null
+ * pointers and N or L below 1 are refused before the launch. */
+int umpr_token_mask(const int64_t* ids, const int32_t* lengths, int N, int L, long pad_id, uint8_t* valid, void* stream);
+/* umpr_coattention_fwd (bf16_scores = 0) or _fwd_bf16 (1) with a key-padding mask: valid_u / valid_i [B][SL] bytes for the user
+ * (column) and item (row) positions.  colmax[k] / argcol[k] run over the valid item positions only (first one on ties) and are
+ * defined when k is valid and some item position is; otherwise colmax[k] = +0.0, argcol[k] = -1.  soft_u is the softmax of
+ * colmax over the defined positions and +0.0 elsewhere; a sample without any gets soft_u = 0 and atte_u = 0, never NaN.  Rows,
+ * soft_i, atte_i alike.  With every byte set each output has the bits of the unmasked call.  Same three launches, same workspace
+ * size; umpr_coattention_bwd consumes the saved tensors unchanged (gradients of masked rows come out as +0.0). */
+int umpr_coattention_fwd_masked(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
+                                float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax,
+                                int32_t* argcol, float* rowmax, int32_t* argrow, const uint8_t* valid_u,
+                                const uint8_t* valid_i, int bf16_scores, float* ws, size_t ws_bytes, void* stream);
 size_t umpr_coattention_bwd_ws_bytes(int B, int SL);
 int umpr_coattention_bwd(const float* Gu, const float* Gi, const float* M, const float* T, const float* soft_u,
                          const float* soft_i, const float* colmax, const int32_t* argcol, const float* rowmax,
@@ -208,6 +222,12 @@ int umpr_coattention_bwd(const float* Gu, const float* Gi, const float* M, const
  * Outputs: self_atte [B][S][128], senti rows at senti + b*ld_senti.  Saved: U [B][S][L][64], P [B][S][L], wsum [B][S]. */
 int umpr_snet_fwd(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S,
                   int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti, void* stream);
+/* umpr_snet_fwd with valid [B][S][L] bytes: P is the softmax of the word scores over the valid tokens of a sentence and +0.0 at
+ * the others; a sentence without a valid token gets P = 0 and self_atte = 0.  wsum and senti keep their formulas.  umpr_snet_bwd
+ * reads P and needs no mask. */
+int umpr_snet_fwd_masked(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S,
+                         int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
+                         const uint8_t* valid, void* stream);
 size_t umpr_snet_bwd_ws_bytes(int B, int S, int L);
 int umpr_snet_bwd(const float* X, const float* Ms, const float* Ws, const float* U, const float* P, const float* wsum,
                   const float* self_atte, const float* d_senti, long ld_ds, const float* d_self_atte /*or NULL*/,
@@ -271,6 +291,12 @@ size_t umpr_review_net_ws_bytes(int B, int S, int L, int E);
 int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
                         float* out, float* ws, size_t ws_bytes, void* stream);
+/* The same through umpr_coattention_fwd_masked and umpr_snet_fwd_masked: valid_pair [2N][L] bytes, user rows then item rows, as
+ * umpr_token_mask writes them for ids_pair.  Same arena, same workspace; both backward calls read the arena as they do. */
+int umpr_review_net_fwd_masked(const int64_t* ids_pair, const float* emb, int E, const float* const* params,
+                               const int32_t* lengths, const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores,
+                               int need_grad, void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair,
+                               void* stream);
 /* grads: 15 pointers in the order of params, each overwritten */
 int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,

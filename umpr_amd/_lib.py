@@ -37,9 +37,12 @@ SIGNATURES = {
     "umpr_coattention_fwd_ws_bytes": ("ii", "z"),
     "umpr_coattention_fwd": ("pppiipppplplpppppzp", "i"),
     "umpr_coattention_fwd_bf16": ("pppiipppplplpppppzp", "i"),
+    "umpr_token_mask": ("ppiilpp", "i"),
+    "umpr_coattention_fwd_masked": ("pppiipppplplppppppipzp", "i"),
     "umpr_coattention_bwd_ws_bytes": ("ii", "z"),
     "umpr_coattention_bwd": ("ppppppppppplplppiipppipzp", "i"),
     "umpr_snet_fwd": ("ppppiiiippppplp", "i"),
+    "umpr_snet_fwd_masked": ("ppppiiiippppplpp", "i"),
     "umpr_snet_bwd_ws_bytes": ("iii", "z"),
     "umpr_snet_bwd": ("pppppppplpiiiipppppzp", "i"),
     "umpr_review_merge_fwd": ("ppppipp", "i"),
@@ -96,6 +99,7 @@ SIGNATURES = {
     "umpr_review_net_arena_bytes": ("iii", "z"),
     "umpr_review_net_ws_bytes": ("iiii", "z"),
     "umpr_review_net_fwd": ("ppipppiiiiiipppzp", "i"),
+    "umpr_review_net_fwd_masked": ("ppipppiiiiiipppzpp", "i"),
     "umpr_review_net_bwd": ("ppipppiiiippppzp", "i"),
     "umpr_review_net_bwd_dx": ("ppipppiiiipppppzp", "i"),
     "umpr_control_net_arena_bytes": ("iiiiiii", "z"),

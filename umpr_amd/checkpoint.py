@@ -4,7 +4,8 @@ The reference only ever pickles the whole module when validation improves (main.
 scheduler / epoch state.  Here a checkpoint is a plain dict of tensors and numbers (loadable with
 ``torch.load(..., weights_only=True)``): the model ``state_dict`` under the reference's key names - so the weights
 move between the two implementations by ``state_dict`` - plus, optionally, the Adam moments, step count and learning
-rate for an exact resume.
+rate for an exact resume.  ``mask_padding`` records whether the ReviewNet ran with its padding mask (model.UMPR.mask_padding):
+loading into a model built with the other setting is refused, and a file without the key counts as False.
 """
 from __future__ import annotations
 
@@ -29,6 +30,8 @@ def save_checkpoint(path, model, opt=None, epoch=0, batch_counter=0, best_loss=N
     if epoch_rng is not None:
         ck["epoch_rng"] = epoch_rng.clone()
     # forward-call counters that seed the dropout masks (model.VGG16._calls): part of an exact resume
+    # --mask_padding changes what the ReviewNet computes without adding a parameter: recorded, and checked by load_checkpoint
+    ck["mask_padding"] = bool(getattr(model, "mask_padding", False))
     ck["rng_calls"] = {n: int(m._calls) for n, m in model.named_modules() if hasattr(m, "_calls")}
     if opt is not None:
         ck["optimizer"] = opt.state_dict()
@@ -46,6 +49,13 @@ def load_checkpoint(path, model, opt=None, map_location="cpu", weights="model"):
         raise ValueError(f"load_checkpoint: weights must be 'model' or 'ema', got {weights!r}")
     ck = torch.load(path, map_location=map_location, weights_only=True)
     sd = ck["model"] if isinstance(ck, dict) and "model" in ck and isinstance(ck["model"], dict) else ck
+    # before anything is written: weights trained with the padding mask are other weights than those trained without it (a
+    # checkpoint from before the option, or a bare state_dict, was trained without)
+    saved_mask = bool(ck.get("mask_padding", False)) if sd is not ck else False
+    if saved_mask != bool(getattr(model, "mask_padding", False)):
+        raise ValueError(f"{path} was written with --mask_padding {saved_mask} and the model is built with --mask_padding "
+                         f"{not saved_mask}: resume or test it with --mask_padding {saved_mask} (the weights themselves are "
+                         "interchangeable by state_dict)")
     ema = None
     if weights == "ema":                                # before anything is written
         ema = ck["optimizer"].get("ema") if isinstance(ck, dict) and isinstance(ck.get("optimizer"), dict) else None

@@ -369,6 +369,19 @@ int umpr_coattention_fwd_bf16(const float* Gu, const float* Gi, const float* M, 
   return umpr_coattn_fwd_impl(Gu, Gi, M, B, SL, T, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, colmax, argcol, rowmax,
                               argrow, ws, ws_bytes, S(stream), 1);
 }
+int umpr_coattention_fwd_masked(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
+                                float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax,
+                                int32_t* argcol, float* rowmax, int32_t* argrow, const uint8_t* valid_u,
+                                const uint8_t* valid_i, int bf16_scores, float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(valid_u && valid_i, "coattention_fwd_masked: null validity mask");
+  return umpr_coattn_fwd_impl(Gu, Gi, M, B, SL, T, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, colmax, argcol, rowmax,
+                              argrow, ws, ws_bytes, S(stream), bf16_scores ? 1 : 0, valid_u, valid_i);
+}
+int umpr_token_mask(const int64_t* ids, const int32_t* lengths, int N, int L, long pad_id, uint8_t* valid, void* stream) {
+  UMPR_REQUIRE(ids && lengths && valid, "token_mask: null pointer");
+  UMPR_REQUIRE(N >= 1 && L >= 1, "token_mask: bad shape %d x %d", N, L);
+  return umpr_token_mask_impl(ids, lengths, N, L, pad_id, valid, S(stream));
+}
 size_t umpr_coattention_bwd_ws_bytes(int B, int SL) { return umpr_coattn_bwd_ws_bytes(B, SL); }
 int umpr_coattention_bwd(const float* Gu, const float* Gi, const float* M, const float* T, const float* soft_u,
                          const float* soft_i, const float* colmax, const int32_t* argcol, const float* rowmax,
@@ -383,6 +396,12 @@ int umpr_coattention_bwd(const float* Gu, const float* Gi, const float* M, const
 int umpr_snet_fwd(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S_,
                   int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti, void* stream) {
   return umpr_snet_fwd_impl(X, Ms, Ws, word_soft, wl, B, S_, L, U, P, wsum, self_atte, senti, ld_senti, S(stream));
+}
+int umpr_snet_fwd_masked(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S_,
+                         int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
+                         const uint8_t* valid, void* stream) {
+  UMPR_REQUIRE(valid, "snet_fwd_masked: null validity mask");
+  return umpr_snet_fwd_impl(X, Ms, Ws, word_soft, wl, B, S_, L, U, P, wsum, self_atte, senti, ld_senti, S(stream), valid);
 }
 size_t umpr_snet_bwd_ws_bytes(int B, int S_, int L) { return umpr_snet_bwd_ws_bytes_impl(B, S_, L); }
 int umpr_snet_bwd(const float* X, const float* Ms, const float* Ws, const float* U, const float* P, const float* wsum,

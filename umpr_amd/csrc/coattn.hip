@@ -1,7 +1,15 @@
 // R-Net co-attention (src/model.py:50-55) for gfx950, hidden width 2u = 128.
 //
 //   A = tanh(G_i M G_u^T)   soft_u = softmax_k(max_j A[j,k])   soft_i = softmax_j(max_k A[j,k])
-//   atte_u = G_u^T soft_u   atte_i = G_i^T soft_i                       (no padding mask, like the reference)
+//   atte_u = G_u^T soft_u   atte_i = G_i^T soft_i
+//
+// The reference has no padding mask, and neither have umpr_coattention_fwd / _fwd_bf16.  umpr_coattention_fwd_masked takes
+// one validity byte per user and per item position: maxima run over valid partners only, an undefined position (masked,
+// or without any valid partner) is saved as colmax = +0.0, argcol = -1, soft = +0.0, and the softmax runs over the
+// defined positions alone (a side without any gets soft = 0 and atte = 0).  The backward needs no mask: soft = 0 makes
+// dS = 0 there, and coattn_bwd_rows_kernel forms no address from a negative index.  The forward kernels live in
+// coattn_fwd_kernels.inc and are compiled twice from it, without and with the mask: the unmasked ones are the text, and
+// compile to the code, they were before the mask existed.
 //
 // The SLxSL affinity matrix is never written to HBM: T = G_i M comes from the GEMM kernel, `scores` forms 64x64
 // tiles of tanh(T G_u^T) on v_mfma_f32_32x32x2_f32 and keeps only row/column maxima with their (first) argmax, and
@@ -46,240 +54,8 @@ __device__ __forceinline__ void stage_tile_f32(const float* __restrict__ src, in
   }
 }
 
-// One workgroup = 64 rows (j) x the column tiles of its split.  Wave (wi, wu) owns a 32 x 32 tile; lane half kh takes
-// the reduction columns c = 64 kh + kk (any split of the 128 columns works as long as A and B agree), so a lane's 64
-// operand values per matrix are contiguous: 16 ds_read_b128 each, all in registers before the 64 MFMAs, which run as
-// two independent accumulator chains.
-__global__ __launch_bounds__(256) void coattn_scores_kernel(ScoreParams p) {
-  __shared__ __attribute__((aligned(16))) float Ts[64 * LDR];
-  __shared__ __attribute__((aligned(16))) float Us[64 * LDR];
-  __shared__ float xv[2][64]; __shared__ int xi[2][64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wu = wave & 1;
-  const int l31 = lane & 31, kh = lane >> 5;
-  const int b = blockIdx.y, blk = blockIdx.x;
-  const int SL = p.SL;
-  const int j0 = blk * 64;
-  const float* Tb = p.T + (long)b * SL * D;
-  const float* Ub = p.Gu + (long)b * SL * D;
-
-  stage_tile_f32(Tb, j0, SL, Ts, tid);
-  float rbest[16]; int ridx[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { rbest[r] = -INFINITY; ridx[r] = 0x7fffffff; }
-  __syncthreads();
-  float4 ta[16];
-#pragma unroll
-  for (int q = 0; q < 16; ++q) ta[q] = *reinterpret_cast<const float4*>(Ts + (wi * 32 + l31) * LDR + 64 * kh + 4 * q);
-
-  const int ntile = (SL + 63) / 64;
-  const int tper = (ntile + p.ksplit - 1) / p.ksplit;
-  const int ut_end = min(ntile, ((int)blockIdx.z + 1) * tper);
-  for (int ut = blockIdx.z * tper; ut < ut_end; ++ut) {
-    const int k0 = ut * 64;
-    __syncthreads();
-    stage_tile_f32(Ub, k0, SL, Us, tid);
-    __syncthreads();
-    float4 ub[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) ub[q] = *reinterpret_cast<const float4*>(Us + (wu * 32 + l31) * LDR + 64 * kh + 4 * q);
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      acc0 = mfma32(ta[q].x, ub[q].x, acc0);
-      acc1 = mfma32(ta[q].y, ub[q].y, acc1);
-      acc0 = mfma32(ta[q].z, ub[q].z, acc0);
-      acc1 = mfma32(ta[q].w, ub[q].w, acc1);
-    }
-    const int kcol = k0 + wu * 32 + l31;
-    const bool kvalid = kcol < SL;
-    float cbest = -INFINITY; int cidx = 0x7fffffff;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = j0 + wi * 32 + mfma_row(r, lane);
-      const float a = tanhf(acc0[r] + acc1[r]);
-      if (kvalid && j < SL) {
-        better_first(rbest[r], ridx[r], a, kcol);
-        better_first(cbest, cidx, a, j);
-      }
-    }
-    // column max: combine the two lane halves (rows +4), then the two wi waves
-    {
-      const float ov = __shfl_xor(cbest, 32, 64);
-      const int oi = __shfl_xor(cidx, 32, 64);
-      better_first(cbest, cidx, ov, oi);
-    }
-    if (wi == 1 && kh == 0) { xv[wu][l31] = cbest; xi[wu][l31] = cidx; }
-    __syncthreads();
-    if (wi == 0 && kh == 0) {
-      better_first(cbest, cidx, xv[wu][l31], xi[wu][l31]);
-      if (kvalid) {
-        const long o = ((long)b * p.nblk + blk) * SL + kcol;
-        p.colmax_part[o] = cbest;
-        p.argcol_part[o] = cidx;
-      }
-    }
-  }
-  // row max: reduce over the 32 lanes of each half (columns), then over the two wu waves
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float v = rbest[r]; int i = ridx[r];
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v, o, 64);
-      const int oi = __shfl_xor(i, o, 64);
-      better_first(v, i, ov, oi);
-    }
-    rbest[r] = v; ridx[r] = i;
-  }
-  // rows of this wave: wi*32 + mfma_row(r, lane); lanes l31==0 of each half hold the result
-  if (wu == 1 && l31 == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int jr = wi * 32 + mfma_row(r, lane);
-      xv[0][jr] = rbest[r]; xi[0][jr] = ridx[r];
-    }
-  }
-  __syncthreads();
-  if (wu == 0 && l31 == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int jr = wi * 32 + mfma_row(r, lane);
-      float v = rbest[r]; int i = ridx[r];
-      better_first(v, i, xv[0][jr], xi[0][jr]);
-      if (j0 + jr < SL) {
-        const long o = ((long)b * p.ksplit + blockIdx.z) * SL + j0 + jr;
-        p.rowmax_part[o] = v;
-        p.argrow_part[o] = i;
-      }
-    }
-  }
-}
-
-// The same tile loop with the score contraction on v_mfma_f32_32x32x16_bf16 (BASELINE.json configs[4]: "MFMA bf16 ...
-// attention"): T and G_u rows are rounded to bf16 when they are staged, products accumulate in fp32, tanh / max /
-// argmax stay fp32.  LDS rows of 128 bf16 are padded to 136 (272 B = 17 slots of 16 B): conflict-free ds_read_b128.
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-__global__ __launch_bounds__(256) void coattn_scores_bf16_kernel(ScoreParams p) {
-  constexpr int LDB = 136;
-  __shared__ __attribute__((aligned(16))) __bf16 Ts[64 * LDB];
-  __shared__ __attribute__((aligned(16))) __bf16 Us[64 * LDB];
-  __shared__ float xv[2][64]; __shared__ int xi[2][64];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wi = wave >> 1, wu = wave & 1;
-  const int l31 = lane & 31, kh = lane >> 5;
-  const int b = blockIdx.y, blk = blockIdx.x;
-  const int SL = p.SL;
-  const int j0 = blk * 64;
-  const float* Tb = p.T + (long)b * SL * D;
-  const float* Ub = p.Gu + (long)b * SL * D;
-  auto stage = [&](const float* src, int row0, __bf16* dst) {
-    float4 v[8];                                        // every load in flight before the first use (clamped rows)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int e = tid + 256 * i;
-      const int j = e >> 5, c4 = (e & 31) * 4;
-      v[i] = *reinterpret_cast<const float4*>(src + (long)min(row0 + j, SL - 1) * D + c4);
-    }
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int e = tid + 256 * i;
-      const int j = e >> 5, c4 = (e & 31) * 4;
-      const bool ok = row0 + j < SL;
-      bf16x4_t o;
-      o[0] = (__bf16)(ok ? v[i].x : 0.f); o[1] = (__bf16)(ok ? v[i].y : 0.f);
-      o[2] = (__bf16)(ok ? v[i].z : 0.f); o[3] = (__bf16)(ok ? v[i].w : 0.f);
-      *reinterpret_cast<bf16x4_t*>(dst + j * LDB + c4) = o;
-    }
-  };
-  stage(Tb, j0, Ts);
-  float rbest[16]; int ridx[16];
-#pragma unroll
-  for (int r = 0; r < 16; ++r) { rbest[r] = -INFINITY; ridx[r] = 0x7fffffff; }
-  const int ntile = (SL + 63) / 64;
-  const int tper = (ntile + p.ksplit - 1) / p.ksplit;
-  const int ut_end = min(ntile, ((int)blockIdx.z + 1) * tper);
-  for (int ut = blockIdx.z * tper; ut < ut_end; ++ut) {
-    const int k0 = ut * 64;
-    __syncthreads();
-    stage(Ub, k0, Us);
-    __syncthreads();
-    f32x16 acc;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-#pragma unroll
-    for (int ks = 0; ks < D / 16; ++ks) {
-      const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(Ts + (wi * 32 + l31) * LDB + ks * 16 + 8 * kh);
-      const bf16x8_t u = *reinterpret_cast<const bf16x8_t*>(Us + (wu * 32 + l31) * LDB + ks * 16 + 8 * kh);
-      acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, u, acc, 0, 0, 0);
-    }
-    const int kcol = k0 + wu * 32 + l31;
-    const bool kvalid = kcol < SL;
-    float cbest = -INFINITY; int cidx = 0x7fffffff;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int j = j0 + wi * 32 + mfma_row(r, lane);
-      const float a = tanhf(acc[r]);
-      if (kvalid && j < SL) {
-        better_first(rbest[r], ridx[r], a, kcol);
-        better_first(cbest, cidx, a, j);
-      }
-    }
-    {
-      const float ov = __shfl_xor(cbest, 32, 64);
-      const int oi = __shfl_xor(cidx, 32, 64);
-      better_first(cbest, cidx, ov, oi);
-    }
-    if (wi == 1 && kh == 0) { xv[wu][l31] = cbest; xi[wu][l31] = cidx; }
-    __syncthreads();
-    if (wi == 0 && kh == 0) {
-      better_first(cbest, cidx, xv[wu][l31], xi[wu][l31]);
-      if (kvalid) {
-        const long o = ((long)b * p.nblk + blk) * SL + kcol;
-        p.colmax_part[o] = cbest;
-        p.argcol_part[o] = cidx;
-      }
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    float v = rbest[r]; int i = ridx[r];
-#pragma unroll
-    for (int o = 16; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(v, o, 64);
-      const int oi = __shfl_xor(i, o, 64);
-      better_first(v, i, ov, oi);
-    }
-    rbest[r] = v; ridx[r] = i;
-  }
-  if (wu == 1 && l31 == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int jr = wi * 32 + mfma_row(r, lane);
-      xv[0][jr] = rbest[r]; xi[0][jr] = ridx[r];
-    }
-  }
-  __syncthreads();
-  if (wu == 0 && l31 == 0) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int jr = wi * 32 + mfma_row(r, lane);
-      float v = rbest[r]; int i = ridx[r];
-      better_first(v, i, xv[0][jr], xi[0][jr]);
-      if (j0 + jr < SL) {
-        const long o = ((long)b * p.ksplit + blockIdx.z) * SL + j0 + jr;
-        p.rowmax_part[o] = v;
-        p.argrow_part[o] = i;
-      }
-    }
-  }
-}
-
 __device__ float block_sum(float v, float* red) {
   v = wave_sum(v);
   __syncthreads();
@@ -311,55 +87,13 @@ struct FinishParams {
   int SL;
 };
 
-// 1024 threads per (sample, side): the weighted sums over the SL positions run as 8 chains of SL/8 terms per column.  Side 0 =
-// the user's columns (colmax -> soft_u -> atte_u), side 1 = the item's rows; one workgroup each (grid (B, 2)): at batch 32 a grid
-// of B workgroups doing both sides one after the other left 7/8 of the chip idle for 33 us.
-__global__ __launch_bounds__(1024) void coattn_finish_kernel(FinishParams p) {
-  extern __shared__ float sm[];  // s[SL]
-  __shared__ float red[16];
-  __shared__ float part[8][D];
-  const int tid = threadIdx.x, b = blockIdx.x, side = blockIdx.y, SL = p.SL;
-  const float* max_part = side ? p.rowmax_part : p.colmax_part;
-  const int* arg_part = side ? p.argrow_part : p.argcol_part;
-  const int nparts = side ? p.ksplit : p.nblk;     // (row parts: ascending column ranges, ties keep the first column)
-  float* vmax = side ? p.rowmax : p.colmax;
-  int* varg = side ? p.argrow : p.argcol;
-  float* soft = side ? p.soft_i : p.soft_u;
-  float* sv = sm;
-  float mx = -INFINITY;
-  for (int k = tid; k < SL; k += 1024) {
-    float v = -INFINITY; int idx = 0x7fffffff;
-    for (int q = 0; q < nparts; ++q) {
-      const long o = ((long)b * nparts + q) * SL + k;
-      better_first(v, idx, max_part[o], arg_part[o]);
-    }
-    vmax[(long)b * SL + k] = v; varg[(long)b * SL + k] = idx;
-    sv[k] = v; mx = fmaxf(mx, v);
-  }
-  mx = block_max(mx, red);
-  float z = 0.f;
-  for (int k = tid; k < SL; k += 1024) {
-    const float e = expf(sv[k] - mx);
-    sv[k] = e; z += e;
-  }
-  z = block_sum(z, red);
-  for (int k = tid; k < SL; k += 1024) {
-    sv[k] /= z;
-    soft[(long)b * SL + k] = sv[k];
-  }
-  __syncthreads();
-  const int c = tid & 127, grp = tid >> 7;
-  const float* G = (side ? p.Gi : p.Gu) + (long)b * SL * D;
-  float a = 0.f;
-#pragma unroll 4
-  for (int k = grp; k < SL; k += 8) a += sv[k] * G[(long)k * D + c];
-  part[grp][c] = a;
-  __syncthreads();
-  if (grp == 0) {
-    const float v = ((part[0][c] + part[1][c]) + (part[2][c] + part[3][c])) + ((part[4][c] + part[5][c]) + (part[6][c] + part[7][c]));
-    if (side == 0) p.atte_u[(long)b * p.ld_u + c] = v; else p.atte_i[(long)b * p.ld_i + c] = v;
-  }
-}
+// coattn_scores_kernel, coattn_scores_bf16_kernel, coattn_finish_kernel and their *_masked_kernel forms
+#define COATTN_MASKED 0
+#include "coattn_fwd_kernels.inc"
+#undef COATTN_MASKED
+#define COATTN_MASKED 1
+#include "coattn_fwd_kernels.inc"
+#undef COATTN_MASKED
 
 struct BwdPrepParams {
   const float* Gu; const float* Gi;
@@ -370,7 +104,8 @@ struct BwdPrepParams {
   int SL;
 };
 
-// grid (B, 2): one workgroup per (sample, side), as coattn_finish_kernel
+// grid (B, 2): one workgroup per (sample, side), as coattn_finish_kernel.  No mask is needed after a masked forward: an undefined
+// position has soft = 0 and max = 0, so it adds 0 to dsum and gets dS = 0 (G and d_soft are finite there).
 __global__ __launch_bounds__(1024) void coattn_bwd_prep_kernel(BwdPrepParams p) {
   extern __shared__ float sm[];  // ds[SL]
   __shared__ float red[16];
@@ -442,8 +177,11 @@ __global__ __launch_bounds__(256) void coattn_bwd_rows_kernel(BwdRowsParams p) {
       const float su = p.soft_u[(long)b * SL + row];
       const int j = ac[row];
       const float w = sc[row];
-      float a0 = su * dau0 + w * T[(long)j * D + lane];
-      float a1 = su * dau1 + w * T[(long)j * D + 64 + lane];
+      float a0 = 0.f, a1 = 0.f;            // j = -1 (masked forward: an undefined position, soft_u = 0): no address from it
+      if (j >= 0) {
+        a0 = su * dau0 + w * T[(long)j * D + lane];
+        a1 = su * dau1 + w * T[(long)j * D + 64 + lane];
+      }
       for (int base = 0; base < SL; base += 64) {
         const int jj = base + lane;
         unsigned long long m = __ballot(jj < SL && ar[jj] == row);
@@ -462,8 +200,11 @@ __global__ __launch_bounds__(256) void coattn_bwd_rows_kernel(BwdRowsParams p) {
     {
       const int k = ar[row];
       const float w = sr[row];
-      float a0 = w * Gu[(long)k * D + lane];
-      float a1 = w * Gu[(long)k * D + 64 + lane];
+      float a0 = 0.f, a1 = 0.f;            // k = -1: as above
+      if (k >= 0) {
+        a0 = w * Gu[(long)k * D + lane];
+        a1 = w * Gu[(long)k * D + 64 + lane];
+      }
       for (int base = 0; base < SL; base += 64) {
         const int kk = base + lane;
         unsigned long long m = __ballot(kk < SL && ac[kk] == row);
@@ -477,7 +218,7 @@ __global__ __launch_bounds__(256) void coattn_bwd_rows_kernel(BwdRowsParams p) {
       }
       p.dT[o + lane] = a0; p.dT[o + 64 + lane] = a1;
       const float si = p.soft_i[(long)b * SL + row];
-      float g0 = si * dai0, g1 = si * dai1;
+      float g0 = k >= 0 ? si * dai0 : 0.f, g1 = k >= 0 ? si * dai1 : 0.f;
       if (p.accumulate) { g0 += p.dGi[o + lane]; g1 += p.dGi[o + 64 + lane]; }
       p.dGi[o + lane] = g0; p.dGi[o + 64 + lane] = g1;
     }
@@ -506,8 +247,11 @@ size_t umpr_coattn_fwd_ws_bytes(int B, int SL) { return coattn_fwd_ws(nullptr, B
 
 int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                          float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax, int* argcol,
-                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores) {
+                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores,
+                         const uint8_t* valid_u, const uint8_t* valid_i) {
   UMPR_REQUIRE(B > 0 && SL > 0, "coattn: bad shape");
+  UMPR_REQUIRE(!valid_u == !valid_i, "coattn: one validity mask without the other");
+  const bool masked = valid_u != nullptr;
   const CoattnFwdWs W = coattn_fwd_ws(ws, B, SL);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "coattn: workspace too small");
   const int nblk = cdiv(SL, 64);
@@ -517,11 +261,15 @@ int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B
   // one 64 x 64 score tile per workgroup: nblk^2 * B workgroups instead of nblk * B serial tile loops
   const int ksplit = nblk;
   ScoreParams sp{T, Gu, W.rpart, W.arpart, W.cpart, W.apart, SL, nblk, ksplit};
-  if (bf16_scores) coattn_scores_bf16_kernel<<<dim3(nblk, B, ksplit), 256, 0, s>>>(sp);
-  else coattn_scores_kernel<<<dim3(nblk, B, ksplit), 256, 0, s>>>(sp);
+  const dim3 sgrid(nblk, B, ksplit);
+  if (masked && bf16_scores) coattn_scores_bf16_masked_kernel<<<sgrid, 256, 0, s>>>(sp, valid_u, valid_i);
+  else if (masked) coattn_scores_masked_kernel<<<sgrid, 256, 0, s>>>(sp, valid_u, valid_i);
+  else if (bf16_scores) coattn_scores_bf16_kernel<<<sgrid, 256, 0, s>>>(sp);
+  else coattn_scores_kernel<<<sgrid, 256, 0, s>>>(sp);
   UMPR_LAUNCH_CHECK("coattn_scores");
   FinishParams fp{Gu, Gi, W.cpart, W.apart, nblk, W.rpart, W.arpart, ksplit, rowmax, argrow, colmax, argcol, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, SL};
-  coattn_finish_kernel<<<dim3(B, 2), 1024, SL * sizeof(float), s>>>(fp);
+  if (masked) coattn_finish_masked_kernel<<<dim3(B, 2), 1024, SL * sizeof(float), s>>>(fp);
+  else coattn_finish_kernel<<<dim3(B, 2), 1024, SL * sizeof(float), s>>>(fp);
   UMPR_LAUNCH_CHECK("coattn_finish");
   return 0;
 }

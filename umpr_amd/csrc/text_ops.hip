@@ -29,66 +29,22 @@ struct SnetFwdParams {
   int S, L;
 };
 
-// one wave per sentence (B*S waves over the grid); the per-sample sum over sentences is snet_senti_kernel
-// NL = ceil(L / 64): lane l % 64 holds position l in slot l / 64 (L <= 64 * NL; the reference's max_sent_length is 20, but
-// review_level='review' makes whole reviews the "sentences", src/dataset.py:24 - supported up to 256 tokens)
-template <int NL>
-__global__ __launch_bounds__(256) void snet_pool_fwd_kernel(SnetFwdParams p, long nsent) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long sent = (long)blockIdx.x * 4 + wave;
-  if (sent >= nsent) return;
-  const float w = p.Ws[lane];
-  const float* X = p.X + sent * p.L * D;
-  const float* U = p.U + sent * p.L * AT;
-  float e[NL];  // lane l % 64 holds e[l / 64]
-#pragma unroll
-  for (int k = 0; k < NL; ++k) e[k] = -INFINITY;
-  int l = 0;
-  for (; l + 3 < p.L; l += 4) {   // four independent reductions in flight (l .. l+3 share a slot: 64 is a multiple of 4)
-    const float v0 = wave_sum(w * U[l * AT + lane]);
-    const float v1 = wave_sum(w * U[(l + 1) * AT + lane]);
-    const float v2 = wave_sum(w * U[(l + 2) * AT + lane]);
-    const float v3 = wave_sum(w * U[(l + 3) * AT + lane]);
-    const int ll = l & 63;
-#pragma unroll
-    for (int k = 0; k < NL; ++k)
-      if (k == (l >> 6)) e[k] = lane == ll ? v0 : lane == ll + 1 ? v1 : lane == ll + 2 ? v2 : lane == ll + 3 ? v3 : e[k];
-  }
-  for (; l < p.L; ++l) {
-    const float v = wave_sum(w * U[l * AT + lane]);
-#pragma unroll
-    for (int k = 0; k < NL; ++k)
-      if (k == (l >> 6) && lane == (l & 63)) e[k] = v;
-  }
-  float mx = e[0];
-#pragma unroll
-  for (int k = 1; k < NL; ++k) mx = fmaxf(mx, e[k]);
-  const float m = wave_max(mx);
-  float ex[NL], zs = 0.f;
-#pragma unroll
-  for (int k = 0; k < NL; ++k) { ex[k] = 64 * k + lane < p.L ? expf(e[k] - m) : 0.f; zs += ex[k]; }
-  const float z = wave_sum(zs);
-  float pr[NL];
-#pragma unroll
-  for (int k = 0; k < NL; ++k) {
-    pr[k] = ex[k] / z;
-    if (64 * k + lane < p.L) p.P[sent * p.L + 64 * k + lane] = pr[k];
-  }
-  float a0 = 0.f, a1 = 0.f;
-  for (l = 0; l < p.L; ++l) {
-    float src = pr[0];
-#pragma unroll
-    for (int k = 1; k < NL; ++k) src = (l >> 6) == k ? pr[k] : src;
-    const float pl = __shfl(src, l & 63, 64);
-    a0 += pl * X[l * D + lane];
-    a1 += pl * X[l * D + 64 + lane];
-  }
-  p.self_atte[sent * D + lane] = a0;
-  p.self_atte[sent * D + 64 + lane] = a1;
-  float ws = 0.f;
-  for (int i = lane; i < p.wl; i += 64) ws += p.word_soft[sent * p.wl + i];
-  ws = wave_sum(ws);
-  if (lane == 0) p.wsum[sent] = ws;
+// snet_pool_fwd_kernel<NL> and snet_pool_fwd_masked_kernel<NL>
+#define SNET_MASKED 0
+#include "snet_pool_fwd.inc"
+#undef SNET_MASKED
+#define SNET_MASKED 1
+#include "snet_pool_fwd.inc"
+#undef SNET_MASKED
+
+// valid[n][l] = l < min(max(len[n], 0), L) && ids[n][l] != pad_id: one thread per token, nothing but the one store
+__global__ __launch_bounds__(256) void token_mask_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ lengths,
+                                                         long total, int L, long pad_id, uint8_t* __restrict__ valid) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long n = i / L;
+  const int l = (int)(i - n * L);
+  valid[i] = l < min(max(lengths[n], 0), L) && ids[i] != pad_id ? 1 : 0;
 }
 
 // senti[b] = sum_s wsum[b][s] * self_atte[b][s]   (fixed order)
@@ -897,7 +853,7 @@ int umpr_sq_err_accumulate_impl(const float* pred, const float* label, long n, d
 // ---- S-Net ---------------------------------------------------------------------------------------------------
 int umpr_snet_fwd_impl(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S,
                        int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
-                       hipStream_t s) {
+                       hipStream_t s, const uint8_t* valid) {
   UMPR_REQUIRE(L >= 1 && L <= 256, "snet: sentence length %d outside 1..256", L);
   UmprGemm g;
   g.A = X; g.lda = D; g.B = Ms; g.ldb = D; g.transB = true; g.C = U; g.ldc = AT; g.M = B * S * L; g.N = AT; g.K = D;
@@ -906,12 +862,23 @@ int umpr_snet_fwd_impl(const float* X, const float* Ms, const float* Ws, const f
   SnetFwdParams p{X, U, Ws, word_soft, wl, P, wsum, self_atte, senti, ld_senti, S, L};
   const long nsent = (long)B * S;
   const unsigned fgrid = (unsigned)((nsent + 3) / 4);
-  if (L <= 64) snet_pool_fwd_kernel<1><<<fgrid, 256, 0, s>>>(p, nsent);
+  if (valid) {
+    if (L <= 64) snet_pool_fwd_masked_kernel<1><<<fgrid, 256, 0, s>>>(p, nsent, valid);
+    else if (L <= 128) snet_pool_fwd_masked_kernel<2><<<fgrid, 256, 0, s>>>(p, nsent, valid);
+    else snet_pool_fwd_masked_kernel<4><<<fgrid, 256, 0, s>>>(p, nsent, valid);
+  } else if (L <= 64) snet_pool_fwd_kernel<1><<<fgrid, 256, 0, s>>>(p, nsent);
   else if (L <= 128) snet_pool_fwd_kernel<2><<<fgrid, 256, 0, s>>>(p, nsent);
   else snet_pool_fwd_kernel<4><<<fgrid, 256, 0, s>>>(p, nsent);
   UMPR_LAUNCH_CHECK("snet_pool_fwd");
   snet_senti_kernel<<<B, D, 0, s>>>(wsum, self_atte, senti, ld_senti, S);
   UMPR_LAUNCH_CHECK("snet_senti");
+  return 0;
+}
+
+int umpr_token_mask_impl(const int64_t* ids, const int32_t* lengths, int N, int L, long pad_id, uint8_t* valid, hipStream_t s) {
+  const long total = (long)N * L;
+  token_mask_kernel<<<(unsigned)((total + 255) / 256), 256, 0, s>>>(ids, lengths, total, L, pad_id, valid);
+  UMPR_LAUNCH_CHECK("token_mask");
   return 0;
 }
 

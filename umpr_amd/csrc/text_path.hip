@@ -148,9 +148,10 @@ size_t umpr_review_net_arena_bytes(int B, int S, int L) { return review_arena(nu
 size_t umpr_review_net_ws_bytes(int B, int S, int L, int E) { return review_ws(nullptr, B, S, L, E).bytes; }
 
 // params: w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, M, Ms_u, Ws_u, Ms_i, Ws_i, W_u, W_i
-int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
-                        const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
-                        float* out, float* ws, size_t ws_bytes, void* stream) {
+// valid_pair (or null): the validity bytes [2N][L] of umpr_token_mask on ids_pair - user rows [B][S*L], then item rows
+static int review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                          const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
+                          float* out, float* ws, size_t ws_bytes, void* stream, const uint8_t* valid_pair) {
   UMPR_REQUIRE(ids_pair && emb && P && lengths && order && arena && out && B > 0 && S > 0 && L > 0, "review_net_fwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_review_net_ws_bytes(B, S, L, E), "review_net_fwd: workspace too small");
   if (poison(ws, ws_bytes, stream) || poison(arena, umpr_review_net_arena_bytes(B, S, L), stream)) return -2;
@@ -161,11 +162,23 @@ int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const 
                                         2 * N, L, A.gru_out, need_grad ? A.gru_saved : nullptr, ws, ws_bytes, stream)) return rc;
   const float* gru_u = A.gru_out;
   const float* gru_i = A.gru_out + (size_t)N * L * D;
-  if (int rc = (b16_scores ? umpr_coattention_fwd_bf16 : umpr_coattention_fwd)(gru_u, gru_i, P[8], B, SL, A.T, A.soft_u, A.soft_i, A.repr_u,
-                                                                         2 * D, A.repr_i, 2 * D, A.colmax, A.argcol, A.rowmax,
-                                                                         A.argrow, ws, ws_bytes, stream)) return rc;
-  if (int rc = umpr_snet_fwd(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D, 2 * D, stream)) return rc;
-  if (int rc = umpr_snet_fwd(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D, 2 * D, stream)) return rc;
+  if (valid_pair) {
+    const uint8_t* valid_u = valid_pair;
+    const uint8_t* valid_i = valid_pair + (size_t)N * L;
+    if (int rc = umpr_coattention_fwd_masked(gru_u, gru_i, P[8], B, SL, A.T, A.soft_u, A.soft_i, A.repr_u, 2 * D, A.repr_i, 2 * D,
+                                             A.colmax, A.argcol, A.rowmax, A.argrow, valid_u, valid_i, b16_scores, ws, ws_bytes,
+                                             stream)) return rc;
+    if (int rc = umpr_snet_fwd_masked(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D,
+                                      2 * D, valid_u, stream)) return rc;
+    if (int rc = umpr_snet_fwd_masked(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D,
+                                      2 * D, valid_i, stream)) return rc;
+  } else {
+    if (int rc = (b16_scores ? umpr_coattention_fwd_bf16 : umpr_coattention_fwd)(gru_u, gru_i, P[8], B, SL, A.T, A.soft_u, A.soft_i, A.repr_u,
+                                                                           2 * D, A.repr_i, 2 * D, A.colmax, A.argcol, A.rowmax,
+                                                                           A.argrow, ws, ws_bytes, stream)) return rc;
+    if (int rc = umpr_snet_fwd(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D, 2 * D, stream)) return rc;
+    if (int rc = umpr_snet_fwd(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D, 2 * D, stream)) return rc;
+  }
   if (B <= 256 && umpr_merge_small())   // one kernel writes the caller's tensor and the arena's copy for backward
     return umpr_review_merge_fwd_impl(A.repr_u, A.repr_i, P[13], P[14], B, out, A.merged, static_cast<hipStream_t>(stream));
   if (int rc = umpr_review_merge_fwd(A.repr_u, A.repr_i, P[13], P[14], B, A.merged, stream)) return rc;
@@ -174,6 +187,20 @@ int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const 
     return -2;
   }
   return 0;
+}
+
+int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                        const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
+                        float* out, float* ws, size_t ws_bytes, void* stream) {
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
+                        stream, nullptr);
+}
+int umpr_review_net_fwd_masked(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                               const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad,
+                               void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair, void* stream) {
+  UMPR_REQUIRE(valid_pair, "review_net_fwd_masked: null validity mask");
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
+                        stream, valid_pair);
 }
 
 // grads: 15 pointers in the order of params, each overwritten; dx_pair (or NULL): the token gradient for a trainable table

@@ -185,7 +185,8 @@ int umpr_gru_bptt(const float* dout, const float* out, const float* saved, const
 size_t umpr_coattn_fwd_ws_bytes(int B, int SL);
 int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                          float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax, int* argcol,
-                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores = 0);
+                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores = 0,
+                         const uint8_t* valid_u = nullptr, const uint8_t* valid_i = nullptr);   // both or neither
 size_t umpr_coattn_bwd_ws_bytes(int B, int SL);
 int umpr_coattn_bwd_impl(const float* Gu, const float* Gi, const float* M, const float* T, const float* soft_u,
                          const float* soft_i, const float* colmax, const int* argcol, const float* rowmax,
@@ -215,7 +216,8 @@ int umpr_bce_head_bwd_impl(const float* att, long ld, const float* w, const floa
 int umpr_sq_err_accumulate_impl(const float* pred, const float* label, long n, double* acc, hipStream_t s);
 int umpr_snet_fwd_impl(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S,
                        int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
-                       hipStream_t s);
+                       hipStream_t s, const uint8_t* valid = nullptr);   // valid [B][S][L] bytes: the masked softmax
+int umpr_token_mask_impl(const int64_t* ids, const int32_t* lengths, int N, int L, long pad_id, uint8_t* valid, hipStream_t s);
 size_t umpr_snet_bwd_ws_bytes_impl(int B, int S, int L);
 int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const float* U, const float* P,
                        const float* wsum, const float* self_atte, const float* d_senti, long ld_ds,

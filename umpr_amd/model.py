@@ -461,12 +461,15 @@ class _SparseRows:
         return self.row_id, self.row_grad
 
 
+PAD_ID = 0      # the <PAD> row of Word2vec: what data.py / synthetic.py pad ids with (<UNK> and <NUM> are words)
+
+
 class _ReviewNetF(torch.autograd.Function):
     """The whole ReviewNet (src/model.py:157-169) on the user+item pair: params = the R-Net GRU's eight, M, Ms_u, Ws_u, Ms_i,
     Ws_i, W_u, W_i."""
 
     @staticmethod
-    def forward(ctx, ids_pair, lens, order, emb, dims, b16_gemm, b16_scores, tok, step, *params):
+    def forward(ctx, ids_pair, lens, order, emb, dims, b16_gemm, b16_scores, mask_padding, tok, step, *params):
         B, S, L = dims
         E = emb.shape[1]
         dev = ids_pair.device
@@ -476,8 +479,16 @@ class _ReviewNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_review_net_ws_bytes", B, S, L, E), dev)
         cp = [_c(p) for p in params]
         keep, parr = _ptr_array(cp)
-        lib().call("umpr_review_net_fwd", ids_pair, emb, E, parr, lens, order, B, S, L, int(b16_gemm), int(b16_scores), int(need),
-                   arena, out, ws, wsb, stream_ptr())
+        if mask_padding:
+            # key-padding mask: one validity byte per token of the pair, from the ids and the device lengths (token id 0 = <PAD>);
+            # the backward reads the arena alone - masked positions are saved with soft = 0 and index -1
+            valid = torch.empty(2 * B * S, L, device=dev, dtype=torch.uint8)
+            lib().call("umpr_token_mask", ids_pair, lens, 2 * B * S, L, PAD_ID, valid, stream_ptr())
+            lib().call("umpr_review_net_fwd_masked", ids_pair, emb, E, parr, lens, order, B, S, L, int(b16_gemm), int(b16_scores),
+                       int(need), arena, out, ws, wsb, valid, stream_ptr())
+        else:
+            lib().call("umpr_review_net_fwd", ids_pair, emb, E, parr, lens, order, B, S, L, int(b16_gemm), int(b16_scores),
+                       int(need), arena, out, ws, wsb, stream_ptr())
         ctx.param_objs = params
         ctx.meta = (B, S, L, int(b16_gemm))
         ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
@@ -505,7 +516,7 @@ class _ReviewNetF(torch.autograd.Function):
             ctx.step.produced(_EmbedStep.R_PAIR, dx)
         if ctx.on_side and any(direct):
             note_gradients_written(ids_pair.device)     # in-place gradients from the side stream: umpr_amd/streams.py
-        return (None,) * 9 + tuple(_grad_returns(ctx.param_objs, tg, direct))
+        return (None,) * 10 + tuple(_grad_returns(ctx.param_objs, tg, direct))
 
 
 class _ControlNetF(torch.autograd.Function):
@@ -1070,6 +1081,11 @@ class UMPR(nn.Module):
             self.photo_augment = PhotoAugment(flip=photo_flip, min_area=photo_crop)
         else:
             self.photo_augment = None
+        # not in the reference: `--mask_padding True` gives the ReviewNet's three softmaxes a key-padding mask - the co-attention
+        # maxima and softmaxes and the S-Nets' word softmax run over real tokens only (position inside the sentence's length and
+        # id != <PAD>), so a sample's prediction no longer depends on how far its batch was padded.  No parameter is added: the
+        # state_dict is the same either way.  The ControlNet is not masked.
+        self.mask_padding = bool(getattr(config, "mask_padding", False))
         self.last_loss_terms = None
         # Parameters whose backward node can write the gradient straight into the optimiser's arena (_grad_targets):
         # everything in the review / control nets (GRU weights accumulate in place across their uses) and, set by VGG16
@@ -1309,7 +1325,8 @@ class UMPR(nn.Module):
                 step = _EmbedStep((ids_pair, ids_pair, ui_reviews) if full else (ids_pair,))
                 tok = _EmbedTable.apply(emb, step, self._sparse_rows)
                 emb = emb.detach()
-            rr = _ReviewNetF.apply(ids_pair, lens, order, emb, (B, S, L), b16_gemm, b16_scores, tok, step,
+            rr = _ReviewNetF.apply(ids_pair, lens, order, emb, (B, S, L), b16_gemm, b16_scores,
+                                   bool(getattr(self, "mask_padding", False)), tok, step,
                                    *self._review_params(device))
             if full:
                 cu, ci, pp, pn = _ControlNetF.apply(ui_reviews.view(B * S_ui, L_ui), ids_pair, lens_ui, ord_ui, lens, order, emb,

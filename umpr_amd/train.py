@@ -142,7 +142,8 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     and a linear warm-up (FusedAdam(lr_scales=, wd_scales=, decoupled_decay=, warmup_steps=)); each is passed on only when it is
     set, and the log then lists the multipliers per prefix and the segments per group.  A model built with `config.photo_flip` /
     `config.photo_crop` augments its photos in every train_step (model.UMPR.photo_augment; validation sees plain photos): one log
-    line says so."""
+    line says so.  `config.mask_padding` is read by the model (model.UMPR.mask_padding); one log line states the setting, the
+    checkpoints record it, and `config.resume` under the other setting is refused by load_checkpoint."""
     accum = int(getattr(config, "accum_steps", 1))
     if accum > 1 and parallel.active():
         raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
@@ -176,6 +177,9 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
         log('Photo augmentation at the fetch, training forwards only: '
             + (f'random crop of {augment.min_area:.0%} to 100% of the image, sides 3:4 to 4:3' if augment.min_area < 1 else 'no crop')
             + ('; horizontal flip with probability 1/2' if augment.flip else '; no flip'))
+    log('Padding mask in the ReviewNet softmaxes (--mask_padding): '
+        + ('on - co-attention and S-Net word attention run over real tokens only' if getattr(model, "mask_padding", False)
+           else 'off - padding takes part, as in the reference'))
     reducer = parallel.GradReducer(opt) if parallel.active() else None
     best_loss, batch_counter, first_epoch, skip, saved = 100, 0, 0, 0, False
     valid_every = int(getattr(config, "valid_every", 500))   # the reference hard-codes 500 (main.py:43)
