@@ -258,6 +258,18 @@ size_t umpr_cnet_head_fwd_ws_bytes(int B, int S, int L, int KS);
 int umpr_cnet_head_fwd(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl, float thr,
                        int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int32_t* argl, float* sp,
                        float* view_p, float* final_, float* ws, size_t ws_bytes, void* stream);
+/* umpr_cnet_head_fwd with a key-padding mask: valid [B][S][L] bytes as umpr_token_mask writes them.  n_s of a
+ * sentence is the length of its LEADING run of valid bytes (a hole ends the run: valid, invalid, valid gives n_s = 1; for what the
+ * loader produces n_s is the number of valid tokens).  Y is computed as above; cmax[k] / argl[k] run over the conv positions
+ * l < lout = n_s for an odd KS, n_s - 1 for an even one (nn.Conv1d(padding=(KS-1)/2) on n_s tokens), first position on ties.  A
+ * sentence with lout < 1 - a padded sentence, or one token under an even KS - is undefined: cmax = +0.0, argl = -1, sp = +0.0,
+ * view_p = +0.0 for every k and v, and it adds exactly +0.0 to final; a sample without a defined sentence gets final = 0.  With
+ * every byte set each output has the bits of umpr_cnet_head_fwd.  Same outputs, saved tensors, launches and workspace size;
+ * umpr_cnet_head_bwd consumes them unchanged (it multiplies by view_p > 0 and writes dY only behind cmax > 0, so argl = -1 forms
+ * no address and an undefined sentence's gradients are +0.0).  A NULL mask is refused before any launch. */
+int umpr_cnet_head_fwd_masked(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl, float thr,
+                              int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int32_t* argl, float* sp,
+                              float* view_p, float* final_, const uint8_t* valid, float* ws, size_t ws_bytes, void* stream);
 size_t umpr_cnet_head_bwd_ws_bytes(int B, int S, int L, int KC, int KS, int V);
 int umpr_cnet_head_bwd(const float* X, const float* Wc, const float* Wl, const float* cmax, const int32_t* argl,
                        const float* sp, const float* view_p, const float* d_final /*or NULL*/,
@@ -306,6 +318,19 @@ int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const 
 int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
                            const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
                            float* const* grads, float* dx_pair, float* ws, size_t ws_bytes, void* stream);
+/* The general forms of the three ReviewNet calls above.  dst_row [2N]: the output row of each input row of the pair in the R-Net
+ * GRU (umpr_embed_gru_bidir_fwd): `order` is the reference's double un-sort (what the calls above pass), the identity 0..2N-1 lets
+ * every sentence keep its own states (--unsort_gru); `order` then only groups similar lengths into tiles.  The backward takes the
+ * dst_row of its forward.  valid_pair and dx_pair may each be NULL.  Same arena, same workspace; dst_row and valid_pair are the
+ * caller's buffers. */
+int umpr_review_net_fwd_ex(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
+                           const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, int b16_scores,
+                           int need_grad, void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair /*or NULL*/,
+                           void* stream);
+int umpr_review_net_bwd_ex(const int64_t* ids_pair, const float* emb, int E, const float* const* params, const int32_t* lengths,
+                           const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, const void* arena,
+                           const float* d_out, float* const* grads, float* dx_pair /*or NULL*/, float* ws, size_t ws_bytes,
+                           void* stream);
 size_t umpr_control_net_arena_bytes(int B, int S_ui, int L_ui, int S, int L, int KC, int V);
 size_t umpr_control_net_ws_bytes(int B, int S_ui, int L_ui, int S, int L, int E, int KC, int KS, int V);
 /* params (16): the C-Net GRU's eight, Wc [KC][128][KS], bc, Wl [V][KC], bl, Ms, Ws, ssW [128], ssb [1];
@@ -326,6 +351,24 @@ int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, cons
                             int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
                             const float* d_ci, const float* d_pp, const float* d_pn, float* const* grads, float* dx_pair,
                             float* dx_ui, float* ws, size_t ws_bytes, void* stream);
+
+/* The general forms of the ControlNet calls: dst_ui [B*S_ui] / dst_pair [2N] as dst_row above for the C-Net GRU's two calls, and
+ * valid_ui [B*S_ui][L_ui] / valid_pair [2N][L] (both or neither; one NULL is refused before any launch): with them the three heads
+ * run as umpr_cnet_head_fwd_masked and the control S-Net as umpr_snet_fwd_masked on valid_ui (--mask_control).  The gate and the
+ * backward need no mask: every term they form carries a factor view_p, +0.0 for an undefined sentence.  dx_pair / dx_ui: both or
+ * neither, as umpr_control_net_bwd_dx.  Same arena, same workspace. */
+int umpr_control_net_fwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* params,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
+                            const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
+                            int V, float thr, int b16_gemm, int need_grad, void* arena, float* c_u, float* c_i, float* prefer_pos,
+                            float* prefer_neg, float* ws, size_t ws_bytes, const uint8_t* valid_ui, const uint8_t* valid_pair,
+                            void* stream);
+int umpr_control_net_bwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* params,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
+                            const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
+                            int V, int b16_gemm, const void* arena, const float* d_cu, const float* d_ci, const float* d_pp,
+                            const float* d_pn, float* const* grads, float* dx_pair, float* dx_ui, float* ws, size_t ws_bytes,
+                            void* stream);
 
 /* ---- K10: VGG16-D feature extractor (torchvision.models.vgg16, call site model.py:204-207,217) ---------------
  * images [n][3][224][224]; params: 32 pointers = 13 x (conv weight [Cout][Cin][3][3], bias) then 3 x (fc weight

@@ -19,6 +19,8 @@
                                                                                       # travels as indices, one kernel pads its ids
     python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
     python main.py --data_dir data/music --mask_padding True                  # attention softmaxes of the ReviewNet skip padding
+    python main.py --data_dir data/music --mask_padding True --mask_control True --unsort_gru True   # ... the ControlNet skips it
+                                                # too and every sentence keeps its own GRU states: batch-invariant predictions
     python main.py --data_dir data/music --train_embedding True --sparse_embedding True   # ... updating only the rows a step names
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 main.py --data_dir synthetic
 
@@ -234,7 +236,7 @@ EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
                  "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False, "ema_decay": 0.0,
                  "lr_scale": "", "wd_scale": "", "decoupled_decay": False, "warmup_steps": 0, "photo_flip": False,
-                 "photo_crop": 1.0, "mask_padding": False}
+                 "photo_crop": 1.0, "mask_padding": False, "mask_control": False, "unsort_gru": False}
 
 
 def check_flags(config):
@@ -249,6 +251,10 @@ def check_flags(config):
         sys.exit(f"--review_store takes True or False, got {config.review_store!r}")
     if not isinstance(config.mask_padding, bool):
         sys.exit(f"--mask_padding takes True or False, got {config.mask_padding!r}")
+    if not isinstance(config.mask_control, bool):
+        sys.exit(f"--mask_control takes True or False, got {config.mask_control!r}")
+    if not isinstance(config.unsort_gru, bool):
+        sys.exit(f"--unsort_gru takes True or False, got {config.unsort_gru!r}")
     if config.sparse_embedding and not config.train_embedding:
         sys.exit("--sparse_embedding needs --train_embedding True: it chooses how a trainable table is updated (the rows a step "
                  "names only, as torch.optim.SparseAdam would)")

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""What does the key-padding mask of the ReviewNet (UMPR(mask_padding=True), --mask_padding True) cost per training step?
+"""What do the key-padding masks - of the ReviewNet (UMPR(mask_padding=True), --mask_padding True) and of the ControlNet
+(UMPR(mask_control=True), --mask_control True) - and own GRU states (--unsort_gru True) cost per training step?
 
 For every workload two model / optimiser pairs live in ONE process - the mask off and on - and take turns in blocks of --steps
 steps (host clock around a block that ends in a device synchronise), so that both see the same machine; the median block of
@@ -7,13 +8,18 @@ steps (host clock around a block that ends in a device synchronise), so that bot
 yardstick.  The on leg adds one umpr_token_mask launch and runs coattn_scores*_masked / coattn_finish_masked / snet_pool_fwd_masked
 in place of the unmasked kernels; nothing else differs.  The batch is the ragged synthetic one (sentence counts 5..20, lengths
 6..20, padded to the batch maximum: about 60 % of the S x L positions are padding).
+Legs: off, on (mask_padding), control (mask_control alone: two umpr_token_mask launches, cnet_head_fwd_masked three times and
+snet_pool_fwd_masked once in place of the unmasked kernels; it changes nothing in the UMPR-R workloads, which have no ControlNet),
+both; unsort (unsort_gru alone: the same kernels, the GRUs write every sentence's states to its own row), all (the three options).
 
     python tools/bench_mask_padding.py [--workloads umpr_r,umpr_r_graphed,full_f32] [--legs off,on] [--rounds 7] [--steps 8]
+    python tools/bench_mask_padding.py --workloads full_f32 --legs off,control,both,unsort,all
 
 Per-kernel times come from one trace per leg (kernel tracing only, no counters in the same run), e.g.
 
     rocprofv3 --kernel-trace --stats -d out_on -o on -- python tools/bench_mask_padding.py --workloads umpr_r --legs on --rounds 3
-    python tools/bench_mask_padding.py --stats out_on        # the rows of coattn_scores*, coattn_finish*, snet_pool_fwd*, token_mask
+    python tools/bench_mask_padding.py --stats out_on        # the rows of coattn_scores*, coattn_finish*, snet_pool_fwd*, token_mask,
+                                                             # cnet_head_fwd* (a trace of legs off,control holds both head kernels)
 
 One JSON line per measurement on stdout."""
 import argparse
@@ -38,7 +44,9 @@ WORKLOADS = {
     "full_f32": dict(dtype="fp32", emb=50, batch=64, review_net_only=False, graphed=False),
 }
 VOCAB = 400003
-KERNELS = ("coattn_scores", "coattn_finish", "snet_pool_fwd", "token_mask", "review_collate")
+KERNELS = ("coattn_scores", "coattn_finish", "snet_pool_fwd", "token_mask", "review_collate", "cnet_head_fwd")
+LEGS = {"off": (False, False, False), "on": (True, False, False), "control": (False, True, False), "both": (True, True, False),
+        "unsort": (False, False, True), "all": (True, True, True)}   # (mask_padding, mask_control, unsort_gru)
 
 
 def build(w, dev, leg):
@@ -48,14 +56,15 @@ def build(w, dev, leg):
     from umpr_amd.optim import FusedAdam
     from umpr_amd.train import train_step
     torch.manual_seed(0)
-    Config.extend({"dtype": "fp32", "mask_padding": False})
+    Config.extend({"dtype": "fp32", "mask_padding": False, "mask_control": False, "unsort_gru": False})
     cfg = Config(argv=[])
-    cfg.review_net_only, cfg.dtype, cfg.mask_padding, cfg.views = w["review_net_only"], w["dtype"], leg == "on", ["v0"]
+    cfg.review_net_only, cfg.dtype, cfg.views = w["review_net_only"], w["dtype"], ["v0"]
+    cfg.mask_padding, cfg.mask_control, cfg.unsort_gru = LEGS[leg]
     P = make_param_state(0, w["emb"], VOCAB, 1, w["review_net_only"])
     model = UMPR(cfg, P["embedding.weight"].numpy())
     model.load_state_dict(P)
     model = model.to(dev)
-    assert model.mask_padding == (leg == "on")
+    assert (model.mask_padding, model.mask_control, model.unsort_gru) == LEGS[leg]
     opt = FusedAdam(model, cfg.learning_rate, cfg.l2_regularization, cfg.lr_decay)
     u, i_, ui, ul, il, uil, photos, labels = make_batch(1234, w["batch"], VOCAB, 1, review_net_only=w["review_net_only"])
     batch = (u.to(dev), i_.to(dev), ui.to(dev), ul, il, uil, photos.to(dev), labels.to(dev))
@@ -98,8 +107,8 @@ def main(argv=None):
     for n in names:
         if n not in WORKLOADS:
             ap.error(f"unknown workload {n!r} (known: {', '.join(WORKLOADS)})")
-    if not legs or any(x not in ("off", "on") for x in legs):
-        ap.error("--legs takes off, on or off,on")
+    if not legs or any(x not in LEGS for x in legs):
+        ap.error("--legs takes a comma-separated choice of " + ", ".join(LEGS))
     if not torch.cuda.is_available():
         sys.exit("bench_mask_padding.py measures on an MI355X: no GPU found")
     dev = torch.device("cuda:0")
@@ -121,7 +130,8 @@ def main(argv=None):
                 ms[leg].append(1e3 * (time.perf_counter() - t0) / a.steps)
         for leg in legs:
             med = statistics.median(ms[leg])
-            line = {"workload": name, **w, "mask_padding": leg, "shape_B_S_L": sides[leg][2], "padding_share": round(sides[leg][1], 3),
+            line = {"workload": name, **w, "leg": leg, "mask_padding": "on" if LEGS[leg][0] else "off",
+                    "mask_control": "on" if LEGS[leg][1] else "off", "unsort_gru": "on" if LEGS[leg][2] else "off", "shape_B_S_L": sides[leg][2], "padding_share": round(sides[leg][1], 3),
                     "steps_per_block": a.steps, "rounds": a.rounds, "ms_per_step": round(med, 4),
                     "min_max": [round(min(ms[leg]), 4), round(max(ms[leg]), 4)], "samples_per_s": round(w["batch"] / (med * 1e-3), 1)}
             if "off" in ms:

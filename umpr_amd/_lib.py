@@ -50,6 +50,7 @@ SIGNATURES = {
     "umpr_review_merge_bwd": ("ppppppipppppzp", "i"),
     "umpr_cnet_head_fwd_ws_bytes": ("iiii", "z"),
     "umpr_cnet_head_fwd": ("pppppfiiiiiipppppppzp", "i"),
+    "umpr_cnet_head_fwd_masked": ("pppppfiiiiiippppppppzp", "i"),
     "umpr_cnet_head_bwd_ws_bytes": ("iiiiii", "z"),
     "umpr_cnet_head_bwd": ("pppppppppiiiiiipiipppppzp", "i"),
     "umpr_control_gate_fwd": ("pppppiiippppp", "i"),
@@ -102,11 +103,15 @@ SIGNATURES = {
     "umpr_review_net_fwd_masked": ("ppipppiiiiiipppzpp", "i"),
     "umpr_review_net_bwd": ("ppipppiiiippppzp", "i"),
     "umpr_review_net_bwd_dx": ("ppipppiiiipppppzp", "i"),
+    "umpr_review_net_fwd_ex": ("ppippppiiiiiipppzpp", "i"),
+    "umpr_review_net_bwd_ex": ("ppippppiiiipppppzp", "i"),
     "umpr_control_net_arena_bytes": ("iiiiiii", "z"),
     "umpr_control_net_ws_bytes": ("iiiiiiiii", "z"),
     "umpr_control_net_fwd": ("pppipppppiiiiiiiifiippppppzp", "i"),
     "umpr_control_net_bwd": ("pppipppppiiiiiiiiipppppppzp", "i"),
     "umpr_control_net_bwd_dx": ("pppipppppiiiiiiiiipppppppppzp", "i"),
+    "umpr_control_net_fwd_ex": ("pppipppppppiiiiiiiifiippppppzppp", "i"),
+    "umpr_control_net_bwd_ex": ("pppipppppppiiiiiiiiipppppppppzp", "i"),
     "umpr_head_fwd": ("pppppppppppppfiiipppppppp", "i"),
     "umpr_head_bwd": ("pppppppppppfiiippppppppppppppppppppp", "i"),
     "umpr_photo_resize_u8": ("pzpiiipp", "i"),

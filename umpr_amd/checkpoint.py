@@ -5,7 +5,8 @@ scheduler / epoch state.  Here a checkpoint is a plain dict of tensors and numbe
 ``torch.load(..., weights_only=True)``): the model ``state_dict`` under the reference's key names - so the weights
 move between the two implementations by ``state_dict`` - plus, optionally, the Adam moments, step count and learning
 rate for an exact resume.  ``mask_padding`` records whether the ReviewNet ran with its padding mask (model.UMPR.mask_padding):
-loading into a model built with the other setting is refused, and a file without the key counts as False.
+loading into a model built with the other setting is refused, and a file without the key counts as False.  ``mask_control`` and
+``unsort_gru`` (model.UMPR.mask_control, .unsort_gru) are recorded and checked in the same way.
 """
 from __future__ import annotations
 
@@ -32,6 +33,8 @@ def save_checkpoint(path, model, opt=None, epoch=0, batch_counter=0, best_loss=N
     # forward-call counters that seed the dropout masks (model.VGG16._calls): part of an exact resume
     # --mask_padding changes what the ReviewNet computes without adding a parameter: recorded, and checked by load_checkpoint
     ck["mask_padding"] = bool(getattr(model, "mask_padding", False))
+    ck["mask_control"] = bool(getattr(model, "mask_control", False))     # likewise: the ControlNet's mask ...
+    ck["unsort_gru"] = bool(getattr(model, "unsort_gru", False))         # ... and which sentence's GRU states a row holds
     ck["rng_calls"] = {n: int(m._calls) for n, m in model.named_modules() if hasattr(m, "_calls")}
     if opt is not None:
         ck["optimizer"] = opt.state_dict()
@@ -56,6 +59,11 @@ def load_checkpoint(path, model, opt=None, map_location="cpu", weights="model"):
         raise ValueError(f"{path} was written with --mask_padding {saved_mask} and the model is built with --mask_padding "
                          f"{not saved_mask}: resume or test it with --mask_padding {saved_mask} (the weights themselves are "
                          "interchangeable by state_dict)")
+    for opt_name in ("mask_control", "unsort_gru"):
+        was = bool(ck.get(opt_name, False)) if sd is not ck else False
+        if was != bool(getattr(model, opt_name, False)):
+            raise ValueError(f"{path} was written with --{opt_name} {was} and the model is built with --{opt_name} {not was}: "
+                             f"resume or test it with --{opt_name} {was} (the weights themselves are interchangeable by state_dict)")
     ema = None
     if weights == "ema":                                # before anything is written
         ema = ck["optimizer"].get("ema") if isinstance(ck, dict) and isinstance(ck.get("optimizer"), dict) else None

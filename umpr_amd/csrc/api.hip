@@ -468,6 +468,13 @@ int umpr_cnet_head_fwd(const float* X, const float* Wc, const float* bc, const f
   return umpr_cnet_head_fwd_impl(X, Wc, bc, Wl, bl, thr, B, S_, L, KC, KS, V, Y, cmax, argl, sp, view_p, final_, ws,
                                  ws_bytes, S(stream));
 }
+int umpr_cnet_head_fwd_masked(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl, float thr,
+                              int B, int S_, int L, int KC, int KS, int V, float* Y, float* cmax, int32_t* argl, float* sp,
+                              float* view_p, float* final_, const uint8_t* valid, float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(valid, "cnet_head_fwd_masked: null validity mask");
+  return umpr_cnet_head_fwd_impl(X, Wc, bc, Wl, bl, thr, B, S_, L, KC, KS, V, Y, cmax, argl, sp, view_p, final_, ws,
+                                 ws_bytes, S(stream), valid);
+}
 size_t umpr_cnet_head_bwd_ws_bytes(int B, int S_, int L, int KC, int KS, int V) {
   return umpr_cnet_bwd_ws_bytes(B, S_, L, KC, KS, V);
 }

@@ -189,6 +189,52 @@ __global__ __launch_bounds__(256) void cnet_head_fwd_kernel(CnetHeadFwdParams p,
   }
 }
 
+// cnet_head_fwd_kernel with valid [B][S][L] bytes (umpr_cnet_head_fwd_masked): a kernel of its own, so that the one above keeps its code.
+// n_s = the length of the sentence's leading run of valid bytes (the wave reads them lane-strided, one ballot per 64); the
+// maximum runs over the conv positions l < lout = n_s - even (even = 1 for an even KS: nn.Conv1d(padding=(KS-1)/2) on n_s
+// tokens), first position on ties as above - so the wave reads lout rows of Y, not Lout.  A sentence with lout < 1 is undefined:
+// cmax = +0.0, argl = -1, sp = view_p = +0.0, and Y is not read.  With every byte set lout = Lout: the bits of the kernel above.
+__global__ __launch_bounds__(256) void cnet_head_fwd_masked_kernel(CnetHeadFwdParams p, long nsent,
+                                                                   const uint8_t* __restrict__ valid, int even) {
+  extern __shared__ float sm[];  // cm[4][KC]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long sent = (long)blockIdx.x * 4 + wave;
+  if (sent >= nsent) return;
+  const uint8_t* vb = valid + sent * p.L;
+  int ns = p.L;
+  for (int base = 0; base < p.L; base += 64) {            // wave-uniform: every lane sees the same ballot
+    const int l = base + lane;
+    const unsigned long long bad = __ballot(l < p.L && vb[l] == 0);
+    if (bad) { ns = base + __ffsll(bad) - 1; break; }
+  }
+  const int lout = ns - even;                               // <= p.Lout = L - even
+  if (lout < 1) {
+    for (int k = lane; k < p.KC; k += 64) { p.cmax[sent * p.KC + k] = 0.f; p.argl[sent * p.KC + k] = -1; }
+    for (int v = lane; v < p.V; v += 64) { p.sp[sent * p.V + v] = 0.f; p.view_p[sent * p.V + v] = 0.f; }
+    return;
+  }
+  float* cm = sm + wave * p.KC;
+  const float* Y = p.Y + sent * p.L * p.KC;
+  for (int k = lane; k < p.KC; k += 64) {
+    float m = Y[k]; int a = 0;
+    for (int l = 1; l < lout; ++l) {
+      const float y = Y[l * p.KC + k];
+      if (y > m) { m = y; a = l; }
+    }
+    cm[k] = m;
+    p.cmax[sent * p.KC + k] = m; p.argl[sent * p.KC + k] = a;
+  }
+  // cm is written and read by this wave only: a wave executes in lock-step, no barrier needed
+  for (int v = 0; v < p.V; ++v) {
+    float a = 0.f;
+    for (int k = lane; k < p.KC; k += 64) a += p.Wl[v * p.KC + k] * cm[k];
+    a = wave_sum(a) + p.bl[v];
+    const float sg = sigmoidf_(a);
+    const float vp = sg < p.thr ? 0.f : sg;
+    if (lane == 0) { p.sp[sent * p.V + v] = sg; p.view_p[sent * p.V + v] = vp; }
+  }
+}
+
 // final[b][v] = sum_s view_p[b][s][v]^2   (fixed order)
 __global__ void cnet_final_kernel(const float* __restrict__ view_p, float* __restrict__ final_, int S, int V) {
   const int b = blockIdx.x;
@@ -925,7 +971,8 @@ size_t umpr_cnet_fwd_ws_bytes(int B, int S, int L, int KS) { (void)B; (void)S; (
 
 int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl,
                             float thr, int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int* argl,
-                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, hipStream_t s) {
+                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, hipStream_t s,
+                            const uint8_t* valid) {
   UMPR_REQUIRE(ws_bytes >= umpr_cnet_fwd_ws_bytes(B, S, L, KS), "cnet: workspace too small");
   const long R = (long)B * S * L;
   // nn.Conv1d(padding=(KS-1)/2) (src/model.py:93): an even KS yields L - 1 positions; the window GEMM computes L (the last one
@@ -942,7 +989,8 @@ int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, co
   if (int rc = umpr_gemm(g, s)) return rc;
   CnetHeadFwdParams p{Y, Wl, bl, thr, cmax, argl, sp, view_p, final_, S, L, KC, V, Lout};
   const long nsent = (long)B * S;
-  cnet_head_fwd_kernel<<<(unsigned)((nsent + 3) / 4), 256, 4 * KC * sizeof(float), s>>>(p, nsent);
+  if (valid) cnet_head_fwd_masked_kernel<<<(unsigned)((nsent + 3) / 4), 256, 4 * KC * sizeof(float), s>>>(p, nsent, valid, (KS & 1) ^ 1);
+  else cnet_head_fwd_kernel<<<(unsigned)((nsent + 3) / 4), 256, 4 * KC * sizeof(float), s>>>(p, nsent);
   UMPR_LAUNCH_CHECK("cnet_head_fwd");
   cnet_final_kernel<<<B, 64, 0, s>>>(view_p, final_, S, V);
   UMPR_LAUNCH_CHECK("cnet_final");

@@ -149,16 +149,17 @@ size_t umpr_review_net_ws_bytes(int B, int S, int L, int E) { return review_ws(n
 
 // params: w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, M, Ms_u, Ws_u, Ms_i, Ws_i, W_u, W_i
 // valid_pair (or null): the validity bytes [2N][L] of umpr_token_mask on ids_pair - user rows [B][S*L], then item rows
+// dst_row: the output row of each input row of the pair (umpr_embed_gru_bidir_fwd): `order` for the reference's double un-sort
 static int review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
-                          const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
-                          float* out, float* ws, size_t ws_bytes, void* stream, const uint8_t* valid_pair) {
-  UMPR_REQUIRE(ids_pair && emb && P && lengths && order && arena && out && B > 0 && S > 0 && L > 0, "review_net_fwd: bad arguments");
+                          const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, int b16_scores,
+                          int need_grad, void* arena, float* out, float* ws, size_t ws_bytes, void* stream, const uint8_t* valid_pair) {
+  UMPR_REQUIRE(ids_pair && emb && P && lengths && order && dst_row && arena && out && B > 0 && S > 0 && L > 0, "review_net_fwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_review_net_ws_bytes(B, S, L, E), "review_net_fwd: workspace too small");
   if (poison(ws, ws_bytes, stream) || poison(arena, umpr_review_net_arena_bytes(B, S, L), stream)) return -2;
   const ReviewArena A = review_arena(arena, B, S, L);
   const int N = B * S, SL = S * L;
   UmprB16Scope b16(b16_gemm);
-  if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], lengths, order, order,
+  if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], lengths, order, dst_row,
                                         2 * N, L, A.gru_out, need_grad ? A.gru_saved : nullptr, ws, ws_bytes, stream)) return rc;
   const float* gru_u = A.gru_out;
   const float* gru_i = A.gru_out + (size_t)N * L * D;
@@ -192,22 +193,29 @@ static int review_net_fwd(const int64_t* ids_pair, const float* emb, int E, cons
 int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
                         float* out, float* ws, size_t ws_bytes, void* stream) {
-  return review_net_fwd(ids_pair, emb, E, P, lengths, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
                         stream, nullptr);
 }
 int umpr_review_net_fwd_masked(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                                const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad,
                                void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair, void* stream) {
   UMPR_REQUIRE(valid_pair, "review_net_fwd_masked: null validity mask");
-  return review_net_fwd(ids_pair, emb, E, P, lengths, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
                         stream, valid_pair);
+}
+int umpr_review_net_fwd_ex(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                           const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, int b16_scores,
+                           int need_grad, void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair,
+                           void* stream) {
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, dst_row, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws,
+                        ws_bytes, stream, valid_pair);
 }
 
 // grads: 15 pointers in the order of params, each overwritten; dx_pair (or NULL): the token gradient for a trainable table
-int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
-                           const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
-                           float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
-  UMPR_REQUIRE(ids_pair && emb && P && G && lengths && order && arena && d_out, "review_net_bwd: bad arguments");
+static int review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                          const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, const void* arena,
+                          const float* d_out, float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
+  UMPR_REQUIRE(ids_pair && emb && P && G && lengths && order && dst_row && arena && d_out, "review_net_bwd: bad arguments");
   const ReviewWs W = review_ws(ws, B, S, L, E);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "review_net_bwd: workspace too small");
   if (poison(ws, ws_bytes, stream)) return -2;
@@ -232,8 +240,18 @@ int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, con
   if (int rc = umpr_coattention_bwd(gru_u, gru_i, P[8], A.T, A.soft_u, A.soft_i, A.colmax, A.argcol, A.rowmax, A.argrow, d_repr_u,
                                     2 * D, d_repr_i, 2 * D, ds_u, ds_i, B, (int)SL, dGu, dGi, G[8], 1, sws, swsb, stream)) return rc;
   debug_sync(4);
-  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], lengths, order, order, (int)(2 * N), L, dG, A.gru_out, A.gru_saved,
+  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], lengths, order, dst_row, (int)(2 * N), L, dG, A.gru_out, A.gru_saved,
                                      G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_pair, 0, sws, swsb, stream);
+}
+int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                           const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
+                           float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
+  return review_net_bwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm, arena, d_out, G, dx_pair, ws, ws_bytes, stream);
+}
+int umpr_review_net_bwd_ex(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
+                           const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, const void* arena,
+                           const float* d_out, float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
+  return review_net_bwd(ids_pair, emb, E, P, lengths, order, dst_row, B, S, L, b16_gemm, arena, d_out, G, dx_pair, ws, ws_bytes, stream);
 }
 int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
@@ -250,11 +268,17 @@ size_t umpr_control_net_ws_bytes(int B, int S_ui, int L_ui, int S, int L, int E,
 }
 
 // params: the C-Net GRU's eight (as above), Wc [KC][128][KS], bc, Wl [V][KC], bl, Ms, Ws, ssW [128], ssb [1]
-int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
-                         const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
-                         int S_ui, int L_ui, int S, int L, int KC, int KS, int V, float thr, int b16_gemm, int need_grad, void* arena,
-                         float* c_u, float* c_i, float* prefer_pos, float* prefer_neg, float* ws, size_t ws_bytes, void* stream) {
-  UMPR_REQUIRE(ids_ui && ids_pair && emb && P && arena && c_u && c_i && prefer_pos && prefer_neg, "control_net_fwd: bad arguments");
+// dst_ui / dst_pair: the output row of each input row of the two GRU calls (ord_* for the reference's double un-sort);
+// valid_ui [B*S_ui][L_ui], valid_pair [2N][L] (both or neither): the validity bytes of umpr_token_mask on ids_ui / ids_pair
+static int control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                           const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
+                           const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
+                           int V, float thr, int b16_gemm, int need_grad, void* arena, float* c_u, float* c_i, float* prefer_pos,
+                           float* prefer_neg, float* ws, size_t ws_bytes, void* stream, const uint8_t* valid_ui,
+                           const uint8_t* valid_pair) {
+  UMPR_REQUIRE((valid_ui == nullptr) == (valid_pair == nullptr), "control_net_fwd: valid_ui and valid_pair go together");
+  UMPR_REQUIRE(ids_ui && ids_pair && emb && P && arena && c_u && c_i && prefer_pos && prefer_neg && dst_ui && dst_pair,
+               "control_net_fwd: bad arguments");
   const ControlWs W = control_ws(ws, B, S_ui, L_ui, S, L, E, KC, KS, V);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "control_net_fwd: workspace too small");
   if (poison(ws, ws_bytes, stream) || poison(arena, umpr_control_net_arena_bytes(B, S_ui, L_ui, S, L, KC, V), stream)) return -2;
@@ -262,19 +286,28 @@ int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
   const long Nui = (long)B * S_ui, N = (long)B * S;
   hipStream_t s = static_cast<hipStream_t>(stream);
   UmprB16Scope b16(b16_gemm);
-  if (int rc = umpr_embed_gru_bidir_fwd(ids_ui, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_ui, ord_ui, ord_ui, (int)Nui,
+  if (int rc = umpr_embed_gru_bidir_fwd(ids_ui, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_ui, ord_ui, dst_ui, (int)Nui,
                                         L_ui, A.gru_ui, need_grad ? A.saved_ui : nullptr, ws, ws_bytes, stream)) return rc;
-  if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_pair, ord_pair, ord_pair,
+  if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_pair, ord_pair, dst_pair,
                                         (int)(2 * N), L, A.gru_pair, need_grad ? A.saved_pair : nullptr, ws, ws_bytes, stream)) return rc;
   float* Y = W.Y;   // (the GRUs above used the whole buffer)
   float* sws = W.stage; const size_t swsb = ws_bytes - W.prefix;
   const float* X[3] = {A.gru_ui, A.gru_pair, A.gru_pair + (size_t)N * L * D};
   const int ss[3] = {S_ui, S, S}, ll[3] = {L_ui, L, L};
-  for (int q = 0; q < 3; ++q)
-    if (int rc = umpr_cnet_head_fwd(X[q], P[8], P[9], P[10], P[11], thr, B, ss[q], ll[q], KC, KS, V, Y, A.h[q].cmax, A.h[q].argl,
-                                    A.h[q].sp, A.h[q].vp, A.h[q].fin, sws, swsb, stream)) return rc;
-  // control S-Net weighted by view_p (model.py:185); its sentiment vector is not used: written into scratch
-  if (int rc = umpr_snet_fwd(A.gru_ui, P[12], P[13], A.h[0].vp, V, B, S_ui, L_ui, A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, Y, D, stream)) return rc;
+  if (valid_ui) {
+    const uint8_t* vv[3] = {valid_ui, valid_pair, valid_pair + (size_t)N * L};
+    for (int q = 0; q < 3; ++q)
+      if (int rc = umpr_cnet_head_fwd_masked(X[q], P[8], P[9], P[10], P[11], thr, B, ss[q], ll[q], KC, KS, V, Y, A.h[q].cmax,
+                                             A.h[q].argl, A.h[q].sp, A.h[q].vp, A.h[q].fin, vv[q], sws, swsb, stream)) return rc;
+    if (int rc = umpr_snet_fwd_masked(A.gru_ui, P[12], P[13], A.h[0].vp, V, B, S_ui, L_ui, A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, Y, D,
+                                      valid_ui, stream)) return rc;
+  } else {
+    for (int q = 0; q < 3; ++q)
+      if (int rc = umpr_cnet_head_fwd(X[q], P[8], P[9], P[10], P[11], thr, B, ss[q], ll[q], KC, KS, V, Y, A.h[q].cmax, A.h[q].argl,
+                                      A.h[q].sp, A.h[q].vp, A.h[q].fin, sws, swsb, stream)) return rc;
+    // control S-Net weighted by view_p (model.py:185); its sentiment vector is not used: written into scratch
+    if (int rc = umpr_snet_fwd(A.gru_ui, P[12], P[13], A.h[0].vp, V, B, S_ui, L_ui, A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, Y, D, stream)) return rc;
+  }
   if (int rc = umpr_control_gate_fwd(A.sn.sa, P[14], P[15], A.h[0].vp, A.h[0].fin, B, S_ui, V, A.senti, A.vs, prefer_pos, prefer_neg, stream)) return rc;
   if (hipMemcpyAsync(c_u, A.h[1].fin, (size_t)B * V * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
       hipMemcpyAsync(c_i, A.h[2].fin, (size_t)B * V * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
@@ -283,16 +316,33 @@ int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
   }
   return 0;
 }
+int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                         const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
+                         int S_ui, int L_ui, int S, int L, int KC, int KS, int V, float thr, int b16_gemm, int need_grad, void* arena,
+                         float* c_u, float* c_i, float* prefer_pos, float* prefer_neg, float* ws, size_t ws_bytes, void* stream) {
+  return control_net_fwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, ord_ui, len_pair, ord_pair, ord_pair, B, S_ui, L_ui, S, L, KC, KS,
+                         V, thr, b16_gemm, need_grad, arena, c_u, c_i, prefer_pos, prefer_neg, ws, ws_bytes, stream, nullptr, nullptr);
+}
+int umpr_control_net_fwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
+                            const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
+                            int V, float thr, int b16_gemm, int need_grad, void* arena, float* c_u, float* c_i, float* prefer_pos,
+                            float* prefer_neg, float* ws, size_t ws_bytes, const uint8_t* valid_ui, const uint8_t* valid_pair,
+                            void* stream) {
+  return control_net_fwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, dst_ui, len_pair, ord_pair, dst_pair, B, S_ui, L_ui, S, L, KC, KS,
+                         V, thr, b16_gemm, need_grad, arena, c_u, c_i, prefer_pos, prefer_neg, ws, ws_bytes, stream, valid_ui, valid_pair);
+}
 
 // d_cu, d_ci, d_pp, d_pn [B][V]; grads: 16 pointers in the order of params, each overwritten
 // dx_pair / dx_ui (both or neither): the token gradients of the C-Net GRU's two calls for a trainable table
-int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
-                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
-                            int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
-                            const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* dx_pair, float* dx_ui,
-                            float* ws, size_t ws_bytes, void* stream) {
+static int control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                           const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
+                           const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
+                           int V, int b16_gemm, const void* arena, const float* d_cu, const float* d_ci, const float* d_pp,
+                           const float* d_pn, float* const* G, float* dx_pair, float* dx_ui, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE((dx_pair == nullptr) == (dx_ui == nullptr), "control_net_bwd: dx_pair and dx_ui go together");
-  UMPR_REQUIRE(ids_ui && ids_pair && emb && P && G && arena && d_cu && d_ci && d_pp && d_pn, "control_net_bwd: bad arguments");
+  UMPR_REQUIRE(ids_ui && ids_pair && emb && P && G && arena && d_cu && d_ci && d_pp && d_pn && dst_ui && dst_pair,
+               "control_net_bwd: bad arguments");
   const ControlWs W = control_ws(ws, B, S_ui, L_ui, S, L, E, KC, KS, V);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "control_net_bwd: workspace too small");
   if (poison(ws, ws_bytes, stream)) return -2;
@@ -315,11 +365,28 @@ int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, cons
   for (int q = 0; q < 3; ++q)   // the ui head adds onto the S-Net's dX and writes the weight gradients; the other two add onto those
     if (int rc = umpr_cnet_head_bwd(X[q], P[8], P[10], A.h[q].cmax, A.h[q].argl, A.h[q].sp, A.h[q].vp, dfin[q], dvp[q], B, ss[q], ll[q],
                                     KC, KS, V, dX[q], q == 0 ? 1 : 0, q == 0 ? 0 : 1, G[8], G[9], G[10], G[11], sws, swsb, stream)) return rc;
-  if (int rc = umpr_embed_gru_bidir_bwd_dx(ids_ui, emb, E, P[1], P[5], len_ui, ord_ui, ord_ui, (int)Nui, L_ui, dX_ui, A.gru_ui, A.saved_ui,
+  if (int rc = umpr_embed_gru_bidir_bwd_dx(ids_ui, emb, E, P[1], P[5], len_ui, ord_ui, dst_ui, (int)Nui, L_ui, dX_ui, A.gru_ui, A.saved_ui,
                                            G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_ui, 0, sws, swsb, stream)) return rc;
-  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], len_pair, ord_pair, ord_pair, (int)(2 * N), L, dX_pair, A.gru_pair,
+  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], len_pair, ord_pair, dst_pair, (int)(2 * N), L, dX_pair, A.gru_pair,
                                      A.saved_pair, G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 1, P[0], P[4], dx_pair, 0, sws, swsb,
                                      stream);
+}
+int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
+                            int S_ui, int L_ui, int S, int L, int KC, int KS, int V, int b16_gemm, const void* arena, const float* d_cu,
+                            const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* dx_pair, float* dx_ui,
+                            float* ws, size_t ws_bytes, void* stream) {
+  return control_net_bwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, ord_ui, len_pair, ord_pair, ord_pair, B, S_ui, L_ui, S, L, KC, KS,
+                         V, b16_gemm, arena, d_cu, d_ci, d_pp, d_pn, G, dx_pair, dx_ui, ws, ws_bytes, stream);
+}
+int umpr_control_net_bwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
+                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
+                            const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
+                            int V, int b16_gemm, const void* arena, const float* d_cu, const float* d_ci, const float* d_pp,
+                            const float* d_pn, float* const* G, float* dx_pair, float* dx_ui, float* ws, size_t ws_bytes,
+                            void* stream) {
+  return control_net_bwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, dst_ui, len_pair, ord_pair, dst_pair, B, S_ui, L_ui, S, L, KC, KS,
+                         V, b16_gemm, arena, d_cu, d_ci, d_pp, d_pn, G, dx_pair, dx_ui, ws, ws_bytes, stream);
 }
 int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                          const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,

@@ -226,7 +226,8 @@ int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const f
 size_t umpr_cnet_fwd_ws_bytes(int B, int S, int L, int KS);
 int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl,
                             float thr, int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int* argl,
-                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, hipStream_t s);
+                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, hipStream_t s,
+                            const uint8_t* valid = nullptr);   // valid [B][S][L] bytes: the masked head
 size_t umpr_cnet_bwd_ws_bytes(int B, int S, int L, int KC, int KS, int V);
 int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, const float* cmax, const int* argl,
                             const float* sp, const float* view_p, const float* d_final, const float* d_view_p, int B,

@@ -463,13 +463,30 @@ class _SparseRows:
 
 PAD_ID = 0      # the <PAD> row of Word2vec: what data.py / synthetic.py pad ids with (<UNK> and <NUM> are words)
 
+_IDENTITY = {}  # (device, n) -> int32 arange(n): the GRUs' dst_row under --unsort_gru; static, so a captured step replays it
+
+
+def _identity_rows(n, device):
+    t = _IDENTITY.get((device, n))
+    if t is None:
+        t = _IDENTITY[(device, n)] = torch.arange(n, dtype=torch.int32, device=device)
+    return t
+
+
+def _token_valid(ids, lens, n, L):
+    """one validity byte per token (umpr_token_mask), filled on the current stream into a buffer of this node's own"""
+    valid = torch.empty(n, L, device=ids.device, dtype=torch.uint8)
+    lib().call("umpr_token_mask", ids, lens, n, L, PAD_ID, valid, stream_ptr())
+    return valid
+
 
 class _ReviewNetF(torch.autograd.Function):
     """The whole ReviewNet (src/model.py:157-169) on the user+item pair: params = the R-Net GRU's eight, M, Ms_u, Ws_u, Ms_i,
     Ws_i, W_u, W_i."""
 
     @staticmethod
-    def forward(ctx, ids_pair, lens, order, emb, dims, b16_gemm, b16_scores, mask_padding, tok, step, *params):
+    def forward(ctx, ids_pair, lens, order, dst, emb, dims, b16_gemm, b16_scores, mask_padding, tok, step, *params):
+        # dst: None (the reference's double un-sort, dst_row = order) or the GRU's output rows [2N] (--unsort_gru: the identity)
         B, S, L = dims
         E = emb.shape[1]
         dev = ids_pair.device
@@ -479,7 +496,11 @@ class _ReviewNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_review_net_ws_bytes", B, S, L, E), dev)
         cp = [_c(p) for p in params]
         keep, parr = _ptr_array(cp)
-        if mask_padding:
+        if dst is not None:
+            valid = _token_valid(ids_pair, lens, 2 * B * S, L) if mask_padding else None
+            lib().call("umpr_review_net_fwd_ex", ids_pair, emb, E, parr, lens, order, dst, B, S, L, int(b16_gemm), int(b16_scores),
+                       int(need), arena, out, ws, wsb, valid, stream_ptr())
+        elif mask_padding:
             # key-padding mask: one validity byte per token of the pair, from the ids and the device lengths (token id 0 = <PAD>);
             # the backward reads the arena alone - masked positions are saved with soft = 0 and index -1
             valid = torch.empty(2 * B * S, L, device=dev, dtype=torch.uint8)
@@ -493,6 +514,7 @@ class _ReviewNetF(torch.autograd.Function):
         ctx.meta = (B, S, L, int(b16_gemm))
         ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
         ctx.step = step if tok is not None else None     # a trainable table: the backward also hands out the token gradient
+        ctx.dst = dst
         if need:
             ctx.save_for_backward(ids_pair, lens, order, emb, arena, *cp)
         return out
@@ -506,17 +528,23 @@ class _ReviewNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_review_net_ws_bytes", B, S, L, E), ids_pair.device)
         keep_p, parr = _ptr_array(cp)
         keep_g, garr = _ptr_array(tg)
-        if ctx.step is None:
+        dx = None
+        if ctx.step is not None:
+            dx = torch.empty(ids_pair.numel(), E, device=ids_pair.device, dtype=torch.float32)
+        if ctx.dst is not None:
+            lib().call("umpr_review_net_bwd_ex", ids_pair, emb, E, parr, lens, order, ctx.dst, B, S, L, b16, arena, _c(d_out), garr,
+                       dx, ws, wsb, stream_ptr())
+        elif dx is None:
             lib().call("umpr_review_net_bwd", ids_pair, emb, E, parr, lens, order, B, S, L, b16, arena, _c(d_out), garr, ws, wsb,
                        stream_ptr())
         else:
-            dx = torch.empty(ids_pair.numel(), E, device=ids_pair.device, dtype=torch.float32)
             lib().call("umpr_review_net_bwd_dx", ids_pair, emb, E, parr, lens, order, B, S, L, b16, arena, _c(d_out), garr, dx, ws,
                        wsb, stream_ptr())
+        if dx is not None:
             ctx.step.produced(_EmbedStep.R_PAIR, dx)
         if ctx.on_side and any(direct):
             note_gradients_written(ids_pair.device)     # in-place gradients from the side stream: umpr_amd/streams.py
-        return (None,) * 10 + tuple(_grad_returns(ctx.param_objs, tg, direct))
+        return (None,) * 11 + tuple(_grad_returns(ctx.param_objs, tg, direct))
 
 
 class _ControlNetF(torch.autograd.Function):
@@ -524,7 +552,10 @@ class _ControlNetF(torch.autograd.Function):
     control S-Net Ms / Ws, SS-Net weight / bias.  Returns (c_u, c_i, prefer_pos, prefer_neg)."""
 
     @staticmethod
-    def forward(ctx, ids_ui, ids_pair, lens_ui, ord_ui, lens, order, emb, dims, thr, b16_gemm, tok, step, *params):
+    def forward(ctx, ids_ui, ids_pair, lens_ui, ord_ui, lens, order, dsts, mask_control, emb, dims, thr, b16_gemm, tok, step,
+                *params):
+        # dsts: None (dst_row = order in both GRU calls) or (dst_ui, dst_pair) (--unsort_gru); mask_control: the three heads and the
+        # control S-Net run over each sentence's real tokens (--mask_control)
         B, S_ui, L_ui, S, L = dims
         E = emb.shape[1]
         KC, _, KS = params[8].shape
@@ -537,12 +568,22 @@ class _ControlNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_control_net_ws_bytes", B, S_ui, L_ui, S, L, E, KC, KS, V), dev)
         cp = [_c(p) for p in params]
         keep, parr = _ptr_array(cp)
-        lib().call("umpr_control_net_fwd", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L, KC, KS, V,
-                   float(thr), int(b16_gemm), int(need), arena, outs[0], outs[1], outs[2], outs[3], ws, wsb, stream_ptr())
+        if dsts is None and not mask_control:
+            lib().call("umpr_control_net_fwd", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L, KC, KS,
+                       V, float(thr), int(b16_gemm), int(need), arena, outs[0], outs[1], outs[2], outs[3], ws, wsb, stream_ptr())
+        else:
+            dst_ui, dst_pair = dsts if dsts is not None else (ord_ui, order)
+            # this node's own validity bytes, filled on its own stream: the ReviewNet's mask is another buffer
+            valid_ui = _token_valid(ids_ui, lens_ui, B * S_ui, L_ui) if mask_control else None
+            valid_pair = _token_valid(ids_pair, lens, 2 * B * S, L) if mask_control else None
+            lib().call("umpr_control_net_fwd_ex", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, dst_ui, lens, order, dst_pair, B, S_ui,
+                       L_ui, S, L, KC, KS, V, float(thr), int(b16_gemm), int(need), arena, outs[0], outs[1], outs[2], outs[3], ws, wsb,
+                       valid_ui, valid_pair, stream_ptr())
         ctx.param_objs = params
         ctx.meta = (B, S_ui, L_ui, S, L, KC, KS, V, int(b16_gemm))
         ctx.on_side = getattr(_TEXT_TLS, "on_side", False)
         ctx.step = step if tok is not None else None
+        ctx.dsts = dsts
         ctx.set_materialize_grads(False)
         if need:
             ctx.save_for_backward(ids_ui, ids_pair, lens_ui, ord_ui, lens, order, emb, arena, *cp)
@@ -559,19 +600,25 @@ class _ControlNetF(torch.autograd.Function):
         ws, wsb = _ws(lib().size("umpr_control_net_ws_bytes", B, S_ui, L_ui, S, L, E, KC, KS, V), dev)
         keep_p, parr = _ptr_array(cp)
         keep_g, garr = _ptr_array(tg)
-        if ctx.step is None:
+        dx_pair = dx_ui = None
+        if ctx.step is not None:
+            dx_pair = torch.empty(ids_pair.numel(), E, device=dev, dtype=torch.float32)
+            dx_ui = torch.empty(ids_ui.numel(), E, device=dev, dtype=torch.float32)
+        if ctx.dsts is not None:     # the mask needs nothing here: the backward reads the arena, where an undefined sentence has view_p = 0
+            lib().call("umpr_control_net_bwd_ex", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, ctx.dsts[0], lens, order, ctx.dsts[1],
+                       B, S_ui, L_ui, S, L, KC, KS, V, b16, arena, d[0], d[1], d[2], d[3], garr, dx_pair, dx_ui, ws, wsb, stream_ptr())
+        elif dx_pair is None:
             lib().call("umpr_control_net_bwd", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L, KC,
                        KS, V, b16, arena, d[0], d[1], d[2], d[3], garr, ws, wsb, stream_ptr())
         else:
-            dx_pair = torch.empty(ids_pair.numel(), E, device=dev, dtype=torch.float32)
-            dx_ui = torch.empty(ids_ui.numel(), E, device=dev, dtype=torch.float32)
             lib().call("umpr_control_net_bwd_dx", ids_ui, ids_pair, emb, E, parr, lens_ui, ord_ui, lens, order, B, S_ui, L_ui, S, L,
                        KC, KS, V, b16, arena, d[0], d[1], d[2], d[3], garr, dx_pair, dx_ui, ws, wsb, stream_ptr())
+        if dx_pair is not None:
             ctx.step.dx[_EmbedStep.C_UI] = dx_ui
             ctx.step.produced(_EmbedStep.C_PAIR, dx_pair)
         if ctx.on_side and any(direct):
             note_gradients_written(dev)
-        return (None,) * 12 + tuple(_grad_returns(ctx.param_objs, tg, direct))
+        return (None,) * 14 + tuple(_grad_returns(ctx.param_objs, tg, direct))
 
 
 # --------------------------------------------------------------------------------------------- K10
@@ -1084,8 +1131,15 @@ class UMPR(nn.Module):
         # not in the reference: `--mask_padding True` gives the ReviewNet's three softmaxes a key-padding mask - the co-attention
         # maxima and softmaxes and the S-Nets' word softmax run over real tokens only (position inside the sentence's length and
         # id != <PAD>), so a sample's prediction no longer depends on how far its batch was padded.  No parameter is added: the
-        # state_dict is the same either way.  The ControlNet is not masked.
+        # state_dict is the same either way.  The ControlNet has its own option, below.
         self.mask_padding = bool(getattr(config, "mask_padding", False))
+        # not in the reference either: `--mask_control True` gives the ControlNet the same token validity - the C-Net
+        # heads take their conv maximum over each sentence's real tokens, a padded sentence contributes exactly 0, the control S-Net
+        # softmax runs over real tokens (ignored in UMPR-R: there is no ControlNet) - and `--unsort_gru True` lets every sentence keep
+        # its own GRU states (out[n] = GRU(x[n])) instead of the reference's double un-sort, in the R-Net and both C-Net GRU calls.
+        # With all three a sample's eval-mode prediction does not depend on its batch.  No parameter is added.
+        self.mask_control = bool(getattr(config, "mask_control", False))
+        self.unsort_gru = bool(getattr(config, "unsort_gru", False))
         self.last_loss_terms = None
         # Parameters whose backward node can write the gradient straight into the optimiser's arena (_grad_targets):
         # everything in the review / control nets (GRU weights accumulate in place across their uses) and, set by VGG16
@@ -1325,11 +1379,15 @@ class UMPR(nn.Module):
                 step = _EmbedStep((ids_pair, ids_pair, ui_reviews) if full else (ids_pair,))
                 tok = _EmbedTable.apply(emb, step, self._sparse_rows)
                 emb = emb.detach()
-            rr = _ReviewNetF.apply(ids_pair, lens, order, emb, (B, S, L), b16_gemm, b16_scores,
+            unsort = bool(getattr(self, "unsort_gru", False))
+            rr = _ReviewNetF.apply(ids_pair, lens, order, _identity_rows(2 * N, device) if unsort else None, emb, (B, S, L),
+                                   b16_gemm, b16_scores,
                                    bool(getattr(self, "mask_padding", False)), tok, step,
                                    *self._review_params(device))
             if full:
-                cu, ci, pp, pn = _ControlNetF.apply(ui_reviews.view(B * S_ui, L_ui), ids_pair, lens_ui, ord_ui, lens, order, emb,
+                dsts = (_identity_rows(B * S_ui, device), _identity_rows(2 * N, device)) if unsort else None
+                cu, ci, pp, pn = _ControlNetF.apply(ui_reviews.view(B * S_ui, L_ui), ids_pair, lens_ui, ord_ui, lens, order, dsts,
+                                                    bool(getattr(self, "mask_control", False)), emb,
                                                     (B, S_ui, L_ui, S, L), self.control_net.c_net.threshold, b16_gemm, tok, step,
                                                     *self._control_params(device))
         _TEXT_TLS.on_side = False

@@ -143,7 +143,8 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     set, and the log then lists the multipliers per prefix and the segments per group.  A model built with `config.photo_flip` /
     `config.photo_crop` augments its photos in every train_step (model.UMPR.photo_augment; validation sees plain photos): one log
     line says so.  `config.mask_padding` is read by the model (model.UMPR.mask_padding); one log line states the setting, the
-    checkpoints record it, and `config.resume` under the other setting is refused by load_checkpoint."""
+    checkpoints record it, and `config.resume` under the other setting is refused by load_checkpoint; `config.mask_control` and
+    `config.unsort_gru` (model.UMPR.mask_control / .unsort_gru) are treated the same way."""
     accum = int(getattr(config, "accum_steps", 1))
     if accum > 1 and parallel.active():
         raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
@@ -180,6 +181,13 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     log('Padding mask in the ReviewNet softmaxes (--mask_padding): '
         + ('on - co-attention and S-Net word attention run over real tokens only' if getattr(model, "mask_padding", False)
            else 'off - padding takes part, as in the reference'))
+    log('Padding mask in the ControlNet (--mask_control): '
+        + ('ignored - UMPR-R has no ControlNet' if getattr(model, "review_net_only", False) and getattr(model, "mask_control", False)
+           else 'on - C-Net maxima and the control S-Net run over real tokens only, a padded sentence contributes 0'
+           if getattr(model, "mask_control", False) else 'off - padding takes part, as in the reference'))
+    log('GRU output rows (--unsort_gru): '
+        + ('on - every sentence keeps its own states' if getattr(model, "unsort_gru", False)
+           else "off - the reference's double un-sort: a row holds the states of the sentence at its rank in the batch's length sort"))
     reducer = parallel.GradReducer(opt) if parallel.active() else None
     best_loss, batch_counter, first_epoch, skip, saved = 100, 0, 0, 0, False
     valid_every = int(getattr(config, "valid_every", 500))   # the reference hard-codes 500 (main.py:43)
