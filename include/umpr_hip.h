@@ -420,12 +420,25 @@ typedef void (*umpr_block_callback)(int block, void* user);
 int umpr_vgg16_set_block_callback(umpr_block_callback cb, void* user);
 void* umpr_vgg16_wgrad_stream(void);
 /* per-layer entry points (also what the composite calls) */
-/* wpack / wt: scratch of umpr_conv3x3_pack_bytes(...) - packed weights, or on the 56/28/14 maps the Winograd
- * F(2x2,3x3) buffers (with a smaller scratch those layers fall back to the direct kernel) */
+/* Any N, Cin, Cout, H, W >= 1; maps need not be square (only the square 224/112/56/28/14 maps have kernels of their own, any
+ * other map - non-square, one pixel high or wide - runs the generic kernels at the same accuracy).
+ * wpack / wt: scratch of umpr_conv3x3_pack_bytes(...) - packed weights, or on the 56/28/14 maps (and 112 with >= 128 channels)
+ * the Winograd buffers.  Nothing is read from it that the call did not write, nothing is written behind its size, and the
+ * result does not depend on it being larger.  With less:
+ *   - a layer planned on Winograd runs the direct kernel as long as the packed weights fit - Cout * ceil(Cin / 4) * 36 floats in
+ *     forward, Cin * ceil(Cout / 4) * 36 in the data gradient; below that the call is refused ("weight scratch too small") and
+ *     writes nothing;
+ *   - umpr_conv3x3_fwd with wpack = NULL, wpack_bytes = 0 runs the generic kernel on every shape; umpr_conv3x3_bwd_data needs
+ *     its scratch and refuses NULL ("needs the weight scratch");
+ *   - umpr_conv3x3_bwd_weight with k * (9 * Cout * Cin + Cout) * 4 bytes, k >= 1 below what umpr_conv3x3_bwd_weight_ws_bytes
+ *     reports, runs the shape's non-Winograd kernel with at most k split-K slabs ([9][Cout][Cin] each, the bias rows behind
+ *     them); less than one slab is refused ("workspace too small") with nothing written.
+ * (tests/test_gpu_conv_seams.py pins all of this on NaN-filled buffers between guard bands.) */
 size_t umpr_conv3x3_pack_bytes(int N, int Cin, int Cout, int H, int W);
 int umpr_conv3x3_fwd(const float* x, const float* w, const float* bias, float* y, int N, int Cin, int H, int W,
                      int Cout, int relu, float* wpack, size_t wpack_bytes, void* stream);
-/* dx = conv_transpose(dy, w) [* (mask_src > 0)] */
+/* dx = conv_transpose(dy, w) [* (mask_src > 0)].  The comparison is IEEE's and flushes nothing: false at +0, -0 and every
+ * negative value, true at positive denormals.  Where it is true dx holds the bits of the unmasked call, elsewhere +0. */
 int umpr_conv3x3_bwd_data(const float* dy, const float* w, const float* mask_src /*or NULL*/, float* dx, int N,
                           int Cin, int H, int W, int Cout, float* wt, size_t wt_bytes, void* stream);
 size_t umpr_conv3x3_bwd_weight_ws_bytes(int N, int Cin, int Cout, int H, int W);

@@ -301,7 +301,7 @@ def _count_conv_base(vgg, monkeypatch):
 
 def test_cold_then_warm_pass(L, dev, photo_set, model1, tmp_path, monkeypatch):
     paths = own_copy(photo_set[:3] + photo_set[7:8], tmp_path)              # 500x375, 224x224, 100x80, grey
-    samples = samples_for(paths, 3, 2, 1)                                  # 6 photos: p0 p1 p2 p3 p0 p1
+    samples = samples_for(paths, 3, 1, 2)                                  # 6 photos: p0 p1 p2 p3 p0 p1 (model1 has one view)
     flat = [p for s in samples for v in s[3] for p in v]
     vgg = model1.visual_net.vgg16[0]
     store = Pool5Store(dev, capacity_bytes=8 * SLOT + 100).register(paths)
@@ -357,7 +357,7 @@ def test_mixed_pass_and_the_zero_row(dev, photo_set, model1, monkeypatch):
     store.features(first, vgg)
     held = {q: _row(store, q).clone() for q in p[:3]}
     order = [p[0], p[7], p[1], p[8], p[7], p[2], "unknown", p[11]]         # p[11] does not exist
-    samples = samples_for(order, 2, 2, 2)
+    samples = samples_for(order, 2, 1, 4)                                   # one view, as model1 has: the same eight in this order
     host = batch_loader(samples)[6].reshape(-1, 3, 224, 224).to(dev)
     fresh = vgg.conv_base(host[[1, 3]]).clone()
     zero = vgg.conv_base(torch.zeros(1, 3, 224, 224, device=dev)).clone()
@@ -476,6 +476,9 @@ def test_refusals(dev, photo_set, model1):
     trainable.classifier.requires_grad_(False)                              # a conv parameter that trains is enough
     with pytest.raises(UmprHipError, match="Pool5Store: the conv base has trainable parameters"):
         store.features(_collate(store, samples)[6], trainable)
+    # two views for a model of one: the head is told no sizes and would read behind pos_v_emb, the gates and the fusion weight
+    with pytest.raises(RuntimeError, match="photos of 2 views, the model was built for 1"):
+        model1(*_collate(store, samples_for(p, 2, 2, 1)))
     assert store.stats()["used"] == 0 and store.stats()["vgg_calls"] == 0
     assert fstore.stats()["used"] == 0 and fstore.stats()["vgg_calls"] == 0
 

@@ -1335,6 +1335,11 @@ class UMPR(nn.Module):
                                                   for v in (user_reviews, item_reviews, ui_reviews)]
         # a batch collated against a photos.FeatureStore (frozen VGG): its photos are never materialised, see below
         feature_store = self._feature_store(photos) if not self.review_net_only else None
+        if not self.review_net_only and photos.shape[1] != len(self.views):
+            # the head walks pos_v_emb / neg_v_emb, the control gates and the fusion weight by the batch's view count and is
+            # told no sizes: more views than the model has would be read from behind those tensors
+            raise RuntimeError(f"the batch carries photos of {photos.shape[1]} views, the model was built for "
+                               f"{len(self.views)} ({', '.join(self.views)})")
         if self.photo_augment is not None and self.training and torch.is_grad_enabled():
             # a training forward: a fresh crop / flip of every photo (evaluation, no_grad and validation fetch the plain photos)
             from .photos import RawPhotos
