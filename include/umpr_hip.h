@@ -592,6 +592,26 @@ int umpr_review_collate(const int32_t* tokens, const int64_t* sent_off, long n_s
                         const float* ratings, long n_samples, const int32_t* idx, int B, int S, int L, int S_ui, int L_ui, long pad,
                         int64_t* ids_pair, int64_t* ids_ui, float* labels, void* stream);
 
+/* ---- sampled review collate (umpr_amd/reviews.py::ReviewDraw): a fresh draw of each pool per epoch, word dropout -----------------
+ * umpr_review_collate with the user and item tables holding pools of up to 1024 sentences, of which a sample shows `keep`.  With
+ * mix64 splitmix64's output function, n the sample's index and role 0 / 1 / 2 for user / item / ui:
+ *   role_key = mix64(mix64(seed_epoch_key + n) + role),   key_j = mix64(role_key + j) for the pool's positions j;
+ * row s of a user or item holds the sentence whose key has rank s among the pool's (ties to the smaller j), for
+ * s < min(keep, pool size), and `pad` beyond; the ui rows are umpr_review_collate's.  With drop_threshold T > 0 the token at (s, l)
+ * of any role, l inside the sentence's kept length, becomes `unk` iff
+ *   (mix64(mix64(role_key ^ 0xD6E8FEB86659FD93) + ((s << 8) | l)) >> 32) < T;
+ * padding stays `pad`.  T = 0 runs the instantiation without the test.  seed_epoch_key = mix64(mix64(seed) + epoch) is formed by
+ * the caller; drop_threshold is 32 bits wide, min(floor(p * 2^32), 2^32 - 1) for a dropout rate p.  One workgroup per
+ * (sample, role); what it reads from the tables is clipped (pool size to 1024, sentence ids to n_sent, lengths to the row), so a
+ * corrupt table gives wrong ids, never an access out of bounds.  Refused without launching, the
+ * outputs untouched: all that umpr_review_collate refuses; keep outside [1, 1024]; S > keep; T > 0 with unk < 0.  No allocation
+ * or copy: capture-safe. */
+int umpr_review_collate_sampled(const int32_t* tokens, const int64_t* sent_off, long n_sent, const int64_t* ptr_u,
+                                const int32_t* sid_u, const int64_t* ptr_i, const int32_t* sid_i, const int64_t* ptr_ui,
+                                const int32_t* sid_ui, const float* ratings, long n_samples, const int32_t* idx, int B, int S, int L,
+                                int S_ui, int L_ui, long pad, int keep, uint64_t seed_epoch_key, unsigned int drop_threshold, long unk,
+                                int64_t* ids_pair, int64_t* ids_ui, float* labels, void* stream);
+
 /* ---- R-Net pre-training head (pretrain/pretrain_rnet.py:147-169): result = sigmoid(Linear(K -> 1)(att)),
  * loss = BCELoss(mean)(result, target) with torch's log clamp at -100.  att rows at att + b*ld (K = 256: [atte_u;atte_i]
  * as umpr_coattention_fwd leaves them).  ws: B floats.  Backward follows ATen's binary_cross_entropy_backward

@@ -17,6 +17,9 @@
                                                                               # training step on the GPU: random crop >= 30 %, flip
     python main.py --data_dir data/music --review_net_only True --review_store True   # tokenised reviews kept in HBM: a batch
                                                                                       # travels as indices, one kernel pads its ids
+    python main.py --data_dir data/music --review_net_only True --review_store True --review_pool 200 --word_dropout 0.1
+                                                # every epoch shows a fresh draw of max_sent_count sentences out of up to 200 per
+                                                # user and item, and replaces a tenth of the tokens by <UNK>, in the collate kernel
     python main.py --data_dir data/music --train_embedding True               # fine-tune the word vectors (frozen by default)
     python main.py --data_dir data/music --mask_padding True                  # attention softmaxes of the ReviewNet skip padding
     python main.py --data_dir data/music --mask_padding True --mask_control True --unsort_gru True   # ... the ControlNet skips it
@@ -82,6 +85,12 @@ class ShardedLoader:
     def __len__(self):
         return len(self.loader)
 
+    def set_epoch(self, epoch):
+        """passed on to a loader that draws per epoch (reviews.StoreLoader with a ReviewDraw)"""
+        inner = getattr(self.loader, "set_epoch", None)
+        if inner is not None:
+            inner(epoch)
+
 
 class _Collate:
     """Picklable collate (worker processes): src/dataset.py:173-182 via umpr_amd.data.batch_loader."""
@@ -115,6 +124,14 @@ def _averaged_test(config, opt, saved):
     if config.ema_decay > 0 and not config.test_only and not saved and opt is not None and opt.ema_ready:
         return opt.swapped_ema()
     return contextlib.nullcontext()
+
+
+def _unpooled(config):
+    """`config` as the validation and test Datasets read it: --review_pool off, so that only the training set builds pools."""
+    import copy
+    plain = copy.copy(config)
+    plain.review_pool = 0
+    return plain
 
 
 def run_real(config, rank, world, log):
@@ -173,14 +190,22 @@ def run_real(config, rank, world, log):
     if workers:
         dl.update(prefetch_factor=2, persistent_workers=True)
 
-    def loader(data, name, **kw):
-        """The DataLoader of `data`, cut to this rank's chunks; with --review_store its text half comes from a ReviewStore"""
+    def loader(data, name, draw=None, **kw):
+        """The DataLoader of `data`, cut to this rank's chunks; with --review_store its text half comes from a ReviewStore, and
+        with `draw` (the training set under --review_pool / --word_dropout) from a sampled collate"""
         if not config.review_store:
             return ShardedLoader(DataLoader(data, batch_size=config.batch_size, **kw, **dl), rank, world)
         reviews = ReviewStore(data, config.device)
         log(f'Review store ({name}): {reviews!r}')
-        return ShardedLoader(StoreLoader(DataLoader(IndexView(data), batch_size=config.batch_size, **kw, **dl), reviews, rank, world),
-                             rank, world)
+        if draw is not None:
+            wide = (reviews.pool_count["user"] > reviews.draw_keep()) | (reviews.pool_count["item"] > reviews.draw_keep())
+            log(f'Sampled collate ({name}): a fresh draw of {reviews.draw_keep()} sentences per user and item pool every epoch'
+                + (f' out of up to {config.review_pool}' if config.review_pool else ' (--review_pool 0: the pools are shuffled)')
+                + f', word dropout {draw.word_dropout}; {reviews.nbytes} B on the device, {wide.mean():.1%} of the '
+                f'{reviews.n_samples} samples have a pool above {reviews.draw_keep()} sentences; validation and test see the '
+                'plain batches')
+        return ShardedLoader(StoreLoader(DataLoader(IndexView(data), batch_size=config.batch_size, **kw, **dl), reviews, rank, world,
+                                         draw=draw), rank, world)
 
     model = UMPR(config, w2v.embedding).to(config.device)
     os.makedirs(os.path.dirname(model_path) or '.', exist_ok=True)
@@ -188,11 +213,15 @@ def run_real(config, rank, world, log):
     saved, opt = False, None
     if not config.test_only:
         train_data = Dataset(os.path.join(d, 'train.csv'), photo_json, photo_path, w2v, config)
-        valid_data = Dataset(os.path.join(d, 'valid.csv'), photo_json, photo_path, w2v, config)
+        valid_data = Dataset(os.path.join(d, 'valid.csv'), photo_json, photo_path, w2v, _unpooled(config))
         log(f'Training dataset contains {len(train_data)} samples.')
         known(train_data), known(valid_data)           # before the loaders exist: their workers copy the path table
         g = torch.Generator().manual_seed(0)  # same shuffle on every rank
-        train_dlr = loader(train_data, 'train', shuffle=True, generator=g)
+        draw = None
+        if config.review_pool or config.word_dropout > 0:         # the training loader only
+            from umpr_amd.reviews import ReviewDraw
+            draw = ReviewDraw(torch.initial_seed(), 0, config.word_dropout, w2v.word2index[w2v.unknown])
+        train_dlr = loader(train_data, 'train', draw, shuffle=True, generator=g)
         valid_dlr = loader(valid_data, 'valid')
         opt, saved = training(train_dlr, valid_dlr, model, config, model_path, logger=logger, world=world, rank=rank)
         if store:
@@ -204,7 +233,7 @@ def run_real(config, rank, world, log):
         log('No checkpoint was written in this run (validation never improved at a multiple of the validation '
             'interval): testing the model as it stands at the end of training'
             + (' (the moving average of its weights)' if config.ema_decay > 0 and opt.ema_ready else ''))
-    test_data = Dataset(os.path.join(d, 'test.csv'), photo_json, photo_path, w2v, config)
+    test_data = Dataset(os.path.join(d, 'test.csv'), photo_json, photo_path, w2v, _unpooled(config))
     known(test_data)
     test_dlr = loader(test_data, 'test')
     with _averaged_test(config, opt, saved):
@@ -236,7 +265,8 @@ EXTRA_OPTIONS = {"synthetic_batches": 20, "synthetic_vocab": 400003, "synthetic_
                  "freeze_vgg": False, "feature_store_gb": 0.0, "train_embedding": False, "sparse_embedding": False,
                  "freeze_conv": False, "pool5_store_gb": 0.0, "accum_steps": 1, "review_store": False, "ema_decay": 0.0,
                  "lr_scale": "", "wd_scale": "", "decoupled_decay": False, "warmup_steps": 0, "photo_flip": False,
-                 "photo_crop": 1.0, "mask_padding": False, "mask_control": False, "unsort_gru": False}
+                 "photo_crop": 1.0, "mask_padding": False, "mask_control": False, "unsort_gru": False, "review_pool": 0,
+                 "word_dropout": 0.0}
 
 
 def check_flags(config):
@@ -255,6 +285,20 @@ def check_flags(config):
         sys.exit(f"--mask_control takes True or False, got {config.mask_control!r}")
     if not isinstance(config.unsort_gru, bool):
         sys.exit(f"--unsort_gru takes True or False, got {config.unsort_gru!r}")
+    if isinstance(config.review_pool, bool) or not isinstance(config.review_pool, int) or \
+            (config.review_pool != 0 and not config.max_sent_count < config.review_pool <= 1024):
+        sys.exit(f"--review_pool takes 0 (off) or the sentences kept per user and item pool, max_sent_count = "
+                 f"{config.max_sent_count} < N <= 1024, got {config.review_pool!r}")
+    if isinstance(config.word_dropout, bool) or not isinstance(config.word_dropout, (int, float)) or \
+            not 0 <= config.word_dropout < 1:
+        sys.exit(f"--word_dropout takes the share of tokens replaced by <UNK> in a training batch, 0 <= p < 1 (0: off), got "
+                 f"{config.word_dropout!r}")
+    for option in ("review_pool", "word_dropout"):
+        if getattr(config, option) and not config.review_store:
+            sys.exit(f"--{option} needs --review_store True: the draw is made by the kernel that collates a batch from the store")
+        if getattr(config, option) and config.data_dir == "synthetic":
+            sys.exit(f"--{option} needs tokenised reviews (a --data_dir with train.csv): the synthetic batches carry finished id "
+                     "tensors, which are not sampled")
     if config.sparse_embedding and not config.train_embedding:
         sys.exit("--sparse_embedding needs --train_embedding True: it chooses how a trainable table is updated (the rows a step "
                  "names only, as torch.optim.SparseAdam would)")

@@ -120,6 +120,7 @@ SIGNATURES = {
     "umpr_photo_fetch_augment_u8": ("pzppppiiiplplpppp", "i"),
     "umpr_feature_fetch_f32": ("pipppiiplpp", "i"),
     "umpr_review_collate": ("pplppppppplpiiiiilpppp", "i"),
+    "umpr_review_collate_sampled": ("pplppppppplpiiiiil" "iuil" "pppp", "i"),   # (the unsigned threshold: its 32 bits as an int)
     "umpr_bce_head_fwd": ("plpppiipppzp", "i"),
     "umpr_bce_head_bwd": ("plpppppiiplpppzp", "i"),
     "umpr_adam_step": ("ppppldddddldp", "i"),

@@ -79,6 +79,12 @@ class Dataset(torch.utils.data.Dataset):
         self.max_s_length = config.max_sent_length
         self.photo_count = config.photo_count
         self.views = config.views
+        # review_pool N > 0 (not in the reference): beside `data`, `pools` keeps up to N sentences per user and item pool, of
+        # which `data` holds the first max_sent_count; reviews.ReviewStore draws from them anew every epoch
+        self.review_pool = int(getattr(config, "review_pool", 0) or 0)
+        if self.review_pool and not self.max_s_count < self.review_pool <= 1024:
+            raise ValueError(f"Dataset: review_pool must be 0 (off) or lie in (max_sent_count = {self.max_s_count}, 1024], got "
+                             f"{self.review_pool}")
         df = pd.read_csv(data_path)
         by_sentence = config.review_level == 'sentence'
 
@@ -90,8 +96,9 @@ class Dataset(torch.utils.data.Dataset):
         reviews = [to_sentences(x) for x in df['review']]
         keep = [len(r) > 0 for r in reviews]
         photos = self._photo_paths(photo_json, photo_dir, list(df['itemID']), keep)
-        users = self._pool(list(df['user_num']), list(df['item_num']), reviews, keep)
-        items = self._pool(list(df['item_num']), list(df['user_num']), reviews, keep)
+        users_full, items_full = ([], []) if self.review_pool else (None, None)
+        users = self._pool(list(df['user_num']), list(df['item_num']), reviews, keep, users_full)
+        items = self._pool(list(df['item_num']), list(df['user_num']), reviews, keep, items_full)
         uis = []
         for i, sents in enumerate(reviews):
             if not keep[i]:
@@ -106,6 +113,9 @@ class Dataset(torch.utils.data.Dataset):
         sel = [i for i, k in enumerate(keep) if k]
         self.data = ([users[i] for i in sel], [items[i] for i in sel], [uis[i] for i in sel],
                      [photos[i] for i in sel], [ratings[i] for i in sel])
+        if self.review_pool:
+            # aligned with data: data[0][i] == pools[0][i][:max_sent_count], and likewise for the items
+            self.pools = ([users_full[i] for i in sel], [items_full[i] for i in sel])
 
     def __getitem__(self, idx):
         return tuple(x[idx] for x in self.data)
@@ -117,25 +127,31 @@ class Dataset(torch.utils.data.Dataset):
     def __len__(self):
         return len(self.data[0])
 
-    def _pool(self, lead, costar, reviews, keep):
-        """Sentences of every review the lead (user or item) wrote/received except the one about `costar`."""
+    def _pool(self, lead, costar, reviews, keep, full=None):
+        """Sentences of every review the lead (user or item) wrote/received except the one about `costar`.  With `full` a list
+        (review_pool), it receives, aligned with the result, the same pool cut to review_pool sentences instead."""
         groups = defaultdict(list)
         for l, c, r in zip(lead, costar, reviews):
             groups[l].append((c, r))
         out = []
         for i, (l, c) in enumerate(zip(lead, costar)):
-            if not keep[i]:
-                out.append(None)
-                continue
-            sents = [s for cid, r in groups[l] if cid != c for s in r]
-            if len(sents) < self.min_s_count:
-                keep[i] = False
-                out.append(None)
-                continue
-            if len(sents) > self.max_s_count:
-                sents.sort(key=lambda x: -len(x))  # stable, longest first
-                sents = sents[: self.max_s_count]
+            wide = None
+            if keep[i]:
+                sents = [s for cid, r in groups[l] if cid != c for s in r]
+                if len(sents) < self.min_s_count:
+                    keep[i] = False
+                    sents = None
+                elif len(sents) > self.max_s_count:
+                    sents.sort(key=lambda x: -len(x))  # stable, longest first
+                    wide = sents[: self.review_pool]
+                    sents = sents[: self.max_s_count]
+                else:
+                    wide = sents                       # not sorted: its own prefix
+            else:
+                sents = None
             out.append(sents)
+            if full is not None:
+                full.append(wide)
         return out
 
     def _photo_paths(self, photos_json, photo_dir, item_ids, keep):

@@ -122,6 +122,19 @@ def _shuffle_generator(loader):
     return None
 
 
+def _set_epoch(loader, epoch):
+    """Tells a (possibly wrapped) loader that draws per epoch which epoch begins: the outermost set_epoch along the `.loader`
+    chain (main.ShardedLoader, reviews.StoreLoader).  A loader without one draws nothing per epoch."""
+    seen = 0
+    while loader is not None and seen < 4:
+        f = getattr(loader, "set_epoch", None)
+        if callable(f):
+            f(epoch)
+            return
+        loader = getattr(loader, "loader", None)
+        seen += 1
+
+
 def training(train_dataloader, valid_dataloader, model, config, model_path, logger=None, world=1, rank=0):
     """main.py:16-61.  Returns (optimiser, saved): `saved` says whether THIS run wrote `model_path`.
     Not in the reference: `config.resume` continues a run exactly - parameters, Adam moments, learning rate, the
@@ -144,7 +157,10 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
     `config.photo_crop` augments its photos in every train_step (model.UMPR.photo_augment; validation sees plain photos): one log
     line says so.  `config.mask_padding` is read by the model (model.UMPR.mask_padding); one log line states the setting, the
     checkpoints record it, and `config.resume` under the other setting is refused by load_checkpoint; `config.mask_control` and
-    `config.unsort_gru` (model.UMPR.mask_control / .unsort_gru) are treated the same way."""
+    `config.unsort_gru` (model.UMPR.mask_control / .unsort_gru) are treated the same way.  A training loader with `set_epoch`
+    (reviews.StoreLoader with a ReviewDraw: --review_pool / --word_dropout) is told the epoch at its head; its draws are a function
+    of (seed, epoch, sample), so a run resumed inside an epoch skips the consumed batches and draws what the uninterrupted run
+    drew, without a checkpoint key."""
     accum = int(getattr(config, "accum_steps", 1))
     if accum > 1 and parallel.active():
         raise NotImplementedError("training: --accum_steps > 1 runs on one rank only (no gradient exchange for accumulated arenas)")
@@ -227,6 +243,7 @@ def training(train_dataloader, valid_dataloader, model, config, model_path, logg
         total_loss, total_samples, consumed = 0.0, 0, 0
         t0 = time.perf_counter()
         epoch_rng = gen.get_state() if gen is not None else None
+        _set_epoch(train_dataloader, epoch)
         for bi, batch in enumerate(train_dataloader):
             consumed = bi + 1
             if epoch == first_epoch and bi < skip:   # consumed before the checkpoint was taken
