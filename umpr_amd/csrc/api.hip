@@ -89,6 +89,15 @@ VggLayout vgg_layout(int n) {
 }
 }  // namespace
 
+// Mixed precision for the GEMM-shaped text products (GRU input projections, co-attention / S-Net / C-Net projections and
+// their gradients): while set on the calling host thread, the products a public entry point issues through the generic GEMM
+// round their operands to bf16 on the way into LDS and run on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (what
+// torch.autocast does to the same nn.GRU / nn.Linear / nn.Conv1d layers).  Hosts set it around a call and clear it after.
+// Like the conv hints below it is read only where a public entry point starts (umpr_ambient_gemm_b16, once per call); the
+// code underneath sees `gemm_b16` arguments and UmprGemm::b16.  DESIGN.md, "GEMM precision", lists what each product follows.
+static thread_local bool t_gemm_b16 = false;
+bool umpr_ambient_gemm_b16() { return t_gemm_b16; }
+
 extern "C" {
 
 const char* umpr_version(void) { return "umpr_hip 0.1 (gfx950)"; }
@@ -109,15 +118,11 @@ int umpr_gemm_f32(const float* A, long lda, int transA, const float* B, long ldb
   UmprGemm g;
   g.A = A; g.lda = lda; g.transA = transA != 0; g.B = B; g.ldb = ldb; g.transB = transB != 0; g.C = C; g.ldc = ldc;
   g.M = M; g.N = N; g.K = K; g.bias = bias; g.bias_mode = bias_mode; g.act = act; g.accumulate = accumulate != 0;
-  g.alpha = alpha; g.split_k = ws ? 0 : 1; g.ws = ws; g.ws_bytes = ws_bytes;
+  g.alpha = alpha; g.split_k = ws ? 0 : 1; g.ws = ws; g.ws_bytes = ws_bytes; g.b16 = umpr_ambient_gemm_b16();
   return umpr_gemm(g, S(stream));
 }
 
-// Mixed precision for the GEMM-shaped text products (GRU input projections, co-attention / S-Net / C-Net projections and
-// their gradients): while set on the calling host thread, every product the library issues through its generic GEMM rounds
-// its operands to bf16 on the way into LDS and runs on v_mfma_f32_32x32x16_bf16 with fp32 accumulation (what
-// torch.autocast does to the same nn.GRU / nn.Linear / nn.Conv1d layers).  Hosts set it around a call and clear it after.
-int umpr_set_gemm_bf16(int on) { umpr_gemm_set_b16(on != 0); return 0; }
+int umpr_set_gemm_bf16(int on) { t_gemm_b16 = on != 0; return 0; }
 // The two conv hints a host sets around its calls, per host thread.  They are read only where a public entry point builds the
 // ConvHints of a call (conv_hints below); the convolution code itself sees arguments.
 static thread_local bool t_conv_inference = false, t_conv_pool_follows = false;
@@ -232,11 +237,13 @@ int gather_rows(const int64_t* ids, const float* emb, int E, int Ep, float* out,
 
 // the size is that of rows of E rounded up to 4 floats (16-B rows), also where UMPR_EMB_GATHER=0 carves with a pitch of E
 size_t umpr_embed_gru_bidir_ws_bytes(int N, int L, int E) { return gru_ws(nullptr, N, L, (E + 3) & ~3).bytes; }
-int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
-                             const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
-                             const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
-                             const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
-                             float* out, float* saved, float* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+int umpr_embed_gru_fwd_impl(const int64_t* ids, const float* emb, int E,
+                            const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
+                            const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
+                            const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                            float* out, float* saved, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s) {
   UMPR_REQUIRE(N > 0 && L > 0 && E > 0, "embed_gru: bad shape N=%d L=%d E=%d", N, L, E);
   UMPR_REQUIRE(ws_bytes >= (size_t)N * L * 384 * sizeof(float), "embed_gru: workspace too small");
   const int Ep = emb_pitch(E);
@@ -247,7 +254,6 @@ int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
   // its second one).  The stacked [384][Ep] weight / [384] bias live on the backward's slab area.
   if (ws_bytes >= umpr_embed_gru_bidir_ws_bytes(N, L, E)) {
     float *wst = W.wst, *bst = W.bst;
-    const hipStream_t s = S(stream);
     // stack the two directions' input weights and biases: one launch
     stack_wih_kernel<<<cdiv(2 * G3 * Ep, 256), 256, 0, s>>>(w_ih_f, w_ih_r, b_ih_f, b_ih_r, E, Ep, wst, bst);
     UMPR_LAUNCH_CHECK("stack_wih");
@@ -260,34 +266,34 @@ int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
       g.A = emb; g.lda = E; g.gatherA = ids;
     }
     g.B = wst; g.ldb = Ep; g.transB = true;
-    g.C = gx; g.ldc = 384; g.M = N * L; g.N = 2 * G3; g.K = Ep; g.bias = bst; g.bias_mode = 1;
+    g.C = gx; g.ldc = 384; g.M = N * L; g.N = 2 * G3; g.K = Ep; g.bias = bst; g.bias_mode = 1; g.b16 = gemm_b16;
     if (int rc = umpr_gemm(g, s)) return rc;
   } else {
     for (int d = 0; d < 2; ++d) {  // small workspace (inference callers sized for gx only): one GEMM per direction
       UmprGemm g;
       g.A = emb; g.lda = E; g.gatherA = ids; g.B = d ? w_ih_r : w_ih_f; g.ldb = E; g.transB = true;
       g.C = gx + d * G3; g.ldc = 384; g.M = N * L; g.N = G3; g.K = E;
-      g.bias = d ? b_ih_r : b_ih_f; g.bias_mode = 1;
-      if (int rc = umpr_gemm(g, S(stream))) return rc;
+      g.bias = d ? b_ih_r : b_ih_f; g.bias_mode = 1; g.b16 = gemm_b16;
+      if (int rc = umpr_gemm(g, s)) return rc;
     }
   }
-  return umpr_gru_recurrent_fwd(gx, w_hh_f, b_hh_f, w_hh_r, b_hh_r, lengths, order, dst_row, out, saved, N, L, S(stream));
+  return umpr_gru_recurrent_fwd(gx, w_hh_f, b_hh_f, w_hh_r, b_hh_r, lengths, order, dst_row, out, saved, N, L, s);
 }
 
-int umpr_embed_gru_bidir_bwd_dx(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
-                                const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
-                                const float* dout, const float* out, const float* saved,
-                                float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
-                                float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
-                                int accumulate, const float* w_ih_f, const float* w_ih_r, float* dx, int dx_accumulate,
-                                float* ws, size_t ws_bytes, void* stream) {
+int umpr_embed_gru_bwd_impl(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
+                            const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                            const float* dout, const float* out, const float* saved,
+                            float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
+                            float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
+                            int accumulate, const float* w_ih_f, const float* w_ih_r, float* dx, int dx_accumulate,
+                            float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s) {
   UMPR_REQUIRE(dx == nullptr || (w_ih_f != nullptr && w_ih_r != nullptr), "embed_gru_bwd: dx needs w_ih_f and w_ih_r");
   UMPR_REQUIRE(dout != nullptr && out != nullptr && saved != nullptr, "embed_gru_bwd: dout / out / saved must not be NULL");
   UMPR_REQUIRE(ws_bytes >= umpr_embed_gru_bidir_ws_bytes(N, L, E), "embed_gru_bwd: workspace too small");
   const int tiles = umpr_gru_tiles(N), Ep = emb_pitch(E);
   const GruWs W = gru_ws(ws, N, L, Ep);
   float *dgx = W.gx, *wslab = W.wslab, *bslab = W.bslab;
-  if (int rc = umpr_gru_bptt(dout, out, saved, w_hh_f, w_hh_r, lengths, order, dst_row, dgx, wslab, bslab, N, L, S(stream)))
+  if (int rc = umpr_gru_bptt(dout, out, saved, w_hh_f, w_hh_r, lengths, order, dst_row, dgx, wslab, bslab, N, L, s))
     return rc;
   float* dwhh[2] = {dw_hh_f, dw_hh_r};
   float* dbih[2] = {db_ih_f, db_ih_r};
@@ -301,7 +307,7 @@ int umpr_embed_gru_bidir_bwd_dx(const int64_t* ids, const float* emb, int E, con
       src[3 * d + 2] = bslab + (size_t)d * 2 * G3 + G3;   dst[3 * d + 2] = dbhh[d]; cols[3 * d + 2] = G3;     rs[3 * d + 2] = 4 * G3;
     }
     for (int q = 0; q < 6; ++q) { rows[q] = tiles; acc[q] = accumulate; }
-    if (int rc = umpr_multi_colsum_rows(src, rows, cols, rs, dst, acc, 6, S(stream))) return rc;
+    if (int rc = umpr_multi_colsum_rows(src, rows, cols, rs, dst, acc, 6, s)) return rc;
   }
   {  // [dW_ih_f ; dW_ih_r] [384][E] = dgx^T emb[ids]: one split-K gather-GEMM for both directions, then rows 0..191 /
      // 192..383 are copied (or added) to their parameters' gradients
@@ -310,28 +316,50 @@ int umpr_embed_gru_bidir_bwd_dx(const int64_t* ids, const float* emb, int E, con
     g.A = dgx; g.lda = 384; g.transA = true;
     if (g_emb_gather) {
       float* xg = W.rows;
-      if (int rc = gather_rows(ids, emb, E, Ep, xg, (long)N * L, S(stream))) return rc;
+      if (int rc = gather_rows(ids, emb, E, Ep, xg, (long)N * L, s)) return rc;
       g.B = xg; g.ldb = Ep;
     } else {
       g.B = emb; g.ldb = E; g.gatherB = ids;
     }
     g.C = stacked; g.ldc = Ep; g.M = 2 * G3; g.N = Ep; g.K = N * L; g.split_k = 0; g.ws = W.kslab;   // (tail columns: zeros)
-    g.ws_bytes = W.kslab_bytes;
-    if (int rc = umpr_gemm(g, S(stream))) return rc;
-    unstack_dwih_kernel<<<cdiv(2 * G3 * E, 256), 256, 0, S(stream)>>>(stacked, E, Ep, dwih[0], dwih[1], accumulate);
+    g.ws_bytes = W.kslab_bytes; g.b16 = gemm_b16;
+    if (int rc = umpr_gemm(g, s)) return rc;
+    unstack_dwih_kernel<<<cdiv(2 * G3 * E, 256), 256, 0, s>>>(stacked, E, Ep, dwih[0], dwih[1], accumulate);
     UMPR_LAUNCH_CHECK("unstack_dwih");
   }
   if (dx) {  // token gradient for a trainable table: dx = dgx[:, 0:192] W_ih_f + dgx[:, 192:384] W_ih_r, fp32 in both precisions
-    UmprF32Scope f32;
     const float* wih[2] = {w_ih_f, w_ih_r};
     for (int d = 0; d < 2; ++d) {
       UmprGemm g;
       g.A = dgx + d * G3; g.lda = 384; g.B = wih[d]; g.ldb = E;
-      g.C = dx; g.ldc = E; g.M = N * L; g.N = E; g.K = G3; g.accumulate = d == 1 || dx_accumulate != 0;
-      if (int rc = umpr_gemm(g, S(stream))) return rc;
+      g.C = dx; g.ldc = E; g.M = N * L; g.N = E; g.K = G3; g.accumulate = d == 1 || dx_accumulate != 0; g.b16 = false;
+      if (int rc = umpr_gemm(g, s)) return rc;
     }
   }
   return 0;
+}
+
+extern "C" {
+
+int umpr_embed_gru_bidir_fwd(const int64_t* ids, const float* emb, int E,
+                             const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
+                             const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
+                             const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                             float* out, float* saved, float* ws, size_t ws_bytes, void* stream) {
+  return umpr_embed_gru_fwd_impl(ids, emb, E, w_ih_f, w_hh_f, b_ih_f, b_hh_f, w_ih_r, w_hh_r, b_ih_r, b_hh_r, lengths, order, dst_row,
+                                 N, L, out, saved, ws, ws_bytes, umpr_ambient_gemm_b16(), S(stream));
+}
+
+int umpr_embed_gru_bidir_bwd_dx(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
+                                const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                                const float* dout, const float* out, const float* saved,
+                                float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
+                                float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
+                                int accumulate, const float* w_ih_f, const float* w_ih_r, float* dx, int dx_accumulate,
+                                float* ws, size_t ws_bytes, void* stream) {
+  return umpr_embed_gru_bwd_impl(ids, emb, E, w_hh_f, w_hh_r, lengths, order, dst_row, N, L, dout, out, saved, dw_ih_f, dw_hh_f,
+                                 db_ih_f, db_hh_f, dw_ih_r, dw_hh_r, db_ih_r, db_hh_r, accumulate, w_ih_f, w_ih_r, dx, dx_accumulate,
+                                 ws, ws_bytes, umpr_ambient_gemm_b16(), S(stream));
 }
 
 int umpr_embed_gru_bidir_bwd_acc(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
@@ -361,13 +389,13 @@ int umpr_coattention_fwd(const float* Gu, const float* Gi, const float* M, int B
                          float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax,
                          int32_t* argcol, float* rowmax, int32_t* argrow, float* ws, size_t ws_bytes, void* stream) {
   return umpr_coattn_fwd_impl(Gu, Gi, M, B, SL, T, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, colmax, argcol, rowmax,
-                              argrow, ws, ws_bytes, S(stream));
+                              argrow, ws, ws_bytes, umpr_ambient_gemm_b16(), 0, S(stream));
 }
 int umpr_coattention_fwd_bf16(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                               float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax,
                               int32_t* argcol, float* rowmax, int32_t* argrow, float* ws, size_t ws_bytes, void* stream) {
   return umpr_coattn_fwd_impl(Gu, Gi, M, B, SL, T, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, colmax, argcol, rowmax,
-                              argrow, ws, ws_bytes, S(stream), 1);
+                              argrow, ws, ws_bytes, umpr_ambient_gemm_b16(), 1, S(stream));
 }
 int umpr_coattention_fwd_masked(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                                 float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax,
@@ -375,7 +403,7 @@ int umpr_coattention_fwd_masked(const float* Gu, const float* Gi, const float* M
                                 const uint8_t* valid_i, int bf16_scores, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(valid_u && valid_i, "coattention_fwd_masked: null validity mask");
   return umpr_coattn_fwd_impl(Gu, Gi, M, B, SL, T, soft_u, soft_i, atte_u, ld_u, atte_i, ld_i, colmax, argcol, rowmax,
-                              argrow, ws, ws_bytes, S(stream), bf16_scores ? 1 : 0, valid_u, valid_i);
+                              argrow, ws, ws_bytes, umpr_ambient_gemm_b16(), bf16_scores ? 1 : 0, S(stream), valid_u, valid_i);
 }
 int umpr_token_mask(const int64_t* ids, const int32_t* lengths, int N, int L, long pad_id, uint8_t* valid, void* stream) {
   UMPR_REQUIRE(ids && lengths && valid, "token_mask: null pointer");
@@ -389,19 +417,22 @@ int umpr_coattention_bwd(const float* Gu, const float* Gi, const float* M, const
                          const float* d_soft_u, const float* d_soft_i, int B, int SL, float* dGu, float* dGi,
                          float* dM, int accumulate, float* ws, size_t ws_bytes, void* stream) {
   return umpr_coattn_bwd_impl(Gu, Gi, M, T, soft_u, soft_i, colmax, argcol, rowmax, argrow, d_atte_u, ld_du, d_atte_i,
-                              ld_di, d_soft_u, d_soft_i, B, SL, dGu, dGi, dM, accumulate, ws, ws_bytes, S(stream));
+                              ld_di, d_soft_u, d_soft_i, B, SL, dGu, dGi, dM, accumulate, ws, ws_bytes, umpr_ambient_gemm_b16(),
+                              S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ S-Net
 int umpr_snet_fwd(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S_,
                   int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti, void* stream) {
-  return umpr_snet_fwd_impl(X, Ms, Ws, word_soft, wl, B, S_, L, U, P, wsum, self_atte, senti, ld_senti, S(stream));
+  return umpr_snet_fwd_impl(X, Ms, Ws, word_soft, wl, B, S_, L, U, P, wsum, self_atte, senti, ld_senti, umpr_ambient_gemm_b16(),
+                            S(stream));
 }
 int umpr_snet_fwd_masked(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S_,
                          int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
                          const uint8_t* valid, void* stream) {
   UMPR_REQUIRE(valid, "snet_fwd_masked: null validity mask");
-  return umpr_snet_fwd_impl(X, Ms, Ws, word_soft, wl, B, S_, L, U, P, wsum, self_atte, senti, ld_senti, S(stream), valid);
+  return umpr_snet_fwd_impl(X, Ms, Ws, word_soft, wl, B, S_, L, U, P, wsum, self_atte, senti, ld_senti, umpr_ambient_gemm_b16(),
+                            S(stream), valid);
 }
 size_t umpr_snet_bwd_ws_bytes(int B, int S_, int L) { return umpr_snet_bwd_ws_bytes_impl(B, S_, L); }
 int umpr_snet_bwd(const float* X, const float* Ms, const float* Ws, const float* U, const float* P, const float* wsum,
@@ -409,55 +440,72 @@ int umpr_snet_bwd(const float* X, const float* Ms, const float* Ws, const float*
                   int L, int wl, float* dX, float* dMs, float* dWs, float* d_word_soft, float* ws, size_t ws_bytes,
                   void* stream) {
   return umpr_snet_bwd_impl(X, Ms, Ws, U, P, wsum, self_atte, d_senti, ld_ds, d_self_atte, B, S_, L, wl, dX, dMs, dWs,
-                            d_word_soft, ws, ws_bytes, S(stream));
+                            d_word_soft, ws, ws_bytes, umpr_ambient_gemm_b16(), S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ merge
-int umpr_review_merge_fwd(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, int B,
-                          float* out, void* stream) {
-  if (umpr_merge_small() && B <= 256) return umpr_review_merge_fwd_impl(repr_u, repr_i, W_u, W_i, B, out, nullptr, S(stream));
+}  // extern "C"
+
+int umpr_review_merge_fwd_any(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, int B, float* out,
+                              bool gemm_b16, hipStream_t s) {
+  if (umpr_merge_small() && B <= 256) return umpr_review_merge_fwd_impl(repr_u, repr_i, W_u, W_i, B, out, nullptr, s);
   if (g_fc_small && umpr_fc_small_ok(B, D, 2 * D)) {
     // batch-sized M: the register-streaming kernels (no LDS stage, no barrier per k-tile) instead of one workgroup of
     // the tiled GEMM walking 16 k-tiles one global round trip at a time (35 us -> 4 us at B = 32)
-    if (int rc = umpr_fc_small_fwd(repr_u, W_u, nullptr, out, B, D, 2 * D, UMPR_ACT_NONE, nullptr, 0, S(stream))) return rc;
-    return umpr_fc_small_fwd(repr_i, W_i, nullptr, out, B, D, 2 * D, UMPR_ACT_TANH, nullptr, 0, S(stream), 1);
+    if (int rc = umpr_fc_small_fwd(repr_u, W_u, nullptr, out, B, D, 2 * D, UMPR_ACT_NONE, nullptr, 0, s, 0, 0)) return rc;
+    return umpr_fc_small_fwd(repr_i, W_i, nullptr, out, B, D, 2 * D, UMPR_ACT_TANH, nullptr, 0, s, 1, 0);
   }
   UmprGemm g;
   g.A = repr_u; g.lda = 2 * D; g.B = W_u; g.ldb = 2 * D; g.transB = true; g.C = out; g.ldc = D; g.M = B; g.N = D; g.K = 2 * D;
-  if (int rc = umpr_gemm(g, S(stream))) return rc;
+  g.b16 = gemm_b16;
+  if (int rc = umpr_gemm(g, s)) return rc;
   g.A = repr_i; g.B = W_i; g.accumulate = true; g.act = UMPR_ACT_TANH;
-  return umpr_gemm(g, S(stream));
+  return umpr_gemm(g, s);
 }
-size_t umpr_review_merge_bwd_ws_bytes(int B) { return (size_t)B * D * sizeof(float); }
-int umpr_review_merge_bwd(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i,
-                          const float* out, const float* d_out, int B, float* d_repr_u, float* d_repr_i, float* dW_u,
-                          float* dW_i, float* ws, size_t ws_bytes, void* stream) {
+int umpr_review_merge_bwd_any(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, const float* out,
+                              const float* d_out, int B, float* d_repr_u, float* d_repr_i, float* dW_u, float* dW_i, float* ws,
+                              size_t ws_bytes, bool gemm_b16, hipStream_t s) {
   UMPR_REQUIRE(ws_bytes >= umpr_review_merge_bwd_ws_bytes(B), "review_merge_bwd: workspace too small");
   if (umpr_merge_small() && B <= 256)   // tanh' folded into the two kernels
-    return umpr_review_merge_bwd_impl(repr_u, repr_i, W_u, W_i, out, d_out, B, d_repr_u, d_repr_i, dW_u, dW_i, S(stream));
+    return umpr_review_merge_bwd_impl(repr_u, repr_i, W_u, W_i, out, d_out, B, d_repr_u, d_repr_i, dW_u, dW_i, s);
   float* dpre = ws;
-  if (int rc = umpr_tanh_bwd(out, d_out, dpre, (long)B * D, S(stream))) return rc;
+  if (int rc = umpr_tanh_bwd(out, d_out, dpre, (long)B * D, s)) return rc;
   const float* reprs[2] = {repr_u, repr_i};
   const float* Wm[2] = {W_u, W_i};
   float* drepr[2] = {d_repr_u, d_repr_i};
   float* dW[2] = {dW_u, dW_i};
   if (g_fc_small && umpr_fc_small_ok(B, D, 2 * D)) {
     for (int q = 0; q < 2; ++q) {
-      if (int rc = umpr_fc_small_dx(dpre, Wm[q], drepr[q], B, D, 2 * D, nullptr, 0, S(stream))) return rc;
-      if (int rc = umpr_fc_small_dw(dpre, reprs[q], dW[q], B, D, 2 * D, S(stream))) return rc;
+      if (int rc = umpr_fc_small_dx(dpre, Wm[q], drepr[q], B, D, 2 * D, nullptr, 0, s, 0)) return rc;
+      if (int rc = umpr_fc_small_dw(dpre, reprs[q], dW[q], B, D, 2 * D, s, 0)) return rc;
     }
     return 0;
   }
   for (int q = 0; q < 2; ++q) {
     UmprGemm g;  // d_repr = dpre W
     g.A = dpre; g.lda = D; g.B = Wm[q]; g.ldb = 2 * D; g.C = drepr[q]; g.ldc = 2 * D; g.M = B; g.N = 2 * D; g.K = D;
-    if (int rc = umpr_gemm(g, S(stream))) return rc;
+    g.b16 = gemm_b16;
+    if (int rc = umpr_gemm(g, s)) return rc;
     UmprGemm h;  // dW = dpre^T repr
     h.A = dpre; h.lda = D; h.transA = true; h.B = reprs[q]; h.ldb = 2 * D; h.C = dW[q]; h.ldc = 2 * D; h.M = D;
-    h.N = 2 * D; h.K = B;
-    if (int rc = umpr_gemm(h, S(stream))) return rc;
+    h.N = 2 * D; h.K = B; h.b16 = gemm_b16;
+    if (int rc = umpr_gemm(h, s)) return rc;
   }
   return 0;
+}
+
+extern "C" {
+
+int umpr_review_merge_fwd(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, int B,
+                          float* out, void* stream) {
+  return umpr_review_merge_fwd_any(repr_u, repr_i, W_u, W_i, B, out, umpr_ambient_gemm_b16(), S(stream));
+}
+size_t umpr_review_merge_bwd_ws_bytes(int B) { return (size_t)B * D * sizeof(float); }
+int umpr_review_merge_bwd(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i,
+                          const float* out, const float* d_out, int B, float* d_repr_u, float* d_repr_i, float* dW_u,
+                          float* dW_i, float* ws, size_t ws_bytes, void* stream) {
+  return umpr_review_merge_bwd_any(repr_u, repr_i, W_u, W_i, out, d_out, B, d_repr_u, d_repr_i, dW_u, dW_i, ws, ws_bytes,
+                                   umpr_ambient_gemm_b16(), S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ C-Net head
@@ -466,14 +514,14 @@ int umpr_cnet_head_fwd(const float* X, const float* Wc, const float* bc, const f
                        int B, int S_, int L, int KC, int KS, int V, float* Y, float* cmax, int32_t* argl, float* sp,
                        float* view_p, float* final_, float* ws, size_t ws_bytes, void* stream) {
   return umpr_cnet_head_fwd_impl(X, Wc, bc, Wl, bl, thr, B, S_, L, KC, KS, V, Y, cmax, argl, sp, view_p, final_, ws,
-                                 ws_bytes, S(stream));
+                                 ws_bytes, umpr_ambient_gemm_b16(), S(stream));
 }
 int umpr_cnet_head_fwd_masked(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl, float thr,
                               int B, int S_, int L, int KC, int KS, int V, float* Y, float* cmax, int32_t* argl, float* sp,
                               float* view_p, float* final_, const uint8_t* valid, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(valid, "cnet_head_fwd_masked: null validity mask");
   return umpr_cnet_head_fwd_impl(X, Wc, bc, Wl, bl, thr, B, S_, L, KC, KS, V, Y, cmax, argl, sp, view_p, final_, ws,
-                                 ws_bytes, S(stream), valid);
+                                 ws_bytes, umpr_ambient_gemm_b16(), S(stream), valid);
 }
 size_t umpr_cnet_head_bwd_ws_bytes(int B, int S_, int L, int KC, int KS, int V) {
   return umpr_cnet_bwd_ws_bytes(B, S_, L, KC, KS, V);
@@ -483,7 +531,7 @@ int umpr_cnet_head_bwd(const float* X, const float* Wc, const float* Wl, const f
                        int S_, int L, int KC, int KS, int V, float* dX, int accumulate_dX, int accumulate_w, float* dWc,
                        float* dbc, float* dWl, float* dbl, float* ws, size_t ws_bytes, void* stream) {
   return umpr_cnet_head_bwd_impl(X, Wc, Wl, cmax, argl, sp, view_p, d_final, d_view_p, B, S_, L, KC, KS, V, dX,
-                                 accumulate_dX, accumulate_w, dWc, dbc, dWl, dbl, ws, ws_bytes, S(stream));
+                                 accumulate_dX, accumulate_w, dWc, dbc, dWl, dbl, ws, ws_bytes, umpr_ambient_gemm_b16(), S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ gate
@@ -614,27 +662,25 @@ namespace {
 // classifier activations: pool5 input [n][25088], ReLU outputs of fc1 / fc2 and their dropout outputs ([n][4096] each)
 struct ClsActs { const float* pool5; float* fc[2]; float* drop[2]; };
 
-// Above 128 rows umpr_fc_small_ok fails and the classifier's products run on the generic GEMM: under the bf16 entry points they
-// must round their operands there too (before, they silently ran in fp32): UmprB16Scope.
-
+// Two precisions, because the entry points apply two rules: fc_bf16 (the *_bf16 entry points) for the fc kernels, gemm_b16 (those,
+// or the thread's switch) for the generic GEMM that runs the products above 128 rows, where umpr_fc_small_ok fails.
 int classifier_fwd_impl(const float* const* params, int n, int train, int use_masks, uint64_t seed, const ClsActs& A,
-                        uint8_t* masks, float* out, float* ws, size_t ws_bytes, hipStream_t s, int bf16 = 0) {
+                        uint8_t* masks, float* out, float* ws, size_t ws_bytes, hipStream_t s, int fc_bf16, bool gemm_b16) {
   // AdaptiveAvgPool2d(7) is the identity on the 7x7 map a 224x224 image produces
   const float* x = A.pool5;
-  UmprB16Scope b16_scope(bf16);
   for (int j = 0; j < 3; ++j) {
     float* y = j < 2 ? A.fc[j] : out;
     const int act = j < 2 ? UMPR_ACT_RELU : UMPR_ACT_NONE;
     if (g_fc_small && umpr_fc_small_ok(n, kFc[j][1], kFc[j][0])) {
       // batch-sized M: register-streaming kernels (fc_small.hip) instead of the LDS-tiled GEMM
       if (int rc = umpr_fc_small_fwd(x, params[26 + 2 * j], params[27 + 2 * j], y, n, kFc[j][1], kFc[j][0], act, ws,
-                                     ws_bytes, s, 0, bf16)) return rc;
+                                     ws_bytes, s, 0, fc_bf16)) return rc;
     } else {
       UmprGemm g;
       g.A = x; g.lda = kFc[j][0]; g.B = params[26 + 2 * j]; g.ldb = kFc[j][0]; g.transB = true;
       g.C = y; g.ldc = kFc[j][1]; g.M = n; g.N = kFc[j][1]; g.K = kFc[j][0];
       g.bias = params[27 + 2 * j]; g.bias_mode = 1; g.act = act;
-      g.split_k = 0; g.ws = ws; g.ws_bytes = ws_bytes;
+      g.split_k = 0; g.ws = ws; g.ws_bytes = ws_bytes; g.b16 = gemm_b16;
       if (int rc = umpr_gemm(g, s)) return rc;
     }
     x = y;
@@ -662,7 +708,8 @@ int umpr_vgg16_classifier_fwd(const float* const* params, int n, int train, int 
                               uint8_t* masks, float* out, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(n > 0 && params && acts && out, "vgg16_classifier_fwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_fwd_ws_bytes(n), "vgg16_classifier_fwd: workspace too small");
-  return classifier_fwd_impl(params, n, train, use_masks, seed, cls_acts_full(acts, n), masks, out, ws, ws_bytes, S(stream));
+  return classifier_fwd_impl(params, n, train, use_masks, seed, cls_acts_full(acts, n), masks, out, ws, ws_bytes, S(stream), 0,
+                             umpr_ambient_gemm_b16());
 }
 
 size_t umpr_vgg16_cls_arena_bytes(int n_img) { return ((size_t)n_img * 25088 + (size_t)4 * n_img * 4096) * sizeof(float); }
@@ -673,7 +720,7 @@ int umpr_vgg16_classifier_fwd_compact(const float* const* params, int n, int tra
   UMPR_REQUIRE(n > 0 && params && cls_arena && out, "vgg16_classifier_fwd_compact: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_fwd_ws_bytes(n), "vgg16_classifier_fwd_compact: workspace too small");
   return classifier_fwd_impl(params, n, train, use_masks, seed, cls_acts_compact(cls_arena, n), masks, out, ws, ws_bytes,
-                             S(stream));
+                             S(stream), 0, umpr_ambient_gemm_b16());
 }
 
 int umpr_vgg16_fwd(const float* images, const float* const* params, int n, int train, int use_masks, uint64_t seed,
@@ -690,8 +737,7 @@ size_t umpr_vgg16_classifier_bwd_ws_bytes(int n_img) { return vgg_cls_bwd_ws(nul
 namespace {
 int classifier_bwd_impl(const float* const* params, int n, int train, const ClsActs& A, const uint8_t* masks,
                         const float* d_out, float* const* grads, float* d_pool5, float* ws, size_t ws_bytes, hipStream_t s,
-                        int bf16 = 0) {
-  UmprB16Scope b16_scope(bf16);
+                        int fc_bf16, bool gemm_b16) {
   const VggClsBwdWs W = vgg_cls_bwd_ws(ws, n);
   const float* g = d_out;  // gradient w.r.t. the current layer's output
   float* cur = W.gA; float* oth = W.gB;
@@ -706,22 +752,23 @@ int classifier_bwd_impl(const float* const* params, int n, int train, const ClsA
     }
     const bool small = g_fc_small && umpr_fc_small_ok(n, fout, fin);
     if (small) {  // dW[fout][fin] = g^T xin
-      if (int rc = umpr_fc_small_dw(g, xin, grads[26 + 2 * j], n, fout, fin, s, bf16)) return rc;
+      if (int rc = umpr_fc_small_dw(g, xin, grads[26 + 2 * j], n, fout, fin, s, fc_bf16)) return rc;
     } else {
       UmprGemm w;
       w.A = g; w.lda = fout; w.transA = true; w.B = xin; w.ldb = fin; w.C = grads[26 + 2 * j]; w.ldc = fin;
-      w.M = fout; w.N = fin; w.K = n;
+      w.M = fout; w.N = fin; w.K = n; w.b16 = gemm_b16;
       if (int rc = umpr_gemm(w, s)) return rc;
     }
     if (int rc = umpr_colsum_rows(g, n, fout, fout, grads[27 + 2 * j], 0, s)) return rc;
     float* dxo = j == 0 ? d_pool5 : cur;
     if (!dxo) break;   // fc1 with d_pool5 == NULL: nobody reads the data gradient, so the second pass over fc1's matrix is not launched
     if (small) {  // dx[n][fin] = g W
-      if (int rc = umpr_fc_small_dx(g, params[26 + 2 * j], dxo, n, fout, fin, W.scratch, W.scratch_bytes, s, bf16)) return rc;
+      if (int rc = umpr_fc_small_dx(g, params[26 + 2 * j], dxo, n, fout, fin, W.scratch, W.scratch_bytes, s, fc_bf16)) return rc;
     } else {
       UmprGemm d;
       d.A = g; d.lda = fout; d.B = params[26 + 2 * j]; d.ldb = fin; d.C = dxo; d.ldc = fin; d.M = n;
       d.N = fin; d.K = fout; d.split_k = 0; d.ws = W.scratch; d.ws_bytes = W.scratch_bytes;
+      d.b16 = gemm_b16;
       if (int rc = umpr_gemm(d, s)) return rc;
     }
     g = dxo; float* t = cur; cur = oth; oth = t;
@@ -736,7 +783,7 @@ int umpr_vgg16_classifier_bwd(const float* const* params, int n, int train, cons
   UMPR_REQUIRE(n > 0 && params && acts && grads && d_out, "vgg16_classifier_bwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_full(const_cast<float*>(acts), n), masks, d_out, grads, d_pool5,
-                             ws, ws_bytes, S(stream));
+                             ws, ws_bytes, S(stream), 0, umpr_ambient_gemm_b16());
 }
 
 int umpr_vgg16_classifier_bwd_compact(const float* const* params, int n, int train, const float* cls_arena,
@@ -745,7 +792,7 @@ int umpr_vgg16_classifier_bwd_compact(const float* const* params, int n, int tra
   UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out, "vgg16_classifier_bwd_compact: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd_compact: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_compact(const_cast<float*>(cls_arena), n), masks, d_out, grads,
-                             d_pool5, ws, ws_bytes, S(stream));
+                             d_pool5, ws, ws_bytes, S(stream), 0, umpr_ambient_gemm_b16());
 }
 
 // Mixed precision (BASELINE.json configs[4]): the three products of each layer take bf16-rounded operands on the bf16
@@ -756,7 +803,7 @@ int umpr_vgg16_classifier_fwd_compact_bf16(const float* const* params, int n, in
   UMPR_REQUIRE(n > 0 && params && cls_arena && out, "vgg16_classifier_fwd_compact_bf16: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_fwd_ws_bytes(n), "vgg16_classifier_fwd_compact_bf16: workspace too small");
   return classifier_fwd_impl(params, n, train, use_masks, seed, cls_acts_compact(cls_arena, n), masks, out, ws, ws_bytes,
-                             S(stream), 1);
+                             S(stream), 1, true);
 }
 int umpr_vgg16_classifier_bwd_compact_bf16(const float* const* params, int n, int train, const float* cls_arena,
                                            const uint8_t* masks, const float* d_out, float* const* grads, float* d_pool5,
@@ -764,7 +811,7 @@ int umpr_vgg16_classifier_bwd_compact_bf16(const float* const* params, int n, in
   UMPR_REQUIRE(n > 0 && params && cls_arena && grads && d_out, "vgg16_classifier_bwd_compact_bf16: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_vgg16_classifier_bwd_ws_bytes(n), "vgg16_classifier_bwd_compact_bf16: workspace too small");
   return classifier_bwd_impl(params, n, train, cls_acts_compact(const_cast<float*>(cls_arena), n), masks, d_out, grads,
-                             d_pool5, ws, ws_bytes, S(stream), 1);
+                             d_pool5, ws, ws_bytes, S(stream), 1, true);
 }
 
 size_t umpr_vgg16_features_bwd_ws_bytes(int n_img) { return vgg_feat_bwd_ws(nullptr, n_img).bytes; }

@@ -247,7 +247,7 @@ size_t umpr_coattn_fwd_ws_bytes(int B, int SL) { return coattn_fwd_ws(nullptr, B
 
 int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                          float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax, int* argcol,
-                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores,
+                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, bool gemm_b16, int bf16_scores, hipStream_t s,
                          const uint8_t* valid_u, const uint8_t* valid_i) {
   UMPR_REQUIRE(B > 0 && SL > 0, "coattn: bad shape");
   UMPR_REQUIRE(!valid_u == !valid_i, "coattn: one validity mask without the other");
@@ -256,7 +256,7 @@ int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B
   UMPR_REQUIRE(ws_bytes >= W.bytes, "coattn: workspace too small");
   const int nblk = cdiv(SL, 64);
   UmprGemm g;
-  g.A = Gi; g.lda = D; g.B = M; g.ldb = D; g.C = T; g.ldc = D; g.M = B * SL; g.N = D; g.K = D;
+  g.A = Gi; g.lda = D; g.B = M; g.ldb = D; g.C = T; g.ldc = D; g.M = B * SL; g.N = D; g.K = D; g.b16 = gemm_b16;
   if (int rc = umpr_gemm(g, s)) return rc;
   // one 64 x 64 score tile per workgroup: nblk^2 * B workgroups instead of nblk * B serial tile loops
   const int ksplit = nblk;
@@ -280,7 +280,7 @@ int umpr_coattn_bwd_impl(const float* Gu, const float* Gi, const float* M, const
                          const float* soft_i, const float* colmax, const int* argcol, const float* rowmax,
                          const int* argrow, const float* d_atte_u, long ld_du, const float* d_atte_i, long ld_di,
                          const float* d_soft_u, const float* d_soft_i, int B, int SL, float* dGu, float* dGi, float* dM,
-                         int accumulate, float* ws, size_t ws_bytes, hipStream_t s) {
+                         int accumulate, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s) {
   const CoattnBwdWs W = coattn_bwd_ws(ws, B, SL);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "coattn_bwd: workspace too small");
   float *dSc = W.dSc, *dSr = W.dSr, *dT = W.dT;
@@ -293,11 +293,11 @@ int umpr_coattn_bwd_impl(const float* Gu, const float* Gi, const float* M, const
   // dG_i += dT M^T
   UmprGemm g;
   g.A = dT; g.lda = D; g.B = M; g.ldb = D; g.transB = true; g.C = dGi; g.ldc = D; g.M = B * SL; g.N = D; g.K = D;
-  g.accumulate = true;
+  g.accumulate = true; g.b16 = gemm_b16;
   if (int rc = umpr_gemm(g, s)) return rc;
   // dM = G_i^T dT   (K = B*SL, split-K)
   UmprGemm h;
   h.A = Gi; h.lda = D; h.transA = true; h.B = dT; h.ldb = D; h.C = dM; h.ldc = D; h.M = D; h.N = D; h.K = B * SL;
-  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes;
+  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes; h.b16 = gemm_b16;
   return umpr_gemm(h, s);
 }

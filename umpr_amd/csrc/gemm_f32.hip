@@ -244,11 +244,6 @@ void launch_tile(const GemmParams& p, bool ta, bool tb, dim3 grid, hipStream_t s
 
 }  // namespace
 
-// per host thread: products issued while it is set round their operands to bf16 (umpr_set_gemm_bf16, mixed-precision mode)
-static thread_local int t_gemm_b16 = 0;
-void umpr_gemm_set_b16(int on) { t_gemm_b16 = on; }
-int umpr_gemm_b16() { return t_gemm_b16; }
-
 int umpr_gemm(const UmprGemm& g, hipStream_t stream) {
   UMPR_REQUIRE(g.M > 0 && g.N > 0 && g.K >= 0, "gemm: bad shape M=%d N=%d K=%d", g.M, g.N, g.K);
   UMPR_REQUIRE(g.A && g.B && g.C, "gemm: null operand");
@@ -285,7 +280,7 @@ int umpr_gemm(const UmprGemm& g, hipStream_t stream) {
     // latency, not by the MFMA pipe or HBM - more workgroups in flight (3 fit a CU) hide it
     static const int small_m_target = umpr_env_int("UMPR_GEMM_SMALL_M_WGS", 512);
     static const int b16_target = umpr_env_int("UMPR_GEMM_B16_WGS", 512);
-    const int target = t_gemm_b16 ? b16_target : (g.M <= 64 ? small_m_target : 512);
+    const int target = g.b16 ? b16_target : (g.M <= 64 ? small_m_target : 512);
     if (tiles < target / 2 && g.K >= 512) {
       split = (int)((target + tiles - 1) / tiles);
       const int maxs = g.K / 128;
@@ -307,7 +302,7 @@ int umpr_gemm(const UmprGemm& g, hipStream_t stream) {
   p.split_k = split; p.k_per_split = kps; p.ws = g.ws;
   dim3 grid(tn, tm, split);
   UmprProfScope prof(UMPR_K_GEMM, 2.0 * g.M * g.N * g.K, stream);
-  if (t_gemm_b16) {
+  if (g.b16) {
     if (BM == 128 && BN == 128) launch_tile_b16<128, 128>(p, g.transA, g.transB, grid, stream);
     else if (BM == 64 && BN == 128) launch_tile_b16<64, 128>(p, g.transA, g.transB, grid, stream);
     else if (BM == 128 && BN == 64) launch_tile_b16<128, 64>(p, g.transA, g.transB, grid, stream);

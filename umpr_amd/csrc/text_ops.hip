@@ -899,11 +899,11 @@ int umpr_sq_err_accumulate_impl(const float* pred, const float* label, long n, d
 // ---- S-Net ---------------------------------------------------------------------------------------------------
 int umpr_snet_fwd_impl(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S,
                        int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
-                       hipStream_t s, const uint8_t* valid) {
+                       bool gemm_b16, hipStream_t s, const uint8_t* valid) {
   UMPR_REQUIRE(L >= 1 && L <= 256, "snet: sentence length %d outside 1..256", L);
   UmprGemm g;
   g.A = X; g.lda = D; g.B = Ms; g.ldb = D; g.transB = true; g.C = U; g.ldc = AT; g.M = B * S * L; g.N = AT; g.K = D;
-  g.act = UMPR_ACT_TANH;
+  g.act = UMPR_ACT_TANH; g.b16 = gemm_b16;
   if (int rc = umpr_gemm(g, s)) return rc;
   SnetFwdParams p{X, U, Ws, word_soft, wl, P, wsum, self_atte, senti, ld_senti, S, L};
   const long nsent = (long)B * S;
@@ -941,7 +941,7 @@ size_t umpr_snet_bwd_ws_bytes_impl(int B, int S, int L) { return snet_bwd_ws(nul
 int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const float* U, const float* P,
                        const float* wsum, const float* self_atte, const float* d_senti, long ld_ds,
                        const float* d_self_atte, int B, int S, int L, int wl, float* dX, float* dMs, float* dWs,
-                       float* d_word_soft, float* ws, size_t ws_bytes, hipStream_t s) {
+                       float* d_word_soft, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s) {
   const SnetBwdWs W = snet_bwd_ws(ws, B, S, L);
   UMPR_REQUIRE(ws_bytes >= W.bytes, "snet_bwd: workspace too small");
   const long nsent = (long)B * S;
@@ -955,10 +955,11 @@ int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const f
   const int R = B * S * L;
   UmprGemm g;  // dX += dPre Ms
   g.A = dPre; g.lda = AT; g.B = Ms; g.ldb = D; g.C = dX; g.ldc = D; g.M = R; g.N = D; g.K = AT; g.accumulate = true;
+  g.b16 = gemm_b16;
   if (int rc = umpr_gemm(g, s)) return rc;
   UmprGemm h;  // dMs = dPre^T X
   h.A = dPre; h.lda = AT; h.transA = true; h.B = X; h.ldb = D; h.C = dMs; h.ldc = D; h.M = AT; h.N = D; h.K = R;
-  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes;
+  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes; h.b16 = gemm_b16;
   if (int rc = umpr_gemm(h, s)) return rc;
   colsum_stage2_kernel<<<1, 1024, 0, s>>>(dWs_part, nwg, AT, dWs, 0);
   UMPR_LAUNCH_CHECK("snet_dWs");
@@ -971,8 +972,8 @@ size_t umpr_cnet_fwd_ws_bytes(int B, int S, int L, int KS) { (void)B; (void)S; (
 
 int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl,
                             float thr, int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int* argl,
-                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, hipStream_t s,
-                            const uint8_t* valid) {
+                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, bool gemm_b16,
+                            hipStream_t s, const uint8_t* valid) {
   UMPR_REQUIRE(ws_bytes >= umpr_cnet_fwd_ws_bytes(B, S, L, KS), "cnet: workspace too small");
   const long R = (long)B * S * L;
   // nn.Conv1d(padding=(KS-1)/2) (src/model.py:93): an even KS yields L - 1 positions; the window GEMM computes L (the last one
@@ -985,7 +986,7 @@ int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, co
   UmprGemm g;   // Y = relu(win(X) Wp^T + bc): X read in place through the sliding window
   g.A = X; g.lda = D; g.winA_L = L; g.winA_D = D; g.winA_pad = pad;
   g.B = Wp; g.ldb = D * KS; g.transB = true; g.C = Y; g.ldc = KC; g.M = (int)R; g.N = KC;
-  g.K = D * KS; g.bias = bc; g.bias_mode = 1; g.act = UMPR_ACT_RELU;
+  g.K = D * KS; g.bias = bc; g.bias_mode = 1; g.act = UMPR_ACT_RELU; g.b16 = gemm_b16;
   if (int rc = umpr_gemm(g, s)) return rc;
   CnetHeadFwdParams p{Y, Wl, bl, thr, cmax, argl, sp, view_p, final_, S, L, KC, V, Lout};
   const long nsent = (long)B * S;
@@ -1012,7 +1013,7 @@ size_t umpr_cnet_bwd_ws_bytes(int B, int S, int L, int KC, int KS, int V) { retu
 int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, const float* cmax, const int* argl,
                             const float* sp, const float* view_p, const float* d_final, const float* d_view_p, int B,
                             int S, int L, int KC, int KS, int V, float* dX, int accumulate_dX, int accumulate_w, float* dWc,
-                            float* dbc, float* dWl, float* dbl, float* ws, size_t ws_bytes, hipStream_t s) {
+                            float* dbc, float* dWl, float* dbl, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s) {
   // every argument check comes before the first launch or memset: a refused call writes nothing
   UMPR_REQUIRE(KS >= 1 && (KC & 3) == 0 && KC <= 512, "cnet_bwd: kernel size %d / %d filters (a multiple of 4, at most 512)", KS, KC);
   const size_t head_lds = ((size_t)4 * V * KC + (size_t)8 * V) * sizeof(float);   // cnet_head_bwd_kernel: dW[4][V*KC], db[4][V], dsig[4][V]
@@ -1035,7 +1036,7 @@ int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, co
   UmprGemm h;  // dWp[KC][CK] = dY^T win(X)
   h.A = dY; h.lda = KC; h.transA = true; h.B = X; h.ldb = D; h.winB_L = L; h.winB_D = D; h.winB_pad = pad;
   h.C = dWp; h.ldc = CK; h.M = KC; h.N = CK; h.K = (int)R;
-  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes;
+  h.split_k = 0; h.ws = W.slab; h.ws_bytes = W.slab_bytes; h.b16 = gemm_b16;
   if (int rc = umpr_gemm(h, s)) return rc;
   cnet_weight_order_kernel<<<nblocks((long)KC * CK), 256, 0, s>>>(dWp, dWc, KC, D, KS, 2, accumulate_w);
   cnet_weight_order_kernel<<<nblocks((long)KC * CK), 256, 0, s>>>(Wc, Wq, KC, D, KS, 1, 0);
@@ -1045,6 +1046,7 @@ int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, co
   // (= pad for odd KS)
   g.A = dY; g.lda = KC; g.winA_L = L; g.winA_D = KC; g.winA_pad = KS - 1 - pad;
   g.B = Wq; g.ldb = D; g.C = dX; g.ldc = D; g.M = (int)R; g.N = D; g.K = KS * KC; g.accumulate = accumulate_dX != 0;
+  g.b16 = gemm_b16;
   if (int rc = umpr_gemm(g, s)) return rc;
   return 0;
 }

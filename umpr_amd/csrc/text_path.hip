@@ -4,7 +4,8 @@
 // of UMPR-R is 0.9 ms of kernels, and a host that issues every stage through Python (one ctypes call, a handful of tensor
 // allocations and an autograd node each) needs longer than that to enqueue them; here the stages are issued back to back from
 // C++ into ONE caller-owned arena (everything the backward pass reads) and one scratch buffer.  The stage functions are the
-// per-stage entry points of api.hip, unchanged: these wrappers only carve buffers and call them in order.
+// internal forms of the per-stage entry points of api.hip: these wrappers only carve buffers and call them in order, each with the
+// call's one GEMM precision (gemm_b16: the entry point's b16_gemm argument or the thread's umpr_set_gemm_bf16).
 #include <algorithm>
 
 #include "umpr_common.h"
@@ -151,39 +152,32 @@ size_t umpr_review_net_ws_bytes(int B, int S, int L, int E) { return review_ws(n
 // valid_pair (or null): the validity bytes [2N][L] of umpr_token_mask on ids_pair - user rows [B][S*L], then item rows
 // dst_row: the output row of each input row of the pair (umpr_embed_gru_bidir_fwd): `order` for the reference's double un-sort
 static int review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
-                          const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, int b16_scores,
+                          const int32_t* order, const int32_t* dst_row, int B, int S, int L, bool gemm_b16, int b16_scores,
                           int need_grad, void* arena, float* out, float* ws, size_t ws_bytes, void* stream, const uint8_t* valid_pair) {
   UMPR_REQUIRE(ids_pair && emb && P && lengths && order && dst_row && arena && out && B > 0 && S > 0 && L > 0, "review_net_fwd: bad arguments");
   UMPR_REQUIRE(ws_bytes >= umpr_review_net_ws_bytes(B, S, L, E), "review_net_fwd: workspace too small");
   if (poison(ws, ws_bytes, stream) || poison(arena, umpr_review_net_arena_bytes(B, S, L), stream)) return -2;
   const ReviewArena A = review_arena(arena, B, S, L);
   const int N = B * S, SL = S * L;
-  UmprB16Scope b16(b16_gemm);
-  if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], lengths, order, dst_row,
-                                        2 * N, L, A.gru_out, need_grad ? A.gru_saved : nullptr, ws, ws_bytes, stream)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = umpr_embed_gru_fwd_impl(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], lengths, order, dst_row,
+                                       2 * N, L, A.gru_out, need_grad ? A.gru_saved : nullptr, ws, ws_bytes, gemm_b16, s)) return rc;
   const float* gru_u = A.gru_out;
   const float* gru_i = A.gru_out + (size_t)N * L * D;
-  if (valid_pair) {
-    const uint8_t* valid_u = valid_pair;
-    const uint8_t* valid_i = valid_pair + (size_t)N * L;
-    if (int rc = umpr_coattention_fwd_masked(gru_u, gru_i, P[8], B, SL, A.T, A.soft_u, A.soft_i, A.repr_u, 2 * D, A.repr_i, 2 * D,
-                                             A.colmax, A.argcol, A.rowmax, A.argrow, valid_u, valid_i, b16_scores, ws, ws_bytes,
-                                             stream)) return rc;
-    if (int rc = umpr_snet_fwd_masked(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D,
-                                      2 * D, valid_u, stream)) return rc;
-    if (int rc = umpr_snet_fwd_masked(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D,
-                                      2 * D, valid_i, stream)) return rc;
-  } else {
-    if (int rc = (b16_scores ? umpr_coattention_fwd_bf16 : umpr_coattention_fwd)(gru_u, gru_i, P[8], B, SL, A.T, A.soft_u, A.soft_i, A.repr_u,
-                                                                           2 * D, A.repr_i, 2 * D, A.colmax, A.argcol, A.rowmax,
-                                                                           A.argrow, ws, ws_bytes, stream)) return rc;
-    if (int rc = umpr_snet_fwd(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D, 2 * D, stream)) return rc;
-    if (int rc = umpr_snet_fwd(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D, 2 * D, stream)) return rc;
-  }
+  // the validity bytes of the user and of the item rows, or no mask at all
+  const uint8_t* valid_u = valid_pair;
+  const uint8_t* valid_i = valid_pair ? valid_pair + (size_t)N * L : nullptr;
+  if (int rc = umpr_coattn_fwd_impl(gru_u, gru_i, P[8], B, SL, A.T, A.soft_u, A.soft_i, A.repr_u, 2 * D, A.repr_i, 2 * D, A.colmax,
+                                    A.argcol, A.rowmax, A.argrow, ws, ws_bytes, gemm_b16, b16_scores ? 1 : 0, s, valid_u, valid_i))
+    return rc;
+  if (int rc = umpr_snet_fwd_impl(gru_u, P[9], P[10], A.soft_u, L, B, S, L, A.su.U, A.su.P, A.su.wsum, A.su.sa, A.repr_u + D, 2 * D,
+                                  gemm_b16, s, valid_u)) return rc;
+  if (int rc = umpr_snet_fwd_impl(gru_i, P[11], P[12], A.soft_i, L, B, S, L, A.si.U, A.si.P, A.si.wsum, A.si.sa, A.repr_i + D, 2 * D,
+                                  gemm_b16, s, valid_i)) return rc;
   if (B <= 256 && umpr_merge_small())   // one kernel writes the caller's tensor and the arena's copy for backward
-    return umpr_review_merge_fwd_impl(A.repr_u, A.repr_i, P[13], P[14], B, out, A.merged, static_cast<hipStream_t>(stream));
-  if (int rc = umpr_review_merge_fwd(A.repr_u, A.repr_i, P[13], P[14], B, A.merged, stream)) return rc;
-  if (hipMemcpyAsync(out, A.merged, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)) != hipSuccess) {
+    return umpr_review_merge_fwd_impl(A.repr_u, A.repr_i, P[13], P[14], B, out, A.merged, s);
+  if (int rc = umpr_review_merge_fwd_any(A.repr_u, A.repr_i, P[13], P[14], B, A.merged, gemm_b16, s)) return rc;
+  if (hipMemcpyAsync(out, A.merged, (size_t)B * D * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
     umpr_set_error("review_net_fwd: copy failed");
     return -2;
   }
@@ -193,27 +187,27 @@ static int review_net_fwd(const int64_t* ids_pair, const float* emb, int E, cons
 int umpr_review_net_fwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad, void* arena,
                         float* out, float* ws, size_t ws_bytes, void* stream) {
-  return review_net_fwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
-                        stream, nullptr);
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm || umpr_ambient_gemm_b16(), b16_scores, need_grad, arena,
+                        out, ws, ws_bytes, stream, nullptr);
 }
 int umpr_review_net_fwd_masked(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                                const int32_t* order, int B, int S, int L, int b16_gemm, int b16_scores, int need_grad,
                                void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair, void* stream) {
   UMPR_REQUIRE(valid_pair, "review_net_fwd_masked: null validity mask");
-  return review_net_fwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws, ws_bytes,
-                        stream, valid_pair);
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm || umpr_ambient_gemm_b16(), b16_scores, need_grad, arena,
+                        out, ws, ws_bytes, stream, valid_pair);
 }
 int umpr_review_net_fwd_ex(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                            const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, int b16_scores,
                            int need_grad, void* arena, float* out, float* ws, size_t ws_bytes, const uint8_t* valid_pair,
                            void* stream) {
-  return review_net_fwd(ids_pair, emb, E, P, lengths, order, dst_row, B, S, L, b16_gemm, b16_scores, need_grad, arena, out, ws,
-                        ws_bytes, stream, valid_pair);
+  return review_net_fwd(ids_pair, emb, E, P, lengths, order, dst_row, B, S, L, b16_gemm || umpr_ambient_gemm_b16(), b16_scores, need_grad, arena,
+                        out, ws, ws_bytes, stream, valid_pair);
 }
 
 // grads: 15 pointers in the order of params, each overwritten; dx_pair (or NULL): the token gradient for a trainable table
 static int review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
-                          const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, const void* arena,
+                          const int32_t* order, const int32_t* dst_row, int B, int S, int L, bool gemm_b16, const void* arena,
                           const float* d_out, float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE(ids_pair && emb && P && G && lengths && order && dst_row && arena && d_out, "review_net_bwd: bad arguments");
   const ReviewWs W = review_ws(ws, B, S, L, E);
@@ -227,31 +221,34 @@ static int review_net_bwd(const int64_t* ids_pair, const float* emb, int E, cons
   const float* gru_i = A.gru_out + (size_t)N * L * D;
   float* dGu = dG;
   float* dGi = dG + (size_t)N * L * D;
-  UmprB16Scope b16(b16_gemm);
+  hipStream_t s = static_cast<hipStream_t>(stream);
   debug_sync(0);
-  if (int rc = umpr_review_merge_bwd(A.repr_u, A.repr_i, P[13], P[14], A.merged, d_out, B, d_repr_u, d_repr_i, G[13], G[14], sws, swsb, stream)) return rc;
+  if (int rc = umpr_review_merge_bwd_any(A.repr_u, A.repr_i, P[13], P[14], A.merged, d_out, B, d_repr_u, d_repr_i, G[13], G[14], sws, swsb,
+                                         gemm_b16, s)) return rc;
   debug_sync(1);
-  if (int rc = umpr_snet_bwd(gru_u, P[9], P[10], A.su.U, A.su.P, A.su.wsum, A.su.sa, d_repr_u + D, 2 * D, nullptr, B, S, L, L, dGu,
-                             G[9], G[10], ds_u, sws, swsb, stream)) return rc;
+  if (int rc = umpr_snet_bwd_impl(gru_u, P[9], P[10], A.su.U, A.su.P, A.su.wsum, A.su.sa, d_repr_u + D, 2 * D, nullptr, B, S, L, L, dGu,
+                                  G[9], G[10], ds_u, sws, swsb, gemm_b16, s)) return rc;
   debug_sync(2);
-  if (int rc = umpr_snet_bwd(gru_i, P[11], P[12], A.si.U, A.si.P, A.si.wsum, A.si.sa, d_repr_i + D, 2 * D, nullptr, B, S, L, L, dGi,
-                             G[11], G[12], ds_i, sws, swsb, stream)) return rc;
+  if (int rc = umpr_snet_bwd_impl(gru_i, P[11], P[12], A.si.U, A.si.P, A.si.wsum, A.si.sa, d_repr_i + D, 2 * D, nullptr, B, S, L, L, dGi,
+                                  G[11], G[12], ds_i, sws, swsb, gemm_b16, s)) return rc;
   debug_sync(3);
-  if (int rc = umpr_coattention_bwd(gru_u, gru_i, P[8], A.T, A.soft_u, A.soft_i, A.colmax, A.argcol, A.rowmax, A.argrow, d_repr_u,
-                                    2 * D, d_repr_i, 2 * D, ds_u, ds_i, B, (int)SL, dGu, dGi, G[8], 1, sws, swsb, stream)) return rc;
+  if (int rc = umpr_coattn_bwd_impl(gru_u, gru_i, P[8], A.T, A.soft_u, A.soft_i, A.colmax, A.argcol, A.rowmax, A.argrow, d_repr_u,
+                                    2 * D, d_repr_i, 2 * D, ds_u, ds_i, B, (int)SL, dGu, dGi, G[8], 1, sws, swsb, gemm_b16, s)) return rc;
   debug_sync(4);
-  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], lengths, order, dst_row, (int)(2 * N), L, dG, A.gru_out, A.gru_saved,
-                                     G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_pair, 0, sws, swsb, stream);
+  return umpr_embed_gru_bwd_impl(ids_pair, emb, E, P[1], P[5], lengths, order, dst_row, (int)(2 * N), L, dG, A.gru_out, A.gru_saved,
+                                 G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_pair, 0, sws, swsb, gemm_b16, s);
 }
 int umpr_review_net_bwd_dx(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                            const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
                            float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
-  return review_net_bwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm, arena, d_out, G, dx_pair, ws, ws_bytes, stream);
+  return review_net_bwd(ids_pair, emb, E, P, lengths, order, order, B, S, L, b16_gemm || umpr_ambient_gemm_b16(), arena, d_out, G, dx_pair,
+                        ws, ws_bytes, stream);
 }
 int umpr_review_net_bwd_ex(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                            const int32_t* order, const int32_t* dst_row, int B, int S, int L, int b16_gemm, const void* arena,
                            const float* d_out, float* const* G, float* dx_pair, float* ws, size_t ws_bytes, void* stream) {
-  return review_net_bwd(ids_pair, emb, E, P, lengths, order, dst_row, B, S, L, b16_gemm, arena, d_out, G, dx_pair, ws, ws_bytes, stream);
+  return review_net_bwd(ids_pair, emb, E, P, lengths, order, dst_row, B, S, L, b16_gemm || umpr_ambient_gemm_b16(), arena, d_out, G, dx_pair,
+                        ws, ws_bytes, stream);
 }
 int umpr_review_net_bwd(const int64_t* ids_pair, const float* emb, int E, const float* const* P, const int32_t* lengths,
                         const int32_t* order, int B, int S, int L, int b16_gemm, const void* arena, const float* d_out,
@@ -273,7 +270,7 @@ size_t umpr_control_net_ws_bytes(int B, int S_ui, int L_ui, int S, int L, int E,
 static int control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
                            const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
-                           int V, float thr, int b16_gemm, int need_grad, void* arena, float* c_u, float* c_i, float* prefer_pos,
+                           int V, float thr, bool gemm_b16, int need_grad, void* arena, float* c_u, float* c_i, float* prefer_pos,
                            float* prefer_neg, float* ws, size_t ws_bytes, void* stream, const uint8_t* valid_ui,
                            const uint8_t* valid_pair) {
   UMPR_REQUIRE((valid_ui == nullptr) == (valid_pair == nullptr), "control_net_fwd: valid_ui and valid_pair go together");
@@ -285,30 +282,23 @@ static int control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const
   const ControlArena A = control_arena(arena, B, S_ui, L_ui, S, L, KC, V);
   const long Nui = (long)B * S_ui, N = (long)B * S;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  UmprB16Scope b16(b16_gemm);
-  if (int rc = umpr_embed_gru_bidir_fwd(ids_ui, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_ui, ord_ui, dst_ui, (int)Nui,
-                                        L_ui, A.gru_ui, need_grad ? A.saved_ui : nullptr, ws, ws_bytes, stream)) return rc;
-  if (int rc = umpr_embed_gru_bidir_fwd(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_pair, ord_pair, dst_pair,
-                                        (int)(2 * N), L, A.gru_pair, need_grad ? A.saved_pair : nullptr, ws, ws_bytes, stream)) return rc;
+  if (int rc = umpr_embed_gru_fwd_impl(ids_ui, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_ui, ord_ui, dst_ui, (int)Nui,
+                                       L_ui, A.gru_ui, need_grad ? A.saved_ui : nullptr, ws, ws_bytes, gemm_b16, s)) return rc;
+  if (int rc = umpr_embed_gru_fwd_impl(ids_pair, emb, E, P[0], P[1], P[2], P[3], P[4], P[5], P[6], P[7], len_pair, ord_pair, dst_pair,
+                                       (int)(2 * N), L, A.gru_pair, need_grad ? A.saved_pair : nullptr, ws, ws_bytes, gemm_b16, s)) return rc;
   float* Y = W.Y;   // (the GRUs above used the whole buffer)
   float* sws = W.stage; const size_t swsb = ws_bytes - W.prefix;
   const float* X[3] = {A.gru_ui, A.gru_pair, A.gru_pair + (size_t)N * L * D};
   const int ss[3] = {S_ui, S, S}, ll[3] = {L_ui, L, L};
-  if (valid_ui) {
-    const uint8_t* vv[3] = {valid_ui, valid_pair, valid_pair + (size_t)N * L};
-    for (int q = 0; q < 3; ++q)
-      if (int rc = umpr_cnet_head_fwd_masked(X[q], P[8], P[9], P[10], P[11], thr, B, ss[q], ll[q], KC, KS, V, Y, A.h[q].cmax,
-                                             A.h[q].argl, A.h[q].sp, A.h[q].vp, A.h[q].fin, vv[q], sws, swsb, stream)) return rc;
-    if (int rc = umpr_snet_fwd_masked(A.gru_ui, P[12], P[13], A.h[0].vp, V, B, S_ui, L_ui, A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, Y, D,
-                                      valid_ui, stream)) return rc;
-  } else {
-    for (int q = 0; q < 3; ++q)
-      if (int rc = umpr_cnet_head_fwd(X[q], P[8], P[9], P[10], P[11], thr, B, ss[q], ll[q], KC, KS, V, Y, A.h[q].cmax, A.h[q].argl,
-                                      A.h[q].sp, A.h[q].vp, A.h[q].fin, sws, swsb, stream)) return rc;
-    // control S-Net weighted by view_p (model.py:185); its sentiment vector is not used: written into scratch
-    if (int rc = umpr_snet_fwd(A.gru_ui, P[12], P[13], A.h[0].vp, V, B, S_ui, L_ui, A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, Y, D, stream)) return rc;
-  }
-  if (int rc = umpr_control_gate_fwd(A.sn.sa, P[14], P[15], A.h[0].vp, A.h[0].fin, B, S_ui, V, A.senti, A.vs, prefer_pos, prefer_neg, stream)) return rc;
+  // the validity bytes of the three heads' rows, or no mask at all
+  const uint8_t* vv[3] = {valid_ui, valid_pair, valid_pair ? valid_pair + (size_t)N * L : nullptr};
+  for (int q = 0; q < 3; ++q)
+    if (int rc = umpr_cnet_head_fwd_impl(X[q], P[8], P[9], P[10], P[11], thr, B, ss[q], ll[q], KC, KS, V, Y, A.h[q].cmax, A.h[q].argl,
+                                         A.h[q].sp, A.h[q].vp, A.h[q].fin, sws, swsb, gemm_b16, s, vv[q])) return rc;
+  // control S-Net weighted by view_p (model.py:185); its sentiment vector is not used: written into scratch
+  if (int rc = umpr_snet_fwd_impl(A.gru_ui, P[12], P[13], A.h[0].vp, V, B, S_ui, L_ui, A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, Y, D,
+                                  gemm_b16, s, valid_ui)) return rc;
+  if (int rc = umpr_gate_fwd_impl(A.sn.sa, P[14], P[15], A.h[0].vp, A.h[0].fin, B, S_ui, V, A.senti, A.vs, prefer_pos, prefer_neg, s)) return rc;
   if (hipMemcpyAsync(c_u, A.h[1].fin, (size_t)B * V * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
       hipMemcpyAsync(c_i, A.h[2].fin, (size_t)B * V * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
     umpr_set_error("control_net_fwd: copy failed");
@@ -321,7 +311,8 @@ int umpr_control_net_fwd(const int64_t* ids_ui, const int64_t* ids_pair, const f
                          int S_ui, int L_ui, int S, int L, int KC, int KS, int V, float thr, int b16_gemm, int need_grad, void* arena,
                          float* c_u, float* c_i, float* prefer_pos, float* prefer_neg, float* ws, size_t ws_bytes, void* stream) {
   return control_net_fwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, ord_ui, len_pair, ord_pair, ord_pair, B, S_ui, L_ui, S, L, KC, KS,
-                         V, thr, b16_gemm, need_grad, arena, c_u, c_i, prefer_pos, prefer_neg, ws, ws_bytes, stream, nullptr, nullptr);
+                         V, thr, b16_gemm || umpr_ambient_gemm_b16(), need_grad, arena, c_u, c_i, prefer_pos, prefer_neg, ws, ws_bytes,
+                         stream, nullptr, nullptr);
 }
 int umpr_control_net_fwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                             const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
@@ -330,7 +321,8 @@ int umpr_control_net_fwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, cons
                             float* prefer_neg, float* ws, size_t ws_bytes, const uint8_t* valid_ui, const uint8_t* valid_pair,
                             void* stream) {
   return control_net_fwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, dst_ui, len_pair, ord_pair, dst_pair, B, S_ui, L_ui, S, L, KC, KS,
-                         V, thr, b16_gemm, need_grad, arena, c_u, c_i, prefer_pos, prefer_neg, ws, ws_bytes, stream, valid_ui, valid_pair);
+                         V, thr, b16_gemm || umpr_ambient_gemm_b16(), need_grad, arena, c_u, c_i, prefer_pos, prefer_neg, ws, ws_bytes,
+                         stream, valid_ui, valid_pair);
 }
 
 // d_cu, d_ci, d_pp, d_pn [B][V]; grads: 16 pointers in the order of params, each overwritten
@@ -338,7 +330,7 @@ int umpr_control_net_fwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, cons
 static int control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                            const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
                            const int32_t* ord_pair, const int32_t* dst_pair, int B, int S_ui, int L_ui, int S, int L, int KC, int KS,
-                           int V, int b16_gemm, const void* arena, const float* d_cu, const float* d_ci, const float* d_pp,
+                           int V, bool gemm_b16, const void* arena, const float* d_cu, const float* d_ci, const float* d_pp,
                            const float* d_pn, float* const* G, float* dx_pair, float* dx_ui, float* ws, size_t ws_bytes, void* stream) {
   UMPR_REQUIRE((dx_pair == nullptr) == (dx_ui == nullptr), "control_net_bwd: dx_pair and dx_ui go together");
   UMPR_REQUIRE(ids_ui && ids_pair && emb && P && G && arena && d_cu && d_ci && d_pp && d_pn && dst_ui && dst_pair,
@@ -351,25 +343,25 @@ static int control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const
   hipStream_t s = static_cast<hipStream_t>(stream);
   float *dX_ui = W.dX_ui, *dX_pair = W.dX_pair, *d_sa = W.d_sa, *d_vp = W.d_vp, *d_cout = W.d_cout, *zero_senti = W.zero_senti;
   float* sws = W.stage; const size_t swsb = ws_bytes - W.prefix;
-  UmprB16Scope b16(b16_gemm);
   if (hipMemsetAsync(zero_senti, 0, (size_t)B * D * sizeof(float), s) != hipSuccess) { umpr_set_error("control_net_bwd: memset"); return -2; }
-  if (int rc = umpr_control_gate_bwd(A.sn.sa, P[14], A.h[0].vp, A.h[0].fin, A.senti, A.vs, d_pp, d_pn, B, S_ui, V, d_sa, d_vp, d_cout,
-                                     G[14], G[15], sws, swsb, stream)) return rc;
-  if (int rc = umpr_snet_bwd(A.gru_ui, P[12], P[13], A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, zero_senti, D, d_sa, B, S_ui, L_ui, V, dX_ui,
-                             G[12], G[13], nullptr, sws, swsb, stream)) return rc;
+  if (int rc = umpr_gate_bwd_impl(A.sn.sa, P[14], A.h[0].vp, A.h[0].fin, A.senti, A.vs, d_pp, d_pn, B, S_ui, V, d_sa, d_vp, d_cout,
+                                  G[14], G[15], sws, swsb, s)) return rc;
+  if (int rc = umpr_snet_bwd_impl(A.gru_ui, P[12], P[13], A.sn.U, A.sn.P, A.sn.wsum, A.sn.sa, zero_senti, D, d_sa, B, S_ui, L_ui, V, dX_ui,
+                                  G[12], G[13], nullptr, sws, swsb, gemm_b16, s)) return rc;
   const float* X[3] = {A.gru_ui, A.gru_pair, A.gru_pair + (size_t)N * L * D};
   float* dX[3] = {dX_ui, dX_pair, dX_pair + (size_t)N * L * D};
   const float* dfin[3] = {d_cout, d_cu, d_ci};
   const float* dvp[3] = {d_vp, nullptr, nullptr};
   const int ss[3] = {S_ui, S, S}, ll[3] = {L_ui, L, L};
   for (int q = 0; q < 3; ++q)   // the ui head adds onto the S-Net's dX and writes the weight gradients; the other two add onto those
-    if (int rc = umpr_cnet_head_bwd(X[q], P[8], P[10], A.h[q].cmax, A.h[q].argl, A.h[q].sp, A.h[q].vp, dfin[q], dvp[q], B, ss[q], ll[q],
-                                    KC, KS, V, dX[q], q == 0 ? 1 : 0, q == 0 ? 0 : 1, G[8], G[9], G[10], G[11], sws, swsb, stream)) return rc;
-  if (int rc = umpr_embed_gru_bidir_bwd_dx(ids_ui, emb, E, P[1], P[5], len_ui, ord_ui, dst_ui, (int)Nui, L_ui, dX_ui, A.gru_ui, A.saved_ui,
-                                           G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_ui, 0, sws, swsb, stream)) return rc;
-  return umpr_embed_gru_bidir_bwd_dx(ids_pair, emb, E, P[1], P[5], len_pair, ord_pair, dst_pair, (int)(2 * N), L, dX_pair, A.gru_pair,
-                                     A.saved_pair, G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 1, P[0], P[4], dx_pair, 0, sws, swsb,
-                                     stream);
+    if (int rc = umpr_cnet_head_bwd_impl(X[q], P[8], P[10], A.h[q].cmax, A.h[q].argl, A.h[q].sp, A.h[q].vp, dfin[q], dvp[q], B, ss[q], ll[q],
+                                         KC, KS, V, dX[q], q == 0 ? 1 : 0, q == 0 ? 0 : 1, G[8], G[9], G[10], G[11], sws, swsb, gemm_b16, s))
+      return rc;
+  if (int rc = umpr_embed_gru_bwd_impl(ids_ui, emb, E, P[1], P[5], len_ui, ord_ui, dst_ui, (int)Nui, L_ui, dX_ui, A.gru_ui, A.saved_ui,
+                                       G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 0, P[0], P[4], dx_ui, 0, sws, swsb, gemm_b16, s)) return rc;
+  return umpr_embed_gru_bwd_impl(ids_pair, emb, E, P[1], P[5], len_pair, ord_pair, dst_pair, (int)(2 * N), L, dX_pair, A.gru_pair,
+                                 A.saved_pair, G[0], G[1], G[2], G[3], G[4], G[5], G[6], G[7], 1, P[0], P[4], dx_pair, 0, sws, swsb,
+                                 gemm_b16, s);
 }
 int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                             const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,
@@ -377,7 +369,7 @@ int umpr_control_net_bwd_dx(const int64_t* ids_ui, const int64_t* ids_pair, cons
                             const float* d_ci, const float* d_pp, const float* d_pn, float* const* G, float* dx_pair, float* dx_ui,
                             float* ws, size_t ws_bytes, void* stream) {
   return control_net_bwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, ord_ui, len_pair, ord_pair, ord_pair, B, S_ui, L_ui, S, L, KC, KS,
-                         V, b16_gemm, arena, d_cu, d_ci, d_pp, d_pn, G, dx_pair, dx_ui, ws, ws_bytes, stream);
+                         V, b16_gemm || umpr_ambient_gemm_b16(), arena, d_cu, d_ci, d_pp, d_pn, G, dx_pair, dx_ui, ws, ws_bytes, stream);
 }
 int umpr_control_net_bwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                             const int32_t* len_ui, const int32_t* ord_ui, const int32_t* dst_ui, const int32_t* len_pair,
@@ -386,7 +378,7 @@ int umpr_control_net_bwd_ex(const int64_t* ids_ui, const int64_t* ids_pair, cons
                             const float* d_pn, float* const* G, float* dx_pair, float* dx_ui, float* ws, size_t ws_bytes,
                             void* stream) {
   return control_net_bwd(ids_ui, ids_pair, emb, E, P, len_ui, ord_ui, dst_ui, len_pair, ord_pair, dst_pair, B, S_ui, L_ui, S, L, KC, KS,
-                         V, b16_gemm, arena, d_cu, d_ci, d_pp, d_pn, G, dx_pair, dx_ui, ws, ws_bytes, stream);
+                         V, b16_gemm || umpr_ambient_gemm_b16(), arena, d_cu, d_ci, d_pp, d_pn, G, dx_pair, dx_ui, ws, ws_bytes, stream);
 }
 int umpr_control_net_bwd(const int64_t* ids_ui, const int64_t* ids_pair, const float* emb, int E, const float* const* P,
                          const int32_t* len_ui, const int32_t* ord_ui, const int32_t* len_pair, const int32_t* ord_pair, int B,

@@ -14,28 +14,17 @@ struct UmprGemm {
   int act = 0; bool accumulate = false; float alpha = 1.0f;
   int split_k = 1;                   // 0 = auto (needs ws)
   float* ws = nullptr; size_t ws_bytes = 0;
+  bool b16 = false;                  // operands rounded to bf16 on the way into LDS, bf16 matrix pipe, fp32 accumulation
   // Sliding-window operand (1-D convolution as a GEMM without im2col): the operand is a matrix X [rows][winD] of
   // sentences of winL rows, and its logical element (row r, column j*winD + c) is X[r + j - winPad][c], zero where
   // (r % winL) + j - winPad leaves the sentence.  winA: A [M][KS*winD] (!transA);  winB: B [K][KS*winD] (!transB).
   int winA_L = 0, winA_D = 1, winA_pad = 0;
   int winB_L = 0, winB_D = 1, winB_pad = 0;
 };
-void umpr_gemm_set_b16(int on);
-int umpr_gemm_b16();             // the calling host thread's current setting
 int umpr_gemm(const UmprGemm& g, hipStream_t stream);
-// The generic GEMM's products on the bf16 pipe while alive, where `on`; the host thread's own setting is restored on exit.
-struct UmprB16Scope {
-  int prev;
-  explicit UmprB16Scope(int on) : prev(umpr_gemm_b16()) { if (on) umpr_gemm_set_b16(1); }
-  ~UmprB16Scope() { umpr_gemm_set_b16(prev); }
-};
-
-// ... and in fp32 while alive, whatever the host thread's setting (the embedding-gradient products)
-struct UmprF32Scope {
-  int prev;
-  UmprF32Scope() : prev(umpr_gemm_b16()) { umpr_gemm_set_b16(0); }
-  ~UmprF32Scope() { umpr_gemm_set_b16(prev); }
-};
+// What umpr_set_gemm_bf16 last set on the calling host thread (api.hip).  ONLY the functions declared in include/umpr_hip.h may
+// call it, once on entry; below them GEMM precision is an argument (`gemm_b16`) and a field (UmprGemm::b16), never state.
+bool umpr_ambient_gemm_b16();
 
 constexpr int D = 128, H = 64, G3 = 192, AT = 64;   // text path: token feature 2 * gru_size, gru_size, its 3 gates, self_atte_size
 bool umpr_merge_small();   // UMPR_MERGE_SMALL=0: the review merge on the fc kernels / the generic GEMM (api.hip)
@@ -53,10 +42,10 @@ struct Carve {   // hands out pieces of one buffer, each rounded up to `align` b
 bool umpr_fc_small_ok(int M, int N, int K);
 size_t umpr_fc_small_ws_bytes(int M, int N, int K);
 int umpr_fc_small_fwd(const float* x, const float* W, const float* bias, float* out, int M, int N, int K, int act,
-                      float* ws, size_t ws_bytes, hipStream_t s, int accumulate = 0, int bf16 = 0);
+                      float* ws, size_t ws_bytes, hipStream_t s, int accumulate, int bf16);
 int umpr_fc_small_dx(const float* g, const float* W, float* dx, int M, int N, int K, float* ws, size_t ws_bytes,
-                     hipStream_t s, int bf16 = 0);
-int umpr_fc_small_dw(const float* g, const float* x, float* dW, int M, int N, int K, hipStream_t s, int bf16 = 0);
+                     hipStream_t s, int bf16);
+int umpr_fc_small_dw(const float* g, const float* x, float* dW, int M, int N, int K, hipStream_t s, int bf16);
 
 // small shared launch helpers (util.hip)
 int umpr_fill(float* p, long n, float v, hipStream_t s);
@@ -181,18 +170,33 @@ int umpr_gru_bptt(const float* dout, const float* out, const float* saved, const
                   const int* lengths, const int* order, const int* dst_row, float* dgx, float* dwhh_slab,
                   float* dbias_slab, int N, int L, hipStream_t s);
 
+// embedding + GRU (api.hip): umpr_embed_gru_bidir_fwd / _bwd_dx with the precision of the input projections and of dW_ih as an
+// argument; the two token-gradient (dx) products run in fp32 whatever it says
+int umpr_embed_gru_fwd_impl(const int64_t* ids, const float* emb, int E,
+                            const float* w_ih_f, const float* w_hh_f, const float* b_ih_f, const float* b_hh_f,
+                            const float* w_ih_r, const float* w_hh_r, const float* b_ih_r, const float* b_hh_r,
+                            const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                            float* out, float* saved, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s);
+int umpr_embed_gru_bwd_impl(const int64_t* ids, const float* emb, int E, const float* w_hh_f, const float* w_hh_r,
+                            const int32_t* lengths, const int32_t* order, const int32_t* dst_row, int N, int L,
+                            const float* dout, const float* out, const float* saved,
+                            float* dw_ih_f, float* dw_hh_f, float* db_ih_f, float* db_hh_f,
+                            float* dw_ih_r, float* dw_hh_r, float* db_ih_r, float* db_hh_r,
+                            int accumulate, const float* w_ih_f, const float* w_ih_r, float* dx, int dx_accumulate,
+                            float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s);
+
 // coattn.hip
 size_t umpr_coattn_fwd_ws_bytes(int B, int SL);
 int umpr_coattn_fwd_impl(const float* Gu, const float* Gi, const float* M, int B, int SL, float* T, float* soft_u,
                          float* soft_i, float* atte_u, long ld_u, float* atte_i, long ld_i, float* colmax, int* argcol,
-                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, hipStream_t s, int bf16_scores = 0,
+                         float* rowmax, int* argrow, float* ws, size_t ws_bytes, bool gemm_b16, int bf16_scores, hipStream_t s,
                          const uint8_t* valid_u = nullptr, const uint8_t* valid_i = nullptr);   // both or neither
 size_t umpr_coattn_bwd_ws_bytes(int B, int SL);
 int umpr_coattn_bwd_impl(const float* Gu, const float* Gi, const float* M, const float* T, const float* soft_u,
                          const float* soft_i, const float* colmax, const int* argcol, const float* rowmax,
                          const int* argrow, const float* d_atte_u, long ld_du, const float* d_atte_i, long ld_di,
                          const float* d_soft_u, const float* d_soft_i, int B, int SL, float* dGu, float* dGi, float* dM,
-                         int accumulate, float* ws, size_t ws_bytes, hipStream_t s);
+                         int accumulate, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s);
 
 // text_ops.hip
 int umpr_tanh_bwd(const float* y, const float* gy, float* gx, long n, hipStream_t s);
@@ -202,6 +206,12 @@ int umpr_review_merge_fwd_impl(const float* ru, const float* ri, const float* Wu
                                hipStream_t s);
 int umpr_review_merge_bwd_impl(const float* ru, const float* ri, const float* Wu, const float* Wi, const float* out,
                                const float* d_out, int B, float* dru, float* dri, float* dWu, float* dWi, hipStream_t s);
+// umpr_review_merge_fwd / _bwd (api.hip): the two kernels above, else the fc kernels (fp32), else the generic GEMM at gemm_b16
+int umpr_review_merge_fwd_any(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, int B, float* out,
+                              bool gemm_b16, hipStream_t s);
+int umpr_review_merge_bwd_any(const float* repr_u, const float* repr_i, const float* W_u, const float* W_i, const float* out,
+                              const float* d_out, int B, float* d_repr_u, float* d_repr_i, float* dW_u, float* dW_i, float* ws,
+                              size_t ws_bytes, bool gemm_b16, hipStream_t s);
 int umpr_relu_bwd(const float* y, const float* gy, float* gx, long n, hipStream_t s);
 size_t umpr_colsum_ws_bytes(long rows, int cols);
 int umpr_colsum(const float* src, long rows, int cols, long ld, float* dst, int accumulate, float* ws, size_t ws_bytes,
@@ -216,23 +226,23 @@ int umpr_bce_head_bwd_impl(const float* att, long ld, const float* w, const floa
 int umpr_sq_err_accumulate_impl(const float* pred, const float* label, long n, double* acc, hipStream_t s);
 int umpr_snet_fwd_impl(const float* X, const float* Ms, const float* Ws, const float* word_soft, int wl, int B, int S,
                        int L, float* U, float* P, float* wsum, float* self_atte, float* senti, long ld_senti,
-                       hipStream_t s, const uint8_t* valid = nullptr);   // valid [B][S][L] bytes: the masked softmax
+                       bool gemm_b16, hipStream_t s, const uint8_t* valid = nullptr);   // valid [B][S][L] bytes: the masked softmax
 int umpr_token_mask_impl(const int64_t* ids, const int32_t* lengths, int N, int L, long pad_id, uint8_t* valid, hipStream_t s);
 size_t umpr_snet_bwd_ws_bytes_impl(int B, int S, int L);
 int umpr_snet_bwd_impl(const float* X, const float* Ms, const float* Ws, const float* U, const float* P,
                        const float* wsum, const float* self_atte, const float* d_senti, long ld_ds,
                        const float* d_self_atte, int B, int S, int L, int wl, float* dX, float* dMs, float* dWs,
-                       float* d_word_soft, float* ws, size_t ws_bytes, hipStream_t s);
+                       float* d_word_soft, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s);
 size_t umpr_cnet_fwd_ws_bytes(int B, int S, int L, int KS);
 int umpr_cnet_head_fwd_impl(const float* X, const float* Wc, const float* bc, const float* Wl, const float* bl,
                             float thr, int B, int S, int L, int KC, int KS, int V, float* Y, float* cmax, int* argl,
-                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, hipStream_t s,
-                            const uint8_t* valid = nullptr);   // valid [B][S][L] bytes: the masked head
+                            float* sp, float* view_p, float* final_, float* ws, size_t ws_bytes, bool gemm_b16,
+                            hipStream_t s, const uint8_t* valid = nullptr);   // valid [B][S][L] bytes: the masked head
 size_t umpr_cnet_bwd_ws_bytes(int B, int S, int L, int KC, int KS, int V);
 int umpr_cnet_head_bwd_impl(const float* X, const float* Wc, const float* Wl, const float* cmax, const int* argl,
                             const float* sp, const float* view_p, const float* d_final, const float* d_view_p, int B,
                             int S, int L, int KC, int KS, int V, float* dX, int accumulate_dX, int accumulate_w, float* dWc,
-                            float* dbc, float* dWl, float* dbl, float* ws, size_t ws_bytes, hipStream_t s);
+                            float* dbc, float* dWl, float* dbl, float* ws, size_t ws_bytes, bool gemm_b16, hipStream_t s);
 int umpr_gate_fwd_impl(const float* sa, const float* w, const float* bias, const float* view_p, const float* c_out,
                        int B, int S, int V, float* senti, float* vs, float* pp, float* pn, hipStream_t s);
 size_t umpr_gate_bwd_ws_bytes(int B);
