@@ -68,6 +68,17 @@ long umpr_debug_wino_fix_count(void);
  * *v_bytes: size of the transformed input the training forward keeps in the activation arena for the weight gradient (0: none).
  * Pure host arithmetic: makes no HIP call, runs without a GPU. */
 int umpr_debug_conv3x3_plan(int pass, int N, int Cin, int Cout, int H, int W, int inference, size_t* ws_bytes, size_t* v_bytes);
+/* The same for the bf16 per-layer entry points (umpr_conv3x3_bf16_fwd / _bwd_data / _bwd_weight below): the launch of one pass,
+ * from the very functions the launchers build it with.  Returns 0 and fills out[0..9]; < 0 where the entry point would refuse the
+ * shape (umpr_last_error names the cause).  Pure host arithmetic, no HIP call.
+ *   pass 0 / 1: out[0] BN (output channels per workgroup: 64, 128 or 256), [1] nct output-channel tiles, [2] ntp pixel tiles,
+ *     [3] workgroups launched, [4] grid rule (0: nct divides 8 and an XCD keeps one channel tile; 1: channel tiles interleaved
+ *     along an XCD's slots), [5] 32-channel chunks of the reduction, [6] 1 on the 2-D pixel tile (224 / 112 maps), [7] 1 under
+ *     the ping-pong schedule, [8] bytes of scratch the pass needs, [9] 0.
+ *   pass 2: out[0] 1 on the 128 x 64 channel tile (0: 64 x 64, two k-groups), [1] nseg pixel segments, [2] ntiles channel tiles,
+ *     [3] splits, [4] segments per split, [5] segments of the last split, [6] workgroups launched (those behind `splits`
+ *     idle), [7] 1 on the wide reduce (splits >= 32; 0: linear), [8] bytes of scratch, [9] ncit input-channel tiles. */
+int umpr_debug_conv_bf16_plan(int pass, int N, int Cin, int Cout, int H, int W, long* out);
 
 /* Test aid: the gradients of one conv layer that a 2x2 max-pool follows, on the Winograd kernels whatever the plan says for the
  * shape (H, W even; f4 = 1: the 4x4 tile, H and W multiples of 4 or, data gradient only, any even size; f4 = 0: the 2x2 tile,
@@ -453,14 +464,25 @@ int umpr_maxpool2_bwd_relu(const float* x, const float* dy, float* dx, long plan
  * CB8-PF layout (umpr_amd/csrc/bf16_conv.hip: channel blocks of 8, padded-flat pixels with zero borders); a tensor of
  * N x C x H x W takes umpr_bf16_tensor_bytes(...) bytes and is produced / read back by the two converters.  Per-layer
  * entry points (parity tests): channels must be multiples of 64 (32 for a reduction), maps 224/112/56/28/14 square.
- * ws: umpr_conv3x3_bf16_ws_bytes(...) bytes of scratch (packed bf16 weights, or split-K slabs of the weight gradient). */
+ * ws: umpr_conv3x3_bf16_ws_bytes(...) bytes of scratch (packed bf16 weights, or split-K slabs of the weight gradient): the
+ * largest of what the three passes need for the shape, rounded up to 1024.  Per pass the least a call accepts is
+ *   - forward and data gradient: Cin * Cout * 18 + 1024 bytes (the packed bf16 weights), below that "weight scratch too small";
+ *   - weight gradient: splits * (9 * Cout * Cin + Cout) * 4 + 1024 bytes (one fp32 slab [Cout][Cin][9] and one bias row per
+ *     split), below that "workspace too small"; `splits` is what umpr_debug_conv_bf16_plan reports for the shape.
+ * Forward takes Cin % 32 == 0 and Cout % 64 == 0, the data gradient Cout % 32 == 0 and Cin % 64 == 0, the weight gradient both
+ * % 64 == 0; for a shape a pass refuses, umpr_conv3x3_bf16_ws_bytes covers the passes that take it.  The three conv entry points
+ * and the two pools require N, Cin, Cout (C), H, W > 0 and every pointer but bias, mask_src and db non-NULL; a call that fails a
+ * check names the cause in umpr_last_error, returns non-zero, and has launched and written nothing.  Nothing is read from ws
+ * that the call did not write, and the result does not depend on it being larger (tests/test_gpu_bf16_conv_seams.py). */
 size_t umpr_bf16_tensor_bytes(int N, int C, int H, int W);
 int umpr_bf16_from_nchw_f32(const float* x, void* y, int N, int C, int H, int W, void* stream);
 int umpr_bf16_to_nchw_f32(const void* x, float* y, int N, int C, int H, int W, void* stream);
 size_t umpr_conv3x3_bf16_ws_bytes(int N, int Cin, int Cout, int H, int W);
 int umpr_conv3x3_bf16_fwd(const void* x, const float* w, const float* bias, void* y, int N, int Cin, int H, int W,
                           int Cout, int relu, void* ws, size_t ws_bytes, void* stream);
-/* dx = conv_transpose(dy, w) [* (mask_src > 0)], mask_src in the same layout as dx */
+/* dx = conv_transpose(dy, w) [* (mask_src > 0)], mask_src in the same layout as dx.  The comparison is the fp32 entry point's:
+ * IEEE's, nothing flushed - false at +0, -0 and every negative value, true at positive bf16 subnormals.  Where it is true dx
+ * holds the bits of the unmasked call, elsewhere +0. */
 int umpr_conv3x3_bf16_bwd_data(const void* dy, const float* w, const void* mask_src /*or NULL*/, void* dx, int N,
                                int Cin, int H, int W, int Cout, void* ws, size_t ws_bytes, void* stream);
 /* dw [Cout][Cin][3][3], db [Cout] in fp32 (overwritten) */

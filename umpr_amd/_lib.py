@@ -140,6 +140,7 @@ SIGNATURES = {
     "umpr_set_conv_pool_follows": ("i", "i"),
     "umpr_debug_wino_fix_count": ("", "l"),
     "umpr_debug_conv3x3_plan": ("iiiiiiipp", "i"),
+    "umpr_debug_conv_bf16_plan": ("iiiiiip", "i"),
     "umpr_debug_wino_pool_fold": ("pppppppp" "iiiiiii" "pzp", "i"),
     "umpr_profile_enable": ("i", "i"),
     "umpr_profile_reset": ("", "i"),

@@ -137,6 +137,24 @@ int umpr_debug_conv3x3_plan(int pass, int N, int Cin, int Cout, int H_, int W, i
   if (v_bytes) *v_bytes = p.v_floats * sizeof(float);
   return p.algo;
 }
+// The same for the bf16 entry points: what umpr_conv3x3_bf16_fwd (pass 0) / _bwd_data (1) / _bwd_weight (2) would launch, from
+// the functions the launchers call.  No HIP call.  < 0 where the entry point refuses the shape (umpr_last_error names the cause).
+int umpr_debug_conv_bf16_plan(int pass, int N, int Cin, int Cout, int H_, int W, long* out) {
+  UMPR_REQUIRE(pass >= 0 && pass <= 2 && N > 0 && Cin > 0 && Cout > 0 && H_ > 0 && W > 0 && out, "conv_bf16_plan: bad arguments");
+  const UmprPF g = umpr_pf(N, H_, W);
+  if (pass < 2) {
+    UmprConvB16Plan q;
+    if (int rc = umpr_conv_bf16_plan(g, Cin, Cout, pass, &q)) return rc;
+    const long v[10] = {q.BN, q.nct, q.ntp, q.blocks, q.interleaved, q.nchunks, q.two_d, q.pingpong, (long)q.scratch, 0};
+    memcpy(out, v, sizeof(v));
+  } else {
+    UmprWgradB16Plan q;
+    if (int rc = umpr_wgrad_bf16_plan(g, Cin, Cout, &q)) return rc;
+    const long v[10] = {q.big, q.nseg, q.ntiles, q.splits, q.segs_per_split, q.last_segs, q.blocks, q.wide_reduce, (long)q.scratch, q.ncit};
+    memcpy(out, v, sizeof(v));
+  }
+  return 0;
+}
 int umpr_debug_wino_pool_fold(const float* y, const float* g_pooled, const float* w, const float* x, float* unpooled, float* dx,
                               float* dw, float* db, int N, int Cin, int Cout, int H_, int W, int f4, int fold, float* ws,
                               size_t ws_bytes, void* stream) {
@@ -1040,26 +1058,55 @@ int umpr_bf16_to_nchw_f32(const void* x, float* y, int N, int C, int H_, int W, 
   return umpr_cb8_to_nchw(x, y, umpr_pf(N, H_, W), C, S(stream));
 }
 size_t umpr_conv3x3_bf16_ws_bytes(int N, int Cin, int Cout, int H_, int W) {
+  // a shape the weight gradient refuses (channels off 64, say) still gets the scratch of the passes that take it
   const size_t a = umpr_conv_bf16_pack_bytes(Cin, Cout), b = umpr_wgrad_bf16_ws_bytes(umpr_pf(N, H_, W), Cin, Cout);
   return align_up(a > b ? a : b, 1024);
 }
+// The per-layer wrappers refuse, by name and before anything is launched or written, what the code underneath would take for
+// something else: umpr_conv_bf16_run reads w == nullptr as "the scratch already holds the packed weights" (the composite's way).
+#define UMPR_B16_REQUIRE_SHAPE(fn)                                                                           \
+  UMPR_REQUIRE(N > 0 && Cin > 0 && Cout > 0 && H_ > 0 && W > 0, fn ": N, Cin, Cout, H, W must be positive (%d, %d, %d, %d, %d)", \
+               N, Cin, Cout, H_, W)
 int umpr_conv3x3_bf16_fwd(const void* x, const float* w, const float* bias, void* y, int N, int Cin, int H_, int W,
                           int Cout, int relu, void* ws, size_t ws_bytes, void* stream) {
+  UMPR_B16_REQUIRE_SHAPE("conv3x3_bf16_fwd");
+  UMPR_REQUIRE(x, "conv3x3_bf16_fwd: x is NULL");
+  UMPR_REQUIRE(w, "conv3x3_bf16_fwd: w is NULL");
+  UMPR_REQUIRE(y, "conv3x3_bf16_fwd: y is NULL");
+  UMPR_REQUIRE(ws, "conv3x3_bf16_fwd: ws is NULL");
   return umpr_conv_bf16_run(x, w, 0, bias, nullptr, y, umpr_pf(N, H_, W), Cin, Cout, relu, ws, ws_bytes, S(stream));
 }
 int umpr_conv3x3_bf16_bwd_data(const void* dy, const float* w, const void* mask_src, void* dx, int N, int Cin, int H_,
                                int W, int Cout, void* ws, size_t ws_bytes, void* stream) {
+  UMPR_B16_REQUIRE_SHAPE("conv3x3_bf16_bwd_data");
+  UMPR_REQUIRE(dy, "conv3x3_bf16_bwd_data: dy is NULL");
+  UMPR_REQUIRE(w, "conv3x3_bf16_bwd_data: w is NULL");
+  UMPR_REQUIRE(dx, "conv3x3_bf16_bwd_data: dx is NULL");
+  UMPR_REQUIRE(ws, "conv3x3_bf16_bwd_data: ws is NULL");
   return umpr_conv_bf16_run(dy, w, 1, nullptr, mask_src, dx, umpr_pf(N, H_, W), Cin, Cout, 0, ws, ws_bytes, S(stream));
 }
 int umpr_conv3x3_bf16_bwd_weight(const void* dy, const void* x, float* dw, float* db, int N, int Cin, int H_, int W,
                                  int Cout, void* ws, size_t ws_bytes, void* stream) {
+  UMPR_B16_REQUIRE_SHAPE("conv3x3_bf16_bwd_weight");
+  UMPR_REQUIRE(dy, "conv3x3_bf16_bwd_weight: dy is NULL");
+  UMPR_REQUIRE(x, "conv3x3_bf16_bwd_weight: x is NULL");
+  UMPR_REQUIRE(dw, "conv3x3_bf16_bwd_weight: dw is NULL");
+  UMPR_REQUIRE(ws, "conv3x3_bf16_bwd_weight: ws is NULL");
   return umpr_wgrad_bf16_run(dy, x, dw, db, umpr_pf(N, H_, W), Cin, Cout, 0, static_cast<float*>(ws), ws_bytes, S(stream));
 }
+#undef UMPR_B16_REQUIRE_SHAPE
 int umpr_maxpool2_bf16_fwd(const void* x, void* y, int N, int C, int H_, int W, void* stream) {
+  UMPR_REQUIRE(N > 0 && C > 0 && H_ > 0 && W > 0, "maxpool2_bf16_fwd: N, C, H, W must be positive (%d, %d, %d, %d)", N, C, H_, W);
+  UMPR_REQUIRE(x, "maxpool2_bf16_fwd: x is NULL");
+  UMPR_REQUIRE(y, "maxpool2_bf16_fwd: y is NULL");
   UMPR_REQUIRE((H_ % 2) == 0 && (W % 2) == 0 && (C % 8) == 0, "maxpool2_bf16: bad shape");
   return umpr_maxpool2_bf16_fwd_run(x, y, umpr_pf(N, H_, W), umpr_pf(N, H_ / 2, W / 2), C, S(stream));
 }
 int umpr_maxpool2_bf16_bwd_relu(const void* x, const void* dy, void* dx, int N, int C, int H_, int W, void* stream) {
+  UMPR_REQUIRE(N > 0 && C > 0 && H_ > 0 && W > 0, "maxpool2_bf16_bwd_relu: N, C, H, W must be positive (%d, %d, %d, %d)", N, C, H_, W);
+  UMPR_REQUIRE(x, "maxpool2_bf16_bwd_relu: x is NULL");
+  UMPR_REQUIRE(dy, "maxpool2_bf16_bwd_relu: dy is NULL");
+  UMPR_REQUIRE(dx, "maxpool2_bf16_bwd_relu: dx is NULL");
   UMPR_REQUIRE((H_ % 2) == 0 && (W % 2) == 0 && (C % 8) == 0, "maxpool2_bf16: bad shape");
   return umpr_maxpool2_bf16_bwd_run(x, dy, dx, umpr_pf(N, H_, W), umpr_pf(N, H_ / 2, W / 2), C, S(stream));
 }

@@ -83,6 +83,11 @@ struct ConvB16Params {
                                  // after ptot, per plane), a slice per pixel tile - saves a launch per layer in the backward
 };
 
+// The two grid rules of the forward / data-gradient kernel (decoded in the kernel, sized in umpr_conv_bf16_plan): where the number
+// of output-channel tiles divides 8 an XCD (workgroups b, b + 8, ...) works on one channel tile; any other count interleaves the
+// channel tiles along the slots of an XCD, eight pixel tiles per round.
+__host__ __device__ __forceinline__ bool conv_grid_interleaved(int nct) { return !(nct <= 8 && (8 % nct) == 0); }
+
 // guard pixels [g0, g1) of the zlead + ztail guard pixels of each of this channel tile's planes
 template <int BN, int NT>
 __device__ __forceinline__ void zero_guard_slice(const ConvB16Params& p, int ct, long pt, int tid) {
@@ -146,7 +151,7 @@ __global__ __launch_bounds__(64 * WP * WC, (WP * WC == 4 ? 2 : 1)) void conv_bf1
   const int xcd = blockIdx.x & 7;
   const long slot = blockIdx.x >> 3;
   int ct; long pt;
-  if (p.nct <= 8 && (8 % p.nct) == 0) { const int g = 8 / p.nct; ct = xcd / g; pt = slot * g + (xcd % g); }
+  if (!conv_grid_interleaved(p.nct)) { const int g = 8 / p.nct; ct = xcd / g; pt = slot * g + (xcd % g); }
   else { ct = (int)(slot % p.nct); pt = (slot / p.nct) * 8 + xcd; }
   if (pt >= p.ntp) return;
 
@@ -1113,20 +1118,21 @@ inline int grid_for(long n, int cap) {
   return (int)(b < 1 ? 1 : b);
 }
 
+// pixel tile per map width: TR rows x TC real columns on the 224 / 112 maps, TC consecutive flat pixels (TR = 0) below
+constexpr int conv_tr(int W) { return W == 224 ? 8 : W == 112 ? 16 : 0; }
+constexpr int conv_tc(int W) { return W == 224 ? 32 : W == 112 ? 16 : 256; }
 // Ping-pong schedule in the 8-wave forward / dgrad kernels where it measured faster - the 256-channel tiles (wave tile
 // 128 x 64, 32 MFMAs per phase: +8-10 %, 512->512@28 1158 TF) and the 1-D 128-channel tiles (+3-5 %); the 2-D 128-channel
 // tiles of the 112 x 112 maps (16 MFMAs per phase) lose 15 % to the second barrier (profiles/r02_u_pp_ab.txt).
+constexpr bool conv_pp(int BN, int TR) { return BN != 64 && (BN == 256 || TR == 0); }   // the 64-channel tile runs four waves
+
 template <int W, int TR, int TC, int BN, int WP, int WC>
-void launch_conv(ConvB16Params p, hipStream_t s) {
-  constexpr int BM = TR > 0 ? TR * TC : TC;
-  constexpr bool PP = WP * WC == 8 && (BN == 256 || TR == 0);
-  if (TR > 0) p.ntp = ((p.rows + TR - 1) / TR) * (W / TC);
-  else p.ntp = (p.ptot + BM - 1) / BM;
-  p.nct = p.M / BN;
-  long blocks;
-  if (p.nct <= 8 && (8 % p.nct) == 0) { const int g = 8 / p.nct; blocks = ((p.ntp + g - 1) / g) * 8; }
-  else blocks = ((p.ntp + 7) / 8) * 8 * p.nct;
-  conv_bf16_m16_kernel<W, TR, TC, BN, WP, WC, PP><<<dim3((unsigned)blocks), 64 * WP * WC, 0, s>>>(p);
+void launch_conv(ConvB16Params p, const UmprConvB16Plan& q, hipStream_t s) {
+  static_assert(TR == conv_tr(W) && TC == conv_tc(W), "the plan sizes the grid for this tile");
+  constexpr bool PP = conv_pp(BN, TR);
+  p.ntp = q.ntp;
+  p.nct = q.nct;
+  conv_bf16_m16_kernel<W, TR, TC, BN, WP, WC, PP><<<dim3((unsigned)q.blocks), 64 * WP * WC, 0, s>>>(p);
 }
 
 // tile choice per map width and output-channel count:
@@ -1141,45 +1147,69 @@ int conv_bn_for(int M, int W) {
   return M % 128 == 0 ? 128 : 64;
 }
 
-template <int W, int TR, int TC>
-int dispatch_conv_w(const ConvB16Params& p, hipStream_t s) {
-  const int BN = conv_bn_for(p.M, W);
-  if (BN == 256) launch_conv<W, TR, TC, 256, 2, 4>(p, s);
-  else if (BN == 128) launch_conv<W, TR, TC, 128, 4, 2>(p, s);
-  else if (p.M % 64 == 0) launch_conv<W, TR, TC, 64, 4, 1>(p, s);
-  else return -1;
-  return 0;
+template <int W>
+void dispatch_conv_w(const ConvB16Params& p, const UmprConvB16Plan& q, hipStream_t s) {
+  constexpr int TR = conv_tr(W), TC = conv_tc(W);
+  if (q.BN == 256) launch_conv<W, TR, TC, 256, 2, 4>(p, q, s);
+  else if (q.BN == 128) launch_conv<W, TR, TC, 128, 4, 2>(p, q, s);
+  else launch_conv<W, TR, TC, 64, 4, 1>(p, q, s);
 }
 
 constexpr int kWgradB16Wgs = 256;   // workgroups per launch the split-K factor aims at: one per CU (LDS admits one)
 
-// segment / tile / split-K plan of a weight-gradient launch (shared by the workspace query and the launch)
-struct WgradPlan { bool big; long nseg; int ntiles, ncit, splits, segs_per_split; };
-WgradPlan wgrad_plan(const UmprPF& g, int Cin, int Cout) {
-  WgradPlan q;
-  q.big = (Cout % 128 == 0);                       // 128 co x 64 ci tiles; else 64 x 64 with two k-split wave groups
-  const int tco = q.big ? 128 : 64, tci = 64;
-  if (g.W == 224) q.nseg = ((g.rows + 3) / 4) * (224 / 32);        // 2-D segments 4 rows x 32 columns
-  else if (g.W == 112) q.nseg = ((g.rows + 7) / 8) * (112 / 16);   // 8 x 16
-  else q.nseg = (g.ptot + 127) / 128;                              // 128 consecutive flat pixels
-  q.ncit = Cin / tci;
-  q.ntiles = (Cout / tco) * q.ncit;
-  int splits = (kWgradB16Wgs + q.ntiles - 1) / q.ntiles;
-  splits = (splits + 7) / 8 * 8;
-  if (splits > q.nseg) splits = (int)q.nseg;
-  q.segs_per_split = (int)((q.nseg + splits - 1) / splits);
-  q.splits = (int)((q.nseg + q.segs_per_split - 1) / q.segs_per_split);
-  return q;
-}
+bool vgg_map(const UmprPF& g) { return g.H == g.W && (g.W == 224 || g.W == 112 || g.W == 56 || g.W == 28 || g.W == 14); }
 
 template <int W, int TR, int TC, int WCO, int WCI, int KSW>
-void launch_wgrad(WgradB16Params p, const WgradPlan& q, hipStream_t s) {
+void launch_wgrad(WgradB16Params p, const UmprWgradB16Plan& q, hipStream_t s) {
   p.nseg = q.nseg; p.ncit = q.ncit; p.ntiles = q.ntiles; p.splits = q.splits; p.segs_per_split = q.segs_per_split;
-  const long blocks = (long)((q.splits + 7) / 8) * 8 * q.ntiles;
-  wgrad_bf16_m16_kernel<W, TR, TC, WCO, WCI, KSW><<<dim3((unsigned)blocks), 64 * WCO * WCI * KSW, 0, s>>>(p);
+  wgrad_bf16_m16_kernel<W, TR, TC, WCO, WCI, KSW><<<dim3((unsigned)q.blocks), 64 * WCO * WCI * KSW, 0, s>>>(p);
 }
 
 }  // namespace
+
+// Tile, grid and scratch of a forward (transposed = 0) or data-gradient (1) launch - what umpr_conv_bf16_run launches and
+// what umpr_debug_conv_bf16_plan reports.  Refuses, by name, the shapes the kernels have no tile for.  Pure host arithmetic.
+int umpr_conv_bf16_plan(const UmprPF& g, int Cin, int Cout, int transposed, UmprConvB16Plan* q) {
+  const int M = transposed ? Cin : Cout, C = transposed ? Cout : Cin;
+  UMPR_REQUIRE(C > 0 && M > 0 && C % 32 == 0 && M % 64 == 0, "conv_bf16: channels (%d -> %d) must be multiples of 32 / 64", C, M);
+  UMPR_REQUIRE(vgg_map(g), "conv_bf16: map %dx%d is not a VGG16 map size", g.H, g.W);
+  const int TR = conv_tr(g.W), TC = conv_tc(g.W);
+  q->BN = conv_bn_for(M, g.W);
+  q->nct = M / q->BN;
+  q->ntp = TR > 0 ? ((g.rows + TR - 1) / TR) * (g.W / TC) : (g.ptot + TC - 1) / TC;
+  q->interleaved = conv_grid_interleaved(q->nct);
+  if (!q->interleaved) { const int grp = 8 / q->nct; q->blocks = ((q->ntp + grp - 1) / grp) * 8; }
+  else q->blocks = ((q->ntp + 7) / 8) * 8 * q->nct;
+  q->nchunks = C / 32;
+  q->two_d = TR > 0;
+  q->pingpong = conv_pp(q->BN, TR);
+  q->scratch = umpr_conv_bf16_pack_bytes(Cin, Cout);
+  return 0;
+}
+
+// Segment / tile / split-K plan and scratch of a weight-gradient launch (shared by the workspace query, the launch and
+// umpr_debug_conv_bf16_plan); refuses as umpr_conv_bf16_plan does.
+int umpr_wgrad_bf16_plan(const UmprPF& g, int Cin, int Cout, UmprWgradB16Plan* q) {
+  UMPR_REQUIRE(Cin > 0 && Cout > 0 && Cin % 64 == 0 && Cout % 64 == 0, "wgrad_bf16: channels (%d, %d) must be multiples of 64", Cin, Cout);
+  UMPR_REQUIRE(vgg_map(g), "wgrad_bf16: map %dx%d is not a VGG16 map size", g.H, g.W);
+  q->big = (Cout % 128 == 0);                      // 128 co x 64 ci tiles; else 64 x 64 with two k-split wave groups
+  const int tco = q->big ? 128 : 64, tci = 64;
+  if (g.W == 224) q->nseg = ((g.rows + 3) / 4) * (224 / 32);        // 2-D segments 4 rows x 32 columns
+  else if (g.W == 112) q->nseg = ((g.rows + 7) / 8) * (112 / 16);   // 8 x 16
+  else q->nseg = (g.ptot + 127) / 128;                              // 128 consecutive flat pixels
+  q->ncit = Cin / tci;
+  q->ntiles = (Cout / tco) * q->ncit;
+  int splits = (kWgradB16Wgs + q->ntiles - 1) / q->ntiles;
+  splits = (splits + 7) / 8 * 8;
+  if (splits > q->nseg) splits = (int)q->nseg;
+  q->segs_per_split = (int)((q->nseg + splits - 1) / splits);
+  q->splits = (int)((q->nseg + q->segs_per_split - 1) / q->segs_per_split);
+  q->last_segs = (int)(q->nseg - (long)(q->splits - 1) * q->segs_per_split);
+  q->blocks = (long)((q->splits + 7) / 8) * 8 * q->ntiles;          // whole rounds of 8 splits: the tail idles
+  q->wide_reduce = q->splits >= 32;
+  q->scratch = (size_t)q->splits * ((size_t)9 * Cout * Cin + Cout) * sizeof(float) + 1024;
+  return 0;
+}
 
 // ---- internal host entry points ----------------------------------------------------------------------------------
 size_t umpr_conv_bf16_pack_bytes(int Cin, int Cout) { return (size_t)Cin * Cout * 9 * sizeof(bf16_t) + 1024; }
@@ -1212,11 +1242,10 @@ int umpr_conv_bf16_run(const void* x, const float* w, int transposed, const floa
                        const UmprPF& g, int Cin, int Cout, int relu, void* wpack, size_t wpack_bytes, hipStream_t s,
                        bool zero_guards) {
   const int M = transposed ? Cin : Cout, C = transposed ? Cout : Cin;
-  UMPR_REQUIRE(C % 32 == 0 && M % 64 == 0, "conv_bf16: channels (%d -> %d) must be multiples of 32 / 64", C, M);
-  UMPR_REQUIRE(g.H == g.W && (g.W == 224 || g.W == 112 || g.W == 56 || g.W == 28 || g.W == 14),
-               "conv_bf16: map %dx%d is not a VGG16 map size", g.H, g.W);
-  UMPR_REQUIRE(wpack_bytes >= umpr_conv_bf16_pack_bytes(Cin, Cout), "conv_bf16: weight scratch too small");
-  const int BN = conv_bn_for(M, g.W);
+  UmprConvB16Plan q;
+  if (int rc = umpr_conv_bf16_plan(g, Cin, Cout, transposed, &q)) return rc;
+  UMPR_REQUIRE(wpack_bytes >= q.scratch, "conv_bf16: weight scratch too small");
+  const int BN = q.BN;
   bf16_t* wp = static_cast<bf16_t*>(wpack);
   if (w) {   // w == nullptr: wpack already holds this layer's packed weights (umpr_conv_bf16_pack_all)
     pack_weights_bf16_kernel<<<grid_for((long)M * C * 9, 2048), 256, 0, s>>>(w, wp, M, C, Cin, BN, transposed);
@@ -1232,36 +1261,33 @@ int umpr_conv_bf16_run(const void* x, const float* w, int transposed, const floa
   p.y = y0 + g.lead * 8; p.yps = g.ps;
   p.C = C; p.M = M; p.H = g.H; p.ptot = g.ptot; p.rows = g.rows; p.relu = relu; p.nct = 0; p.ntp = 0;
   UmprProfScope prof(transposed ? UMPR_K_B16_DGRAD : UMPR_K_B16_FWD, 2.0 * (double)g.ptot * M * C * 9, s);
-  int rc;
   switch (g.W) {
-    case 224: rc = dispatch_conv_w<224, 8, 32>(p, s); break;
-    case 112: rc = dispatch_conv_w<112, 16, 16>(p, s); break;
-    case 56: rc = dispatch_conv_w<56, 0, 256>(p, s); break;
-    case 28: rc = dispatch_conv_w<28, 0, 256>(p, s); break;
-    default: rc = dispatch_conv_w<14, 0, 256>(p, s); break;
+    case 224: dispatch_conv_w<224>(p, q, s); break;
+    case 112: dispatch_conv_w<112>(p, q, s); break;
+    case 56: dispatch_conv_w<56>(p, q, s); break;
+    case 28: dispatch_conv_w<28>(p, q, s); break;
+    default: dispatch_conv_w<14>(p, q, s); break;
   }
-  UMPR_REQUIRE(rc == 0, "conv_bf16: unsupported channel count %d", M);
   UMPR_LAUNCH_CHECK("conv_bf16");
   return 0;
 }
 
+// 0 for a shape the weight gradient refuses (a size query has no error channel; the run itself names the cause)
 size_t umpr_wgrad_bf16_ws_bytes(const UmprPF& g, int Cin, int Cout) {
-  const WgradPlan q = wgrad_plan(g, Cin, Cout);
-  return (size_t)q.splits * ((size_t)9 * Cout * Cin + Cout) * sizeof(float) + 1024;
+  UmprWgradB16Plan q;
+  return umpr_wgrad_bf16_plan(g, Cin, Cout, &q) ? 0 : q.scratch;
 }
 
 // dw [Cout][Cin][3][3], db [Cout] (fp32, overwritten or accumulated) from dy, x in CB8-PF (start-of-plane pointers)
 int umpr_wgrad_bf16_run(const void* dy, const void* x, float* dw, float* db, const UmprPF& g, int Cin, int Cout,
                         int accumulate, float* ws, size_t ws_bytes, hipStream_t s) {
-  UMPR_REQUIRE(Cin % 64 == 0 && Cout % 64 == 0, "wgrad_bf16: channels (%d, %d) must be multiples of 64", Cin, Cout);
-  UMPR_REQUIRE(g.H == g.W && (g.W == 224 || g.W == 112 || g.W == 56 || g.W == 28 || g.W == 14),
-               "wgrad_bf16: map %dx%d is not a VGG16 map size", g.H, g.W);
-  UMPR_REQUIRE(ws_bytes >= umpr_wgrad_bf16_ws_bytes(g, Cin, Cout), "wgrad_bf16: workspace too small");
+  UmprWgradB16Plan q;
+  if (int rc = umpr_wgrad_bf16_plan(g, Cin, Cout, &q)) return rc;
+  UMPR_REQUIRE(ws_bytes >= q.scratch, "wgrad_bf16: workspace too small");
   WgradB16Params p;
   p.dy = static_cast<const bf16_t*>(dy) + g.lead * 8; p.dps = g.ps;
   p.x = static_cast<const bf16_t*>(x) + g.lead * 8; p.xps = g.ps;
   p.slab = ws; p.Cin = Cin; p.Cout = Cout;
-  const WgradPlan q = wgrad_plan(g, Cin, Cout);
   p.bslab = db ? ws + (size_t)q.splits * 9 * Cout * Cin : nullptr;
   {
     UmprProfScope prof(UMPR_K_B16_WGRAD, 2.0 * (double)g.ptot * Cout * Cin * 9, s);
@@ -1285,7 +1311,7 @@ int umpr_wgrad_bf16_run(const void* dy, const void* x, float* dw, float* db, con
   }
   UMPR_LAUNCH_CHECK("wgrad_bf16");
   const long per = (long)9 * Cout * Cin;
-  if (q.splits >= 32) {
+  if (q.wide_reduce) {
     const long cols = per / 4 + (db ? (Cout + 3) / 4 : 0);
     wgrad_reduce_wide_kernel<<<(unsigned)((cols + 63) / 64), 1024, 0, s>>>(ws, db ? p.bslab : nullptr, q.splits, per, Cout, dw,
                                                                           db, accumulate);

@@ -139,6 +139,26 @@ struct UmprPF {      // padded-flat geometry of N images of H x W
 UmprPF umpr_pf(int N, int H, int W);
 size_t umpr_pf_bytes(const UmprPF& g, int C);
 size_t umpr_conv_bf16_pack_bytes(int Cin, int Cout);
+// What a forward / data-gradient launch and a weight-gradient launch are built from; each comes from ONE function that the
+// launcher and umpr_debug_conv_bf16_plan (api.hip) both call.
+struct UmprConvB16Plan {
+  int BN, nct;           // output channels per workgroup, output-channel tiles
+  long ntp, blocks;      // pixel tiles, workgroups launched (the grid rule's round-up included)
+  int interleaved;       // grid rule: 0 one channel tile per XCD group (nct divides 8), 1 channel tiles interleaved
+  int nchunks;           // 32-channel chunks of the reduction
+  int two_d, pingpong;   // 2-D pixel tile (224 / 112 maps); ping-pong schedule
+  size_t scratch;        // bytes of packed weights
+};
+struct UmprWgradB16Plan {
+  bool big;              // 128 x 64 channel tile; else 64 x 64 with two k-groups
+  long nseg;             // pixel segments
+  int ntiles, ncit, splits, segs_per_split, last_segs;   // last_segs: segments of the last split
+  long blocks;           // workgroups launched; those behind `splits` idle
+  bool wide_reduce;      // splits >= 32
+  size_t scratch;        // bytes of split-K slabs and bias rows
+};
+int umpr_conv_bf16_plan(const UmprPF& g, int Cin, int Cout, int transposed, UmprConvB16Plan* q);
+int umpr_wgrad_bf16_plan(const UmprPF& g, int Cin, int Cout, UmprWgradB16Plan* q);
 int umpr_conv_bf16_run(const void* x, const float* w, int transposed, const float* bias, const void* mask, void* y,
                        const UmprPF& g, int Cin, int Cout, int relu, void* wpack, size_t wpack_bytes, hipStream_t s,
                        bool zero_guards = true);
